@@ -21,10 +21,15 @@ while new blocks are allocated every frame.
                         raycast from the previous TRACKED pose, then fused and raycast at the
                         tracked pose; the ground truth only scores the result
 
-The default run prints ONE JSON line for `rgbd` that also carries the other two workloads
-under "other_workloads" (same loop, same sizes, fewer steps).
+A plain run sets up, runs W untimed and K timed steps and prints ONE JSON line: `value` (frames/s
+of the K timed steps) and `ms_per_step`. `--full` adds everything else the line can carry: for
+`rgbd` the other two workloads under "other_workloads" (same loop, same sizes, fewer steps), the
+spread over further windows of K steps, the roofline and the probes, the CPU baseline, and at
+N > 1 the rig step below. `--dump-outputs DIR` writes what the last timed step computed (the
+raycast images, the frame's normals, the pose) as DIR/<name>.npy; the inputs are closed forms, the
+same in every run with the same arguments.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 N > 1: `python bench.py --gpus N` starts its own N ranks (fresh child processes, one per
 GPU, before anything touches the GPU); under an external launcher (torchrun: RANK /
@@ -33,7 +38,7 @@ frames (weak scaling, no data-path collective: SURVEY.md §8e); value = frames o
 / max-over-ranks time. After the timed loop the ranks run the one step of the path that
 does exchange data — the rigid multi-camera rig of configs[4]: per rank the ICP normal
 system of its own view, one 48-float all-reduce over RCCL per Gauss-Newton iteration, the
-same solve on every rank — and report it under "collective".
+same solve on every rank — and report it under "collective" (--full).
 
 `roofline`: the dominant kernel of the workload (the fused integrate kernel), timed with HIP
 events on the launch stream inside the timed region; `cpu_baseline`: the CPU oracle on a
@@ -688,6 +693,34 @@ def run_sequences(workload, count, warmup, steps, room=None, stride=60):
     return out, multi
 
 
+def loop_outputs(loop):
+    """What a caller of the timed step holds after the loop's last step, on the host: the raycast (Tracer::Trace's depth,
+    and for the colour workloads its shaded colour; its normals unless they are left to the next frame's pyramid launch),
+    the input frame's normals (Frame::ComputeNormals) and the pose the frame was fused and raycast at (rgbd-icp: the
+    tracked pose)."""
+    images = {"raycast_depth": loop.key.depth}
+    if loop.workload != "depth":
+        images["raycast_color"] = loop.key.color
+        images["frame_normals"] = loop.frame.normals
+    if not loop.key_normals_pending:
+        images["raycast_normals"] = loop.key.normals
+    out = {name: t.float().cpu().numpy() for name, t in images.items()}
+    out["pose"] = loop.T.Transform.from_buffer_copy(bytes(loop.kdesc.depth_to_world)).matrix().astype(np.float64)
+    return out
+
+
+def write_outputs(path, arrays, cap=64 << 20):
+    """DIR/<name>.npy for every array; past `cap` bytes in all, each array is replaced by the same fixed, seeded sample of
+    its elements (flattened), in proportion to its size."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > cap:
+            keep = max(1, int(a.size * (cap - 4096 * len(arrays)) / total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def visible_counts(poses, depths=None):
     """Allocation depends only on the depth image and the pose and is deterministic, so an
     untimed replay of SetView over the same poses gives the visible-block count every
@@ -711,16 +744,17 @@ def visible_counts(poses, depths=None):
 
 
 def run_workload(workload, poses, warmup, steps, vd, with_roofline, sample_frames=0, stream_input=False, requests_ahead=None,
-                 windows=1, room=None):
+                 windows=1, room=None, after_timed=None):
     """W untimed + K timed frames (+ `windows` - 1 further windows of K frames of the same sequence, each bracketed like the
     first: the spread of the headline) (+ `sample_frames` untimed frames with event brackets: the roofline sample);
-    returns the JSON fields of that workload."""
+    returns the JSON fields of that workload. `after_timed(loop)` is called once the K timed frames are done, before
+    anything else runs on the loop."""
     import torch
     from vulcan_amd import vk_types as T
     import scenes
     sequence = None
     if workload == "rgbd-icp":
-        need = warmup + steps * windows + sample_frames
+        need = warmup + steps * windows + max(1, sample_frames)
         sequence = room.view(0, need) if room is not None else RoomSequence(need, T.Projection.make(*scenes.APP_INTRINSICS))
     loop = FrameLoop(workload, poses, sequence=sequence, stream_input=stream_input, requests_ahead=requests_ahead)
 
@@ -737,6 +771,8 @@ def run_workload(workload, poses, warmup, steps, vd, with_roofline, sample_frame
     elapsed = vd.max_over_ranks(local, device="cuda")
     frames_all = vd.sum_over_ranks(steps, device="cuda")
     per_rank_ms = vd.gather_over_ranks(1e3 * local / steps, device="cuda")      # value uses the max; these say who was slow
+    if after_timed is not None:
+        after_timed(loop)
 
     # The spread (a 20-step headline rests on 1.6 ms of wall time): the sequence simply continues for
     # `windows` - 1 further windows of K frames, each between its own barrier + synchronise pair and each the max over
@@ -1286,9 +1322,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-oracle sample budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline as well: the windows' spread, the roofline sample and the "
+                         "per-kernel figures, the other workloads, probes, the past-L3 pass, the CPU baseline and, at N > 1, "
+                         "the rig step (a plain run sets up, warms up, times --steps frames and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (the raycast images, the frame's normals, the pose it was "
+                         "fused at) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU-oracle sample budget (0 = skip)")
     ap.add_argument("--workload", default="rgbd", choices=["rgbd", "depth", "rgbd-icp"])
-    ap.add_argument("--only", action="store_true", help="skip the other workloads, probes and the past-L3 pass")
+    ap.add_argument("--only", action="store_true", help="--full: skip the other workloads, probes and the past-L3 pass")
     ap.add_argument("--stream-input", action="store_true",
                     help="also run the headline workload with the frame's depth + colour images uploaded over PCIe every frame "
                          "(reported under other_workloads, never instead of the headline)")
@@ -1339,36 +1382,50 @@ def main():
         assert world == 1, "--sequences is a single-GPU measurement"
         room = RoomSequence(args.warmup + args.steps + 60 * (args.sequences - 1), T.Projection.make(*scenes.APP_INTRINSICS)) \
             if args.workload == "rgbd-icp" else None
-        o, _ = run_sequences(args.workload, args.sequences, args.warmup, args.steps, room=room)
+        o, multi = run_sequences(args.workload, args.sequences, args.warmup, args.steps, room=room)
         o.update(metric=METRIC + f", {args.sequences} independent sequences on one GPU", n_gpus=1, higher_is_better=True, dtype="f32",
                  data="synthetic", ms_per_step=o["ms_per_frame_of_one_sequence"])
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, {f"seq{j}_{name}": a for j, loop in enumerate(multi.loops)
+                                              for name, a in loop_outputs(loop).items()})
         emit(o)
         vd.shutdown()
         return
-    windows = max(1, min(WINDOWS, (SEQUENCE_FRAMES - args.warmup - ROOFLINE_SAMPLE_FRAMES) // max(1, args.steps)))
+    # a plain run times --steps frames and prints the headline; --full adds the windows' spread and the roofline sample
+    # behind them (and, further down, everything else the line reports)
+    full = args.full
+    windows = max(1, min(WINDOWS, (SEQUENCE_FRAMES - args.warmup - ROOFLINE_SAMPLE_FRAMES) // max(1, args.steps))) if full else 1
+    sample_frames = ROOFLINE_SAMPLE_FRAMES if full else 0
     timed_frames = args.steps * windows
-    total = args.warmup + timed_frames + ROOFLINE_SAMPLE_FRAMES
+    # (a plain run still has the pose after its last frame: that frame is the step every other timed frame is, its raycast
+    # making the next frame's request pass)
+    total = args.warmup + timed_frames + (sample_frames if full else 1)
     # every rank walks the same arc, offset so ranks do not share poses (one degree per rank: the last rank of eight still
     # stays inside the frames the app's pool takes, SEQUENCE_FRAMES)
     poses = [scenes.orbit_pose(i + rank * 2, YAW_STEP) for i in range(total)]
     wl = args.workload
-    res, loop = run_workload(wl, poses, args.warmup, args.steps, vd, with_roofline=True, sample_frames=ROOFLINE_SAMPLE_FRAMES,
-                             windows=windows)
+    outputs = {}
+    res, loop = run_workload(wl, poses, args.warmup, args.steps, vd, with_roofline=full, sample_frames=sample_frames,
+                             windows=windows, after_timed=(lambda lp: outputs.update(loop_outputs(lp)))
+                             if args.dump_outputs and rank == 0 else None)
+    if outputs:
+        write_outputs(args.dump_outputs, outputs)
 
     tracked, depths = res.pop("_tracked", None), res.pop("_depths", None)
-    nvis, rounds_per_frame = visible_counts(tracked or poses, depths)
-    nvis_timed = nvis[args.warmup:]                   # the timed frames (every window), then the roofline sample's
-    image_bytes = IMAGE_BYTES["depth" if wl == "depth" else "rgbd"]
-    alg = nvis_timed * BYTES_PER_BLOCK + image_bytes
-    sampled = res.pop("_sampled")
-    integ_ms, trace_ms = np.array(res.pop("_integrate_ms")), np.array(res.pop("_trace_ms"))
-    achieved = float(alg[sampled].sum() / (integ_ms.sum() * 1e-3) / 1e9)
-    bracket_ms, bracketed = np.array(res.pop("_bracket_ms")), res.pop("_bracketed")
-    by_bracket = float(alg[bracketed].sum() / (bracket_ms.sum() * 1e-3) / 1e9) if len(bracketed) else None
     ctr = res.pop("_counters")
-    pair_us = res.pop("_event_pair_us")
-    frame_bytes = float(alg[:args.steps].mean())
-    voxel_ws = float(nvis_timed[:args.steps].mean()) * 10240
+    if full:
+        nvis, rounds_per_frame = visible_counts(tracked or poses, depths)
+        nvis_timed = nvis[args.warmup:]                   # the timed frames (every window), then the roofline sample's
+        image_bytes = IMAGE_BYTES["depth" if wl == "depth" else "rgbd"]
+        alg = nvis_timed * BYTES_PER_BLOCK + image_bytes
+        sampled = res.pop("_sampled")
+        integ_ms, trace_ms = np.array(res.pop("_integrate_ms")), np.array(res.pop("_trace_ms"))
+        achieved = float(alg[sampled].sum() / (integ_ms.sum() * 1e-3) / 1e9)
+        bracket_ms, bracketed = np.array(res.pop("_bracket_ms")), res.pop("_bracketed")
+        by_bracket = float(alg[bracketed].sum() / (bracket_ms.sum() * 1e-3) / 1e9) if len(bracketed) else None
+        pair_us = res.pop("_event_pair_us")
+        frame_bytes = float(alg[:args.steps].mean())
+        voxel_ws = float(nvis_timed[:args.steps].mean()) * 10240
 
     sphere = ", camera at the centre of a 2 m sphere yawing 0.5 deg/frame"
     names = {"rgbd": "BASELINE configs[2] fusion+raycast: 640x480 RGB-D, Frame::ComputeNormals + SetView x3 + LightIntegrator "
@@ -1378,25 +1435,26 @@ def main():
                          "vs the previous raycast (from the previous tracked pose) + SetView x3 + LightIntegrator + Tracer at "
                          "the TRACKED pose; camera swinging +-24 deg and translating through a 4.4 x 3 x 5.2 m box room with "
                          "9 spheres (closed form, all six pose parameters observable)"}
-    set_view_policy = {
-        "calls_per_frame_upstream": 3, "max_rounds": SET_VIEW_ROUNDS,
-        "policy": "one vk_volume_set_view_rounds(.., 3) per frame = the state of upstream's three SetView calls "
-                  "(apps/vulcan/vulcan.cu:316-318), bit for bit; rounds 2 and 3 run inside the last launch of round 1, "
-                  "and only when the round before lost a request to a bucket contest or dropped one",
-        "rounds_run_per_frame": res.pop("set_view_rounds_run_per_frame"),
-        "frames_that_needed_more_than_one_round": int((rounds_per_frame > 1).sum()),
-    }
-    traffic_bytes, traffic_source = pmc_traffic(wl)
+    if full:
+        set_view_policy = {
+            "calls_per_frame_upstream": 3, "max_rounds": SET_VIEW_ROUNDS,
+            "policy": "one vk_volume_set_view_rounds(.., 3) per frame = the state of upstream's three SetView calls "
+                      "(apps/vulcan/vulcan.cu:316-318), bit for bit; rounds 2 and 3 run inside the last launch of round 1, "
+                      "and only when the round before lost a request to a bucket contest or dropped one",
+            "rounds_run_per_frame": res.pop("set_view_rounds_run_per_frame"),
+            "frames_that_needed_more_than_one_round": int((rounds_per_frame > 1).sum()),
+        }
+        traffic_bytes, traffic_source = pmc_traffic(wl)
     result = {
         "metric": METRIC, "value": res["value"], "unit": "frames/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
         "per_rank_ms_per_step": res["per_rank_ms_per_step"],     # rank order; ms_per_step is their max (barrier to barrier)
-        "windows": res.get("windows", {"count": 1, "frames_each": args.steps, "median": res["value"], "min": res["value"],
-                                       "max": res["value"], "frames_per_s": [res["value"]]}),
+        **({"windows": res.get("windows", {"count": 1, "frames_each": args.steps, "median": res["value"], "min": res["value"],
+                                           "max": res["value"], "frames_per_s": [res["value"]]})} if full else {}),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {
             "workload": names[wl] + ", 5 mm voxels, Volume(65024,8192)",
-            "set_view": set_view_policy,
+            **({"set_view": set_view_policy} if full else {}),
             "input_normals": ("Frame::ComputeNormals of the input frame (vulcan.cu:297) is part of every timed step: "
                               + ("by the launch that builds the tracker's pyramid (vk_icp_pyramid_track_frame)"
                                  + (", which also computes the PREVIOUS raycast's normal image (Tracer::Trace's last stage, "
@@ -1409,16 +1467,16 @@ def main():
             "requests_ahead": ("the request pass of SetView(i + 1) rides behind the workgroups of Trace(i) in one launch "
                                "(vk_trace_ahead_requests; the poses are given, so frame i + 1 is known), SetView(i + 1) launches "
                                "its handle + visibility pass only: the same passes per frame, one launch boundary less; the step "
-                               "without it is other_workloads['%s-requests-inside-set-view']" % wl)
+                               "without it is other_workloads['%s-requests-inside-set-view'] (--full)" % wl)
                               if loop.ahead is not None else
                               "no: SetView makes its own request pass" + (" (the next pose comes out of this frame's raycast)"
                                                                           if wl == "rgbd-icp" else ""),
             "frames_per_rank": args.steps, "image": [W, H], "voxel_length": VOXEL, "truncation_length": TRUNC,
-            "visible_blocks_mean": float(nvis_timed[:args.steps].mean()),
+            **({"visible_blocks_mean": float(nvis_timed[:args.steps].mean())} if full else {}),
             "allocated_blocks_end": int(min(MAIN + EXCESS, MAIN + EXCESS - 1 - ctr[T.VK_CTR_VOXEL_PTR])),
             "dropped_requests": int(ctr[T.VK_CTR_DROPPED]), "parallelism": f"replica volume per GPU x{world}",
         },
-        "roofline": {
+        **({"roofline": {
             "kernel": "integrate_pipelined_kernel<depth%s> (vk_integrate_ahead)" % ("" if wl == "depth" else "+light colour"),
             "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes, "traffic_source": traffic_source,
@@ -1453,7 +1511,7 @@ def main():
                                    "normals in one launch (vk_trace_ahead_requests)") if loop.ahead is not None else
                                   "compute_points_kernel + compute_normals_kernel (vk_trace_ahead)",
                         "avg_us": float(trace_ms.mean() * 1e3)},
-        },
+        }} if full else {}),
     }
     if res.get("error"):
         result["error"] = res["error"]           # e.g. the pool ran dry: the headline is not the configured workload's
@@ -1462,7 +1520,7 @@ def main():
         if key_ in res:
             result["config"][key_] = res[key_]
 
-    extras = not args.only and world == 1          # measured once, on a single GPU
+    extras = full and not args.only and world == 1          # measured once, on a single GPU
     if extras:
         pr = probes(loop, nvis[-1])
         result["roofline"].update(pr)
@@ -1601,7 +1659,7 @@ def main():
         del oloop
         torch.cuda.empty_cache()
 
-    if world > 1:
+    if world > 1 and full:
         # the rig step is reported next to the headline, never instead of it: a failure here is
         # recorded (vk_comm_rig makes the ranks agree on every step that can fail on one of them
         # alone before the next collective), and a rank that still waits for a peer longer than
@@ -1626,7 +1684,7 @@ def main():
             result["collective"] = {"ok": False, "error": f"{type(e).__name__}: {e}"[:400]}
         watchdog.cancel()
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:   # the CPU leg is reported at N=1 only
+    if full and rank == 0 and world == 1 and args.cpu_seconds > 0:   # the CPU leg is reported at N=1 only
         result["cpu_baseline"] = cpu_baseline(wl, poses, args.cpu_seconds)
     gpu_dense = result.pop("configs0_dense_128_gpu", None)
     if gpu_dense is not None:

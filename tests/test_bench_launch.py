@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -161,3 +163,64 @@ def test_recorded_round6_bench_line_is_complete():
     assert gpu["voxels"] == dense["voxels"] == 128 ** 3 and dense["same_voxels_updated"] is True
     assert 0.001 < gpu["ms"] < 1.0 and 0.0 < gpu["past_l3"]["frac_of_8TBps"] < 1.0 and "frac_of_8TBps" not in gpu
     assert dense["gpu_over_cpu"]["1_core"] > 10
+
+
+def test_dumped_outputs_keep_their_dtype_and_stay_under_the_cap(tmp_path):
+    """bench.write_outputs: what fits is written as it is; past the cap every array becomes the same seeded sample of its
+    elements, in float32 / float64 as given, and two writes of the same arrays give the same files."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    small = {"a": np.arange(12, dtype=np.float32).reshape(3, 4), "pose": np.eye(4)}
+    bench.write_outputs(str(tmp_path / "small"), small)
+    for name, a in small.items():
+        got = np.load(tmp_path / "small" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    big = {"depth": np.linspace(0.0, 1.0, 300000, dtype=np.float32), "pose": np.arange(16, dtype=np.float64)}
+    cap = 200000
+    for d in ("big1", "big2"):
+        bench.write_outputs(str(tmp_path / d), big, cap=cap)
+    sizes = [os.path.getsize(tmp_path / "big1" / f) for f in os.listdir(tmp_path / "big1")]
+    assert sum(sizes) <= cap
+    for name, a in big.items():
+        one, two = np.load(tmp_path / "big1" / f"{name}.npy"), np.load(tmp_path / "big2" / f"{name}.npy")
+        assert one.dtype == a.dtype and np.array_equal(one, two) and 0 < one.size < a.size
+        assert np.isin(one, a).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` prints the headline alone — K timed steps, `ms_per_step`, nothing that takes
+    runs of its own — and `--dump-outputs` writes the last timed step's raycast, normals and pose: the same bits in two runs.
+    The raycast of the sphere the camera sits in is the closed-form depth image it was fused from."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    outs = []
+    for run in ("one", "two"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_clean_env(), timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        line = json.loads(lines[0])
+        assert line["metric"] == bench.METRIC and line["unit"] == "frames/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["steps"] == 7 and line["warmup"] == 3 and line["n_gpus"] == 1
+        assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3
+        for key in ("windows", "roofline", "other_workloads", "cpu_baseline", "collective"):
+            assert key not in line, key
+        assert "error" not in line and line["config"]["dropped_requests"] == 0
+        outs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    one, two = outs
+    assert sorted(one) == ["frame_normals", "pose", "raycast_color", "raycast_depth", "raycast_normals"]
+    for name, a in one.items():
+        assert a.dtype == (np.float64 if name == "pose" else np.float32), name
+        assert a.tobytes() == two[name].tobytes(), name
+    from vulcan_amd import vk_types as T
+    import scenes
+    want = bench.sphere_room_depth(T.Projection.make(*scenes.APP_INTRINSICS))
+    got = one["raycast_depth"]
+    hit = np.isfinite(got) & (got > 0)
+    assert one["raycast_depth"].shape == (bench.H, bench.W) and hit.mean() > 0.9
+    assert np.median(np.abs(got[hit] - want[hit])) < bench.VOXEL

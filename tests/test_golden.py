@@ -77,7 +77,7 @@ def test_oracle_reproduces_the_soak_fixtures_first_checkpoint(orc):
     assert golden["240"]["voxels_sha256"] != golden["2000"]["voxels_sha256"]
 
 
-def test_oracle_reproduces_the_soak_drift_fixtures_first_report(orc):
+def test_oracle_reproduces_the_soak_drift_fixtures_first_report(orc, tmp_path):
     """tests/golden/soak_oracle_drift.json (make_soak_oracle_drift.py: the oracle's OWN tracked loop over the soak's sequence —
     what tools/soak.py compares the device's creeping pose with, profiles/r06_soak.json finding 2): the first 100 frames of that
     loop still give the file's first report, to the bit (30 s of oracle; the whole file took ten minutes, once)."""
@@ -86,7 +86,7 @@ def test_oracle_reproduces_the_soak_drift_fixtures_first_report(orc):
     path = os.path.join(os.path.dirname(mf.SOAK_FILE), "soak_oracle_drift.json")
     golden = json.load(open(path))["reports"]
     assert [r["frame"] for r in golden][:3] == [100, 200, 300] and golden[-1]["frame"] == 2000
-    out = os.path.join(os.environ.get("TMPDIR", "/tmp"), "soak_drift_check.json")
+    out = str(tmp_path / "soak_drift_check.json")
     script = os.path.join(os.path.dirname(mf.SOAK_FILE), "make_soak_oracle_drift.py")
     subprocess.run([sys.executable, script, "--frames", "100", "--every", "100", "--out", out], check=True, stdout=subprocess.DEVNULL,
                    timeout=600)

@@ -2,7 +2,7 @@
 set -eo pipefail
 tag=${1:-x}; wl=${2:-rgbd}; pat=${3:-.}
 out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_k -o p -- python3 bench.py --workload $wl --only --steps 100 --warmup 20 --cpu-seconds 0 > $out/bench_k.json 2> $out/prof_k.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_k -o p -- python3 bench.py --full --workload $wl --only --steps 100 --warmup 20 --cpu-seconds 0 > $out/bench_k.json 2> $out/prof_k.err
 python3 - <<PY
 import csv,glob,json
 f=glob.glob("$out/prof_k/**/*kernel_stats.csv",recursive=True)[0]

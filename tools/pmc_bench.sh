@@ -9,7 +9,7 @@ i=0
 while read -r group; do
   i=$((i+1))
   echo "pmc group $i: $group"
-  timeout -k 5 200 rocprofv3 --kernel-trace --pmc $group --output-format csv -d $out/g$i -o p -- python3 bench.py --workload $wl --only --steps 30 --warmup 10 --cpu-seconds 0 > $out/g$i.log 2>&1 || echo "group $i failed/timeout"
+  timeout -k 5 200 rocprofv3 --kernel-trace --pmc $group --output-format csv -d $out/g$i -o p -- python3 bench.py --full --workload $wl --only --steps 30 --warmup 10 --cpu-seconds 0 > $out/g$i.log 2>&1 || echo "group $i failed/timeout"
 done <<GROUPS
 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY
 SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE

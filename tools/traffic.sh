@@ -9,6 +9,6 @@ mkdir -p $out
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "traffic pass: $c ($wl)"
   rm -rf $out/$c
-  timeout -k 5 240 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -o p -- python3 bench.py --workload $wl --only --steps 60 --warmup 20 --cpu-seconds 0 > $out/$c.log 2>&1 || echo "pass $c failed/timeout"
+  timeout -k 5 240 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -o p -- python3 bench.py --full --workload $wl --only --steps 60 --warmup 20 --cpu-seconds 0 > $out/$c.log 2>&1 || echo "pass $c failed/timeout"
 done
 python3 tools/traffic_summary.py $out $wl

@@ -35,7 +35,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
                 bench = json.loads(line)
     except OSError:
         pass
-cmd = f"tools/traffic.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --workload {workload} --only --steps 60 --warmup 20 --cpu-seconds 0 (and a separate pass with --pmc WRITE_SIZE)"
+cmd = f"tools/traffic.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --full --workload {workload} --only --steps 60 --warmup 20 --cpu-seconds 0 (and a separate pass with --pmc WRITE_SIZE)"
 for k in KERNELS:
     fetch, n = res[k]["FETCH_SIZE"]
     write, _ = res[k]["WRITE_SIZE"]
