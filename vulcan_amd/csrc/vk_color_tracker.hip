@@ -698,33 +698,6 @@ __global__ __launch_bounds__(kColorThreads, 1024 / kColorThreads) void color_loo
     steps = it + 1;
     VK_STAMP(4);
 
-#ifdef VK_SCALAR_SOLVE
-    if (threadIdx.x == 0)
-    {
-      // A step needs depth_to_world^-1 (the next update multiplies it) and Tcm's matrix (the
-      // pixels); depth_to_world itself and Tcm^-1 — three more 4x4 products per step — are made
-      // once, after the loop, from the last step's M. (The unused halves are dead code here.)
-      float update[6], old_i[16], M[16], m[16], i[16], out_m[16], out_i[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) old_i[k] = twd[16 + k];
-      color_pose_matrix<N>(sums, sums + 36, old_i, M, update);
-      rigid_from(M, i, m);
-      derive_tcm_arrays(L.frame_Tcd, L.key_Twc, m, i, out_m, out_i);
-      float sq = 0.0f;
-#pragma unroll
-      for (int k = 0; k < N; ++k) sq += update[k] * update[k];
-      stop = (sqrtf(sq) < 1E-6f) ? 1 : 0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) { twd[16 + k] = i[k]; tcm[k] = out_m[k]; }
-      if (publisher)
-      {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) last_M[k] = M[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) last_update[k] = update[k];
-      }
-    }
-#else
     if (threadIdx.x < 64)
     {
       // The same step across the lanes of the first wave (vk_gauss_newton.hpp wave_solve_step: the
@@ -769,7 +742,6 @@ __global__ __launch_bounds__(kColorThreads, 1024 / kColorThreads) void color_loo
         }
       }
     }
-#endif
     __syncthreads();
     VK_STAMP(5);
     if (stop) break;             // tracker.cpp:162

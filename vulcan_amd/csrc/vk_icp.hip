@@ -464,22 +464,13 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
       if (resident) accumulate_pixels<TRANSLATION>(P, Twc, group, 0, px, acc);
       else accumulate_group<TRANSLATION>(P, Twc, group, acc);
       VK_STAMP(1);
-#ifdef VK_LOOP_ATOMIC_EXCHANGE
-      publish_atomic<kIcpThreads / 64>(acc, lds, L.exchange, it);
-#else
       publish_partial<kIcpThreads / 64>(acc, lds, L.exchange, it, group);
-#endif
     }
     VK_STAMP(2);
     VK_STAMP(3);
-#ifdef VK_LOOP_ATOMIC_EXCHANGE
-    if (!gather_atomic(L.exchange, it, TRANSLATION, publisher ? L.hessian : nullptr, publisher ? L.gradient : nullptr, sums, &failed))
-      break;
-#else
     if (!gather_partials<kIcpThreads>(L.exchange, it, TRANSLATION, publisher ? L.hessian : nullptr,
             publisher ? L.gradient : nullptr, slices, sums, &failed))
       break;
-#endif
     if (L.rig.world > 0)
     {
       // a rigid rig: this view's sums go to every rank, every rank's come back (vk_rig_protocol.h);
@@ -512,31 +503,6 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
     steps = it + 1;
     VK_STAMP(4);
 
-#ifdef VK_SCALAR_SOLVE
-    if (threadIdx.x == 0)
-    {
-      // the pixels only ever need the pose's matrix; its inverse (a second 4x4 product per
-      // step) is made once, after the loop, from the last step's M
-      float update[6], old_m[16], M[16], out_m[16], unused_i[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) old_m[i] = pose_m[i];
-      pose_matrix<N>(sums, sums + 36, old_m, M, update);
-      rigid_from(M, out_m, unused_i);
-      float sq = 0.0f;
-#pragma unroll
-      for (int i = 0; i < N; ++i) sq += update[i] * update[i];
-      stop = (sqrtf(sq) < 1E-6f) ? 1 : 0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) pose_m[i] = out_m[i];
-      if (publisher)
-      {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) result[i] = M[i];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) result[16 + i] = update[i];
-      }
-    }
-#else
     if (threadIdx.x < 64)
     {
       // solve + pose update across the lanes of the first wave (wave_solve_step): the bits of
@@ -573,7 +539,6 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
         }
       }
     }
-#endif
     __syncthreads();
     VK_STAMP(5);
     if (stop) break;             // tracker.cpp:162
@@ -870,10 +835,6 @@ int launch_loop(const IcpParams& P, vk_transform* Twc_dev, int iterations, int t
     L.force_abort = vk_forced_loop_abort();
     L.last_launch = (ends_track && done + kExchangeSteps >= iterations) ? 1 : 0;
     IcpParams Pk = P;
-#ifdef VK_LOOP_ATOMIC_EXCHANGE
-    // (the experiment's counter and accumulators start from zero; the product's tagged words need no such launch)
-    VK_CHECK(hipMemsetAsync(workspace, 0, (16 + 3 * kSysStride) * sizeof(float), s));
-#endif
     vk_loop_launch_begin(s);
     const hipError_t le = translation_enabled ? launch_loop_kernel(track_loop_kernel<true>, grid, kIcpThreads, s, Pk, L)
                                               : launch_loop_kernel(track_loop_kernel<false>, grid, kIcpThreads, s, Pk, L);
@@ -1091,7 +1052,7 @@ static int pyramid_track(const vk_icp_view* keyframe, const vk_transform* Twm, c
   if (Twc_start) L.pose_start = *Twc_start;
   if (!level_built || frame_side_only)
   {
-    // (frame_side_only — an experiment, -DVK_TP_KEY_SIDE=0 — : the frame's level exists, its workgroups leave at once)
+    // (frame_side_only: the record has the frame's level only, so the frame's workgroups leave at once)
     if (level_built) L.dst_w[1] = L.dst_h[1] = 0;
     hipLaunchKernelGGL(pyramid_level_kernel, dim3((gw + 63) / 64, (gh + 3) / 4, 2 + due), dim3(256), 0, s, L);
     VK_LAUNCH_CHECK();

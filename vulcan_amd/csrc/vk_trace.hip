@@ -236,25 +236,14 @@ constexpr int kNormalLateWords = 16;      // one more line behind the counters: 
 
 // The raycast's waves above the request pass's in the launch they share (s_setprio, round 5): the launch is as long as its
 // slowest raycast wave, the request pass fills in. 37.75 -> 37.53 us in two alternating pairs of runs (the request pass's waves
-// raised instead: 38.2; a march's waves raised after 8 / 16 / 32 passes through the loop: nothing, either scene). -DVK_TR_PRIO=0: without.
-#ifndef VK_TR_PRIO
-#define VK_TR_PRIO 1
-#endif
+// raised instead: 38.2; a march's waves raised after 8 / 16 / 32 passes through the loop: nothing, either scene).
 #ifndef VK_TR_WAVES
 #define VK_TR_WAVES 5
-#endif
-#ifndef VK_TP_KEY_SIDE
-#define VK_TP_KEY_SIDE 1     // 0 (experiment): only the FRAME side of the next pyramid rides behind the raycast — nothing waits
 #endif
 #ifndef VK_TP_WAVES
 #define VK_TP_WAVES 6        // trace_and_pyramid_kernel: the raycast alone (compute_points_kernel) runs six waves per SIMD
 #endif
-#ifndef VK_TRACE_NORMALS_RIDE
-#define VK_TRACE_NORMALS_RIDE 1
-#endif
-#define VK_POINTS_WAVES 1
-#define VK_POINTS_ORDER 1
-constexpr int kPointsWaves = VK_POINTS_WAVES;
+constexpr int kPointsWaves = 1;
 constexpr int kPointsTile = (kPointsWaves == 4) ? 16 : 8;     // pixels per workgroup edge
 
 // The work of ONE workgroup of the raycast: WAVES = 1: an 8 x 8 tile; WAVES = 4: 2 x 2 of them. `group` of `groups`
@@ -270,23 +259,16 @@ __device__ __forceinline__ void points_group(const PointParams& P, const int gro
   wave_lds_fence();
 
   // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs, each
-  // with its own L2, and neighbouring tiles march through the same voxel blocks.
-  // Workgroup w therefore takes tile (w % 8) * chunk + w / 8, which gives every XCD
-  // one contiguous band of the image (placement only affects speed).
+  // with its own L2, and neighbouring tiles march through the same voxel blocks, so
+  // every XCD takes bands of the image (placement only affects speed): two half bands
+  // per XCD, k and k + 8 of 16 — rays near the image border graze the surface and take
+  // more steps, so every XCD gets one outer and one inner strip.
   const int tiles_x = (P.image_width + TILE - 1) / TILE, tiles_y = (P.image_height + TILE - 1) / TILE;
   const int tiles = tiles_x * tiles_y;
   const int chunk = (tiles + 7) / 8;
-  int tile;
-  if (VK_POINTS_ORDER == 0) tile = (group & 7) * chunk + (group >> 3);
-  else if (VK_POINTS_ORDER == 1)
-  {
-    // two half bands per XCD, k and k + 8 of 16: rays near the image border graze the
-    // surface and take more steps, so every XCD gets one outer and one inner strip
-    const int half = (chunk + 1) / 2;
-    const int i = group >> 3, k = group & 7;
-    tile = (i < half) ? k * half + i : (8 + k) * half + (i - half);
-  }
-  else tile = group;                                        // plain round robin
+  const int half = (chunk + 1) / 2;
+  const int i = group >> 3, k = group & 7;
+  const int tile = (i < half) ? k * half + i : (8 + k) * half + (i - half);
   const int tile_x = tile % tiles_x, tile_y = tile / tiles_x;
   const int x = tile_x * TILE + (WAVES == 4 ? (wave & 1) * 8 : 0) + (lane & 7);
   const int y = tile_y * TILE + (WAVES == 4 ? (wave >> 1) * 8 : 0) + (lane >> 3);
@@ -328,13 +310,8 @@ __device__ __forceinline__ void points_group(const PointParams& P, const int gro
   }
 }
 
-#ifdef VK_POINTS_WAVES_PER_EU      // experiments only: the kernel held to this many waves per SIMD (spills instead of registers)
-#define VK_POINTS_OCCUPANCY __attribute__((amdgpu_waves_per_eu(VK_POINTS_WAVES_PER_EU)))
-#else
-#define VK_POINTS_OCCUPANCY
-#endif
 template <bool POOL32>
-__global__ __launch_bounds__(kPointsWaves * 64) VK_POINTS_OCCUPANCY void compute_points_kernel(PointParams P)
+__global__ __launch_bounds__(kPointsWaves * 64) void compute_points_kernel(PointParams P)
 {
   __shared__ int4 directories[kPointsWaves][kDirWords];
   points_group<POOL32, kPointsWaves>(P, (int)blockIdx.x, (int)gridDim.x, directories);
@@ -414,17 +391,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VK_TR_WAVES
 {
   __shared__ int4 directories[4][kDirWords];
   __shared__ int normals_expired;
-#ifdef VK_TR_EXTRA_LDS
-  // experiment (profiles/r05_two_launch_frame.txt): the static LDS SetView's handle + visibility pass would bring into this
-  // launch if it rode here too (handle_listed 16 KiB, later_rounds 20 KiB) — what that does to the raycast's occupancy
-  __shared__ int extra_lds[VK_TR_EXTRA_LDS / 4];
-  asm volatile("" :: "v"(&extra_lds[threadIdx.x]));
-#endif
   if ((int)blockIdx.x < trace_groups)
   {
-#if VK_TR_PRIO
     __builtin_amdgcn_s_setprio(2);
-#endif
     points_group<POOL32, 4>(P, (int)blockIdx.x, trace_groups, directories);
     return;
   }
@@ -558,9 +527,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VK_TP_WAVES
   __shared__ int normals_expired;
   if ((int)blockIdx.x < trace_groups)
   {
-#if VK_TR_PRIO
     __builtin_amdgcn_s_setprio(2);
-#endif
     points_group<POOL32, 4>(P, (int)blockIdx.x, trace_groups, directories);
     return;
   }
@@ -718,7 +685,7 @@ int launch_points(const vk_hash_entry* entries, const vk_voxel* voxels, const fl
     if (!P.rows_done && ride->groups_key_full + ride->groups_key_half > 0) return VK_ERR_ARGUMENT;
     const int tiles16 = ((image_width + 15) / 16) * ((image_height + 15) / 16);
     int chunk16 = (tiles16 + 7) / 8;
-    if (VK_POINTS_ORDER == 1) chunk16 = 2 * ((chunk16 + 1) / 2);
+    chunk16 = 2 * ((chunk16 + 1) / 2);
     const int trace_groups = 8 * chunk16;
     const dim3 grid2(trace_groups + ride->groups_frame_full + ride->groups_frame_half + ride->groups_key_full + ride->groups_key_half);
     if (pool32) hipLaunchKernelGGL(trace_and_pyramid_kernel<true>, grid2, dim3(256), 0, s, P, *ride, trace_groups, normals);
@@ -731,7 +698,7 @@ int launch_points(const vk_hash_entry* entries, const vk_voxel* voxels, const fl
     // workgroups of 256: 16 x 16 pixel tiles of the raycast, then 64 x 4 pixel groups of the request pass and the normals
     const int tiles16 = ((image_width + 15) / 16) * ((image_height + 15) / 16);
     int chunk16 = (tiles16 + 7) / 8;
-    if (VK_POINTS_ORDER == 1) chunk16 = 2 * ((chunk16 + 1) / 2);
+    chunk16 = 2 * ((chunk16 + 1) / 2);
     const int trace_groups = 8 * chunk16;
     const int normal_groups = P.rows_done ? ((image_width + 63) / 64) * ((image_height + 3) / 4) : 0;
     const int gx = (next_requests->width + 63) / 64, gy = (next_requests->height + 3) / 4;
@@ -746,7 +713,7 @@ int launch_points(const vk_hash_entry* entries, const vk_voxel* voxels, const fl
   }
   const int tiles = ((image_width + kPointsTile - 1) / kPointsTile) * ((image_height + kPointsTile - 1) / kPointsTile);
   int chunk = (tiles + 7) / 8;
-  if (VK_POINTS_ORDER == 1) chunk = 2 * ((chunk + 1) / 2);
+  chunk = 2 * ((chunk + 1) / 2);
   const dim3 grid(8 * chunk);   // padded so every XCD gets an equal share
   if (pool32)
     hipLaunchKernelGGL(compute_points_kernel<true>, grid, dim3(kPointsWaves * 64), 0, s, P);
@@ -965,7 +932,7 @@ static int trace_ahead(const vk_volume* v, const vk_frame* frame, vk_view_bounds
   // (only with the next frame's request pass between the raycast's workgroups and the normals': dispatched right behind
   // the raycast's, the waiting groups cost it 12 to 17 us — profiles/r04_trace_normals_ride.txt)
   const bool ride_waits = ride && ride->groups_key_full + ride->groups_key_half > 0;
-  const bool normals_ride = VK_TRACE_NORMALS_RIDE && (next_requests || ride_waits) && out_normals && partials && rows <= kNormalRows;
+  const bool normals_ride = (next_requests || ride_waits) && out_normals && partials && rows <= kNormalRows;
   if (ride_waits && !normals_ride) ride = nullptr;       // (a grid too large for the counters: the caller's pyramid launch stays)
   if (rode) *rode = ride != nullptr;
   uint32_t* rows_done = nullptr;
@@ -1086,22 +1053,10 @@ int vk_trace_ahead_pyramid(const vk_volume* v, const vk_frame* frame, vk_view_bo
   Y.groups_key_full = ((frame->width + 63) / 64) * ((frame->height + 3) / 4);
   Y.groups_key_half = ((kw + 63) / 64) * ((kh + 3) / 4);
   bool rode = false;
-#if !VK_TP_KEY_SIDE
-  // experiment: the frame side only; the raycast's normal image and half level stay with the next Track's pyramid launch
-  Y.groups_key_full = Y.groups_key_half = 0;
-  const int rc = trace_ahead(v, frame, ahead, out_depth, out_color, nullptr, stream, nullptr, nullptr, 0, &Y, &rode);
-  built->pad_ = 1;
-#else
   const int rc = trace_ahead(v, frame, ahead, out_depth, out_color, out_normals, stream, nullptr, nullptr, 0, &Y, &rode);
   built->pad_ = 0;
-#endif
   if (rc != VK_OK) return rc;
-  if (!rode)
-  {
-    // not ridden (vk_trace_ahead's launches; the record stays invalid) — the experiment's form owes the normal image then
-    if (!VK_TP_KEY_SIDE) return launch_normals(out_depth, &frame->depth_projection, out_normals, frame->width, frame->height, vk_s(stream));
-    return VK_OK;
-  }
+  if (!rode) return VK_OK;   // not ridden (vk_trace_ahead's launches; the record stays invalid)
   built->key_depths = out_depth;
   built->key_normals = out_normals;
   built->frame_depths = next->depths;
