@@ -391,16 +391,6 @@ __device__ __forceinline__ bool evaluate_any(const ColorParams& P, const Rt& Tcm
   return evaluate<TRANSLATION, JACOBIAN>(P, Tcm, x, y, residual, J);
 }
 
-__device__ __forceinline__ Rt rt_of(const float* m)   // column-major 4x4 -> rows 0..2
-{
-  Rt t;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) t.r[r * 4 + c] = m[c * 4 + r];
-  return t;
-}
-
 // ref: color_tracker.cu:140-163
 template <bool LIGHT>
 __global__ __launch_bounds__(256) void color_residuals_kernel(ColorParams P, float* __restrict__ residuals)
@@ -461,7 +451,7 @@ __global__ __launch_bounds__(kColorThreads) void color_partial_kernel(ColorParam
 
   if (P.state && P.state[1]) return;   // tracker.cpp:162, see system_partial_kernel
 
-  const Rt Tcm = P.Tcm_dev ? rt_of(P.Tcm_dev->m) : P.Tcm;
+  const Rt Tcm = P.Tcm_dev ? rt_from_colmajor(P.Tcm_dev->m) : P.Tcm;
   float acc[27];
 #pragma unroll
   for (int i = 0; i < 27; ++i) acc[i] = 0.0f;
@@ -472,29 +462,9 @@ __global__ __launch_bounds__(kColorThreads) void color_partial_kernel(ColorParam
 // ------------------------------------------------------------ pose update ----
 
 // color_tracker.cu:312-320: Tcm = (frame_Tcd * frame_Twd^-1) * keyframe_Tcw^-1 with
-// (A * B).m = A.m * B.m, (A * B).inv = B.inv * A.inv (transform.h:146-159)
+// (A * B).m = A.m * B.m, (A * B).inv = B.inv * A.inv (transform.h:146-159), from the frame's
+// depth_to_world (twd_m, twd_i) and the keyframe's pose
 __device__ __forceinline__ void derive_tcm(const vk_transform& frame_Tcd, const vk_transform& key_Twc,
-    vk_color_pose* pose)
-{
-  float tcd_m[16], tcd_i[16], twd_m[16], twd_i[16], twc_m[16], twc_i[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-  {
-    tcd_m[i] = frame_Tcd.m[i];  tcd_i[i] = frame_Tcd.inv[i];
-    twd_m[i] = pose->depth_to_world.m[i];  twd_i[i] = pose->depth_to_world.inv[i];
-    twc_m[i] = key_Twc.m[i];  twc_i[i] = key_Twc.inv[i];
-  }
-  float tcw_m[16], tcw_i[16], out_m[16], out_i[16];
-  matmul4(tcd_m, twd_i, tcw_m);    // frame_Tcw.m   = Tcd.m * (Twd^-1).m
-  matmul4(twd_m, tcd_i, tcw_i);    // frame_Tcw.inv = (Twd^-1).inv * Tcd.inv
-  matmul4(tcw_m, twc_m, out_m);
-  matmul4(twc_i, tcw_i, out_i);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { pose->Tcm.m[i] = out_m[i]; pose->Tcm.inv[i] = out_i[i]; }
-}
-
-// color_tracker.cu:312-320 on arrays: Tcm from the frame's and the keyframe's poses
-__device__ __forceinline__ void derive_tcm_arrays(const vk_transform& frame_Tcd, const vk_transform& key_Twc,
     const float (&twd_m)[16], const float (&twd_i)[16], float (&out_m)[16], float (&out_i)[16])
 {
   float tcd_m[16], tcd_i[16], twc_m[16], twc_i[16];
@@ -511,43 +481,29 @@ __device__ __forceinline__ void derive_tcm_arrays(const vk_transform& frame_Tcd,
   matmul4(twc_i, tcw_i, out_i);
 }
 
-// ref: tracker.cpp:124-163 + color_tracker.cpp:34-96 on arrays: the update from the system,
-// the new depth_to_world (m, inv) from the old inverse
-template <int N>
-__device__ __forceinline__ void color_pose_matrix(const float* hessian, const float* gradient, const float (&old_i)[16],
-    float (&M)[16], float (&update)[6])
+// pose->Tcm from pose->depth_to_world
+__device__ __forceinline__ void derive_tcm(const vk_transform& frame_Tcd, const vk_transform& key_Twc, vk_color_pose* pose)
 {
-  solve_step<N>(hessian, gradient, update);
-
-  // color_tracker.cpp:45-65: a proper skew matrix (DepthTracker's has Tinc(1,2) = +u0)
-  float Tinc[16];
-  Tinc[0] = 1.0f;        Tinc[4] = -update[2]; Tinc[8] = +update[1];  Tinc[12] = +update[3];
-  Tinc[1] = +update[2];  Tinc[5] = 1.0f;       Tinc[9] = -update[0];  Tinc[13] = +update[4];
-  Tinc[2] = -update[1];  Tinc[6] = +update[0]; Tinc[10] = 1.0f;       Tinc[14] = +update[5];
-  Tinc[3] = 0.0f;        Tinc[7] = 0.0f;       Tinc[11] = 0.0f;       Tinc[15] = 1.0f;
-
-  matmul4(Tinc, old_i, M);             // :67  M = Tinc * Twd^-1
+  float twd_m[16], twd_i[16], out_m[16], out_i[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { twd_m[i] = pose->depth_to_world.m[i];  twd_i[i] = pose->depth_to_world.inv[i]; }
+  derive_tcm(frame_Tcd, key_Twc, twd_m, twd_i, out_m, out_i);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { pose->Tcm.m[i] = out_m[i]; pose->Tcm.inv[i] = out_i[i]; }
 }
 
-template <int N>
-__device__ __forceinline__ void color_pose_step(const float* hessian, const float* gradient, const float (&old_i)[16],
-    float (&twd_m)[16], float (&twd_i)[16], float (&update)[6])
-{
-  float M[16];
-  color_pose_matrix<N>(hessian, gradient, old_i, M, update);
-  rigid_from(M, twd_i, twd_m);         // :69-95 world -> depth, re-orthonormalised; .Inverse() swaps the two
-}
-
-// one lane
+// ref: tracker.cpp:124-163 + color_tracker.cpp:34-96, one lane: the update from the system, the
+// new depth_to_world (m, inv) from the old inverse, then Tcm
 template <int N>
 __device__ __forceinline__ void color_solve_update_n(const float* hessian, const float* gradient,
     const vk_transform& frame_Tcd, const vk_transform& key_Twc, vk_color_pose* pose, int32_t* state,
     float* update_out, Mirror mirror)
 {
-  float update[6], old_i[16], twd_m[16], twd_i[16];
+  float update[6], old_i[16], M[16], twd_m[16], twd_i[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) old_i[i] = pose->depth_to_world.inv[i];
-  color_pose_step<N>(hessian, gradient, old_i, twd_m, twd_i, update);
+  pose_matrix<N, -1>(hessian, gradient, old_i, M, update);     // :67  M = Tinc * Twd^-1
+  rigid_from(M, twd_i, twd_m);         // :69-95 world -> depth, re-orthonormalised; .Inverse() swaps the two
 #pragma unroll
   for (int i = 0; i < 16; ++i) { pose->depth_to_world.m[i] = twd_m[i]; pose->depth_to_world.inv[i] = twd_i[i]; }
 
@@ -567,34 +523,17 @@ __device__ void color_solve_update(const float* hessian, const float* gradient, 
 struct PoseArgs
 {
   vk_transform frame_Tcd, key_Twc;
-  vk_color_pose* pose;      // null: sums only
+  vk_color_pose* pose;
   int32_t* state;
   float* update_out;
   Mirror mirror;   // pinned host {iterations, converged}, or null (vk_track_poll)
 };
-
-// second stage; with a pose it also solves and updates (one workgroup)
-__global__ __launch_bounds__(256) void color_final_kernel(const float* __restrict__ workspace, int partials,
-    int translation_enabled, float* __restrict__ hessian, float* __restrict__ gradient, PoseArgs A)
-{
-  __shared__ float slices[kSysSlices][kSysStride];
-  __shared__ float sums[48];
-  if (A.state && A.state[1]) return;
-  sum_partials(workspace, partials, translation_enabled, hessian, gradient, slices, sums);
-  if (A.pose && threadIdx.x == 0)
-    color_solve_update(sums, sums + 36, translation_enabled, A.frame_Tcd, A.key_Twc, A.pose, A.state, A.update_out, A.mirror);
-}
 
 __global__ void color_solve_kernel(const float* __restrict__ hessian, const float* __restrict__ gradient,
     int translation_enabled, PoseArgs A)
 {
   if (threadIdx.x == 0 && blockIdx.x == 0)
     color_solve_update(hessian, gradient, translation_enabled, A.frame_Tcd, A.key_Twc, A.pose, A.state, A.update_out, A.mirror);
-}
-
-__global__ void color_publish_pose_kernel(Mirror mirror, const vk_color_pose* pose)
-{
-  publish_host_pose(mirror, &pose->depth_to_world);
 }
 
 __global__ void color_prepare_kernel(PoseArgs A)
@@ -604,10 +543,8 @@ __global__ void color_prepare_kernel(PoseArgs A)
 
 // ---- the whole Gauss-Newton loop of the photometric trackers in one launch ----------
 //
-// As track_loop_kernel of the depth tracker (vk_icp.hip; the exchange is described in
-// vk_gauss_newton.hpp): every workgroup evaluates its keyframe pixels, the workgroups
-// exchange their 27 sums inside the launch, every workgroup adds all of them, solves and
-// moves depth_to_world and Tcm itself, in LDS; workgroup 0 publishes once, at the end.
+// gauss_newton_loop (vk_gauss_newton.hpp) with this step: every workgroup moves depth_to_world
+// and Tcm itself, in LDS; workgroup 0 publishes once, at the end.
 struct ColorLoopParams
 {
   Exchange exchange;
@@ -626,203 +563,110 @@ struct ColorLoopParams
   VK_LOOP_TIMING_FIELD
 };
 
+// The colour trackers' part of a step. A step needs depth_to_world^-1 (Tinc multiplies it,
+// color_tracker.cpp:67) and Tcm's matrix (the pixels); depth_to_world itself and Tcm^-1 are
+// made once, after the loop, from the last step's M.
 template <bool LIGHT, bool TRANSLATION>
-__global__ __launch_bounds__(kColorThreads, 1024 / kColorThreads) void color_loop_kernel(ColorParams P, ColorLoopParams L)
+struct ColorStep
 {
-  constexpr int N = TRANSLATION ? 6 : 3;
-  __shared__ float lds[kColorThreads / 64][kSysStride];
-  __shared__ float slices[kSysSlices][kSysStride];
-  __shared__ float sums[48];
-  __shared__ float twd[32];      // depth_to_world: matrix, inverse
-  __shared__ float tcm[32];      // Tcm: matrix, inverse
-  __shared__ float last_update[6];
-  __shared__ float last_M[16];   // workgroup 0: Tinc * Twd^-1 of the last step
-  __shared__ float solve_scratch[64];   // wave_solve_step / wave_rigid_from
-  __shared__ float fixed_m[32];         // frame_Tcd.m, key_Twc.m: indexed per lane by the wave-wide products
-  __shared__ int stop, failed;
+  static constexpr bool kTranslation = TRANSLATION;
+  static constexpr int kSign12 = -1;       // a proper skew matrix (tinc_element)
+  float* twd;        // LDS, depth_to_world: matrix, inverse
+  float* pose;       // LDS, Tcm: matrix, inverse
+  float* fixed_m;    // LDS, frame_Tcd.m, key_Twc.m: indexed per lane by the wave-wide products
+  const float* base;
 
-  const int steps_before = L.fresh_state ? 0 : L.state[0];
-  if (!L.fresh_state && L.state[1])           // uniform over the grid
-  {
-    // converged earlier: the pose stands. Aborted earlier (a level of a coarse-to-fine Track):
-    // no pose is published, the host sees the Track fail and runs it again, launch per stage
-    if (blockIdx.x == 0 && L.last_launch && L.state[1] != VK_TRACK_ABORTED) publish_host_pose(L.mirror, &L.pose->depth_to_world);
-    return;
-  }
-  if (L.force_abort)
-  {
-    if (blockIdx.x == 0 && threadIdx.x == 0) L.state[1] = VK_TRACK_ABORTED;
-    return;
-  }
+  __device__ __forceinline__ ColorStep(float* twd, float* tcm, float* fixed_m) : twd(twd), pose(tcm), fixed_m(fixed_m), base(twd + 16) {}
 
-  if (threadIdx.x < 32)
-  {
-    twd[threadIdx.x] = threadIdx.x < 16 ? L.pose->depth_to_world.m[threadIdx.x] : L.pose->depth_to_world.inv[threadIdx.x - 16];
-    fixed_m[threadIdx.x] = threadIdx.x < 16 ? L.frame_Tcd.m[threadIdx.x] : L.key_Twc.m[threadIdx.x - 16];
-  }
-  if (threadIdx.x == 0) { stop = 0; failed = 0; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    // Tracker::BeginSolve: Tcm of the pose the loop starts from
-    float m[16], i[16], out_m[16], out_i[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { m[k] = twd[k]; i[k] = twd[16 + k]; }
-    derive_tcm_arrays(L.frame_Tcd, L.key_Twc, m, i, out_m, out_i);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { tcm[k] = out_m[k]; tcm[16 + k] = out_i[k]; }
-  }
-  __syncthreads();
+  __device__ __forceinline__ bool ends_at_start(const ColorLoopParams& L) const { return false; }
 
-  const bool publisher = blockIdx.x == 0;
-  int steps = 0;
-  for (int it = 0; it < L.iterations; ++it)
+  __device__ __forceinline__ void load(const ColorParams& P, const ColorLoopParams& L)
   {
-    VK_STAMP(0);
-    const Rt Tcm = rt_of(tcm);
-    for (int group = blockIdx.x; group < L.groups; group += gridDim.x)
+    if (threadIdx.x < 32)
     {
-      if (group != (int)blockIdx.x) __syncthreads();   // the previous group's sums have left the LDS
-      float acc[27];
-#pragma unroll
-      for (int i = 0; i < 27; ++i) acc[i] = 0.0f;
-      accumulate_group<LIGHT, TRANSLATION>(P, Tcm, group, acc);
-      VK_STAMP(1);
-      publish_partial<kColorThreads / 64>(acc, lds, L.exchange, it, group);
+      twd[threadIdx.x] = threadIdx.x < 16 ? L.pose->depth_to_world.m[threadIdx.x] : L.pose->depth_to_world.inv[threadIdx.x - 16];
+      fixed_m[threadIdx.x] = threadIdx.x < 16 ? L.frame_Tcd.m[threadIdx.x] : L.key_Twc.m[threadIdx.x - 16];
     }
-    VK_STAMP(2);
-    VK_STAMP(3);
-    if (!gather_partials<kColorThreads>(L.exchange, it, TRANSLATION, publisher ? L.hessian : nullptr,
-            publisher ? L.gradient : nullptr, slices, sums, &failed))
-      break;
-    steps = it + 1;
-    VK_STAMP(4);
-
-    if (threadIdx.x < 64)
-    {
-      // The same step across the lanes of the first wave (vk_gauss_newton.hpp wave_solve_step: the
-      // bits of the one-lane code). A step needs depth_to_world^-1 (the next update multiplies it)
-      // and Tcm's matrix (the pixels); depth_to_world itself and Tcm^-1 are made once, after the
-      // loop, from the last step's M.
-      float update[6];
-      wave_solve_step<N>(sums, solve_scratch, update);
-      // color_tracker.cpp:45-65: a proper skew matrix (DepthTracker's has Tinc(1,2) = +u0); element l = c * 4 + r
-      const int l = (int)threadIdx.x & 15;
-      float tinc = (l % 5 == 0) ? 1.0f : 0.0f;
-      tinc = (l == 4) ? -update[2] : tinc;  tinc = (l == 8) ? +update[1] : tinc;  tinc = (l == 12) ? +update[3] : tinc;
-      tinc = (l == 1) ? +update[2] : tinc;  tinc = (l == 9) ? -update[0] : tinc;  tinc = (l == 13) ? +update[4] : tinc;
-      tinc = (l == 2) ? -update[1] : tinc;  tinc = (l == 6) ? +update[0] : tinc;  tinc = (l == 14) ? +update[5] : tinc;
-      if (threadIdx.x < 16) solve_scratch[threadIdx.x] = tinc;
-      wave_lds_fence();
-      const float M_lane = matmul4_lane(solve_scratch, twd + 16, (int)threadIdx.x);       // :67  M = Tinc * Twd^-1
-      wave_lds_fence();
-      const float inv_lane = wave_rigid_from(M_lane, solve_scratch);                       // :69-95: the new Twd^-1
-      if (threadIdx.x < 16) twd[16 + threadIdx.x] = inv_lane;
-      wave_lds_fence();
-      const float tcw_lane = matmul4_lane(fixed_m, twd + 16, (int)threadIdx.x);            // frame_Tcw.m = Tcd.m * (Twd^-1).m
-      if (threadIdx.x < 16) solve_scratch[32 + threadIdx.x] = tcw_lane;
-      wave_lds_fence();
-      const float tcm_lane = matmul4_lane(solve_scratch + 32, fixed_m + 16, (int)threadIdx.x);   // Tcm.m = frame_Tcw.m * key_Twc.m
-      wave_lds_fence();
-      float sq = 0.0f;
-#pragma unroll
-      for (int k = 0; k < N; ++k) sq += update[k] * update[k];
-      if (threadIdx.x < 16)
-      {
-        tcm[threadIdx.x] = tcm_lane;
-        if (publisher) last_M[threadIdx.x] = M_lane;
-      }
-      if (threadIdx.x == 0)
-      {
-        stop = (sqrtf(sq) < 1E-6f) ? 1 : 0;
-        if (publisher)
-        {
-#pragma unroll
-          for (int k = 0; k < 6; ++k) last_update[k] = update[k];
-        }
-      }
-    }
-    __syncthreads();
-    VK_STAMP(5);
-    if (stop) break;             // tracker.cpp:162
   }
 
-  if (failed)
-  {
-    if (threadIdx.x == 0) L.state[1] = VK_TRACK_ABORTED;
-    return;
-  }
-  if (!publisher) return;
-  if (steps > 0)
+  __device__ __forceinline__ void prepare(const ColorLoopParams& L)
   {
     if (threadIdx.x == 0)
     {
-      float M[16], m[16], i[16], out_m[16], out_i[16];
+      // Tracker::BeginSolve: Tcm of the pose the loop starts from
+      float m[16], i[16], out_m[16], out_i[16];
 #pragma unroll
-      for (int k = 0; k < 16; ++k) M[k] = last_M[k];
-      rigid_from(M, i, m);
-      derive_tcm_arrays(L.frame_Tcd, L.key_Twc, m, i, out_m, out_i);
+      for (int k = 0; k < 16; ++k) { m[k] = twd[k]; i[k] = twd[16 + k]; }
+      derive_tcm(L.frame_Tcd, L.key_Twc, m, i, out_m, out_i);
 #pragma unroll
-      for (int k = 0; k < 16; ++k) { twd[k] = m[k]; twd[16 + k] = i[k]; tcm[k] = out_m[k]; tcm[16 + k] = out_i[k]; }
+      for (int k = 0; k < 16; ++k) { pose[k] = out_m[k]; pose[16 + k] = out_i[k]; }
     }
     __syncthreads();
   }
-  // the derived Tcm is part of the pose even when no step ran (color_prepare_kernel's job)
-  if (threadIdx.x < 32)
+
+  __device__ __forceinline__ void accumulate(const ColorParams& P, const Rt& Tcm, int group, float (&acc)[27])
   {
-    const float v = tcm[threadIdx.x];
-    if (threadIdx.x < 16) L.pose->Tcm.m[threadIdx.x] = v; else L.pose->Tcm.inv[threadIdx.x - 16] = v;
+    accumulate_group<LIGHT, TRANSLATION>(P, Tcm, group, acc);
   }
-  if (steps > 0)
+
+  __device__ __forceinline__ bool exchanged(const ColorLoopParams& L, int it, float* sums, int* failed, bool publisher)
   {
+    return true;
+  }
+
+  // `rigid` is the new Twd^-1 (:69-95); returns the new Tcm.m
+  __device__ __forceinline__ float advance(float rigid, float* scratch)
+  {
+    if (threadIdx.x < 16) twd[16 + threadIdx.x] = rigid;
+    wave_lds_fence();
+    const float tcw_lane = matmul4_lane(fixed_m, twd + 16, (int)threadIdx.x);            // frame_Tcw.m = Tcd.m * (Twd^-1).m
+    if (threadIdx.x < 16) scratch[32 + threadIdx.x] = tcw_lane;
+    wave_lds_fence();
+    const float tcm_lane = matmul4_lane(scratch + 32, fixed_m + 16, (int)threadIdx.x);   // Tcm.m = frame_Tcw.m * key_Twc.m
+    wave_lds_fence();
+    return tcm_lane;
+  }
+
+  __device__ __forceinline__ void write_pose(const ColorLoopParams& L, int steps, const float* M_last)
+  {
+    if (steps > 0)
+    {
+      if (threadIdx.x == 0)
+      {
+        float M[16], m[16], i[16], out_m[16], out_i[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) M[k] = M_last[k];
+        rigid_from(M, i, m);
+        derive_tcm(L.frame_Tcd, L.key_Twc, m, i, out_m, out_i);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { twd[k] = m[k]; twd[16 + k] = i[k]; pose[k] = out_m[k]; pose[16 + k] = out_i[k]; }
+      }
+      __syncthreads();
+    }
+    // the derived Tcm is part of the pose even when no step ran (color_prepare_kernel's job)
     if (threadIdx.x < 32)
+    {
+      const float v = pose[threadIdx.x];
+      if (threadIdx.x < 16) L.pose->Tcm.m[threadIdx.x] = v; else L.pose->Tcm.inv[threadIdx.x - 16] = v;
+    }
+    if (steps > 0 && threadIdx.x < 32)
     {
       const float v = twd[threadIdx.x];
       if (threadIdx.x < 16) L.pose->depth_to_world.m[threadIdx.x] = v; else L.pose->depth_to_world.inv[threadIdx.x - 16] = v;
     }
-    if (threadIdx.x < 6 && L.update_out) L.update_out[threadIdx.x] = last_update[threadIdx.x];
-    if (threadIdx.x == 0)
-    {
-      const int iterations = steps_before + steps;
-      L.state[0] = iterations;
-      L.state[1] = stop;
-      if (L.mirror.word)
-        __hip_atomic_store(L.mirror.word, ((unsigned long long)(L.mirror.epoch & 0xffffu) << 48) |
-            ((unsigned long long)(uint32_t)(stop & 1) << 32) | (uint32_t)iterations,
-            __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
   }
-  if (L.last_launch)
-  {
-    __syncthreads();
-    publish_host_pose(L.mirror, &L.pose->depth_to_world);
-  }
-}
+
+  __device__ __forceinline__ const vk_transform* host_pose(const ColorLoopParams& L) const { return &L.pose->depth_to_world; }
+};
 
 template <bool LIGHT, bool TRANSLATION>
-int launch_color_loop_of(const ColorParams& P, ColorLoopParams& L, int iterations, float* workspace, hipStream_t s)
+__global__ __launch_bounds__(kColorThreads, 1024 / kColorThreads) void color_loop_kernel(ColorParams P, ColorLoopParams L)
 {
-  const int capacity = resident_workgroups(color_loop_kernel<LIGHT, TRANSLATION>, kColorThreads);
-  if (capacity <= 0) return VK_ERR_ARGUMENT;
-  const int grid = L.groups < capacity ? L.groups : capacity;
-  for (int done = 0; done < iterations; done += kExchangeSteps)
-  {
-    L.exchange.words = reinterpret_cast<unsigned long long*>(workspace);
-    L.exchange.count = L.groups;
-    { const int rc = vk_loop_epoch_begin(workspace, exchange_floats(L.groups) * sizeof(float), s, &L.exchange.epoch);  if (rc != VK_OK) return rc; }
-    VK_LOOP_TIMING_ATTACH(L, s);
-    L.iterations = iterations - done < kExchangeSteps ? iterations - done : kExchangeSteps;
-    L.last_launch = done + kExchangeSteps >= iterations ? 1 : 0;
-    L.force_abort = vk_forced_loop_abort();
-    ColorParams Pk = P;
-    vk_loop_launch_begin(s);
-    const hipError_t le = launch_loop_kernel(color_loop_kernel<LIGHT, TRANSLATION>, grid, kColorThreads, s, Pk, L);
-    vk_loop_launch_end(s);
-    VK_CHECK(le);
-    VK_LAUNCH_CHECK();
-    L.fresh_state = 0;
-  }
-  return VK_OK;
+  __shared__ float twd[32];
+  __shared__ float tcm[32];
+  __shared__ float fixed_m[32];
+  ColorStep<LIGHT, TRANSLATION> step(twd, tcm, fixed_m);
+  gauss_newton_loop<kColorThreads>(P, L, step);
 }
 
 // -------------------------------------------------------------- host side ----
@@ -873,13 +717,6 @@ void launch_color_partials(const ColorParams& P, int translation_enabled, int pa
   vk_loop_area_written(workspace);      // float partials over the loop kernels' tagged words: the next loop launch clears them
   if (P.mask) launch_partials_of<true>(P, translation_enabled, partials, workspace, s);
   else launch_partials_of<false>(P, translation_enabled, partials, workspace, s);
-}
-
-vk_transform identity_transform()
-{
-  vk_transform t;
-  for (int i = 0; i < 16; ++i) t.m[i] = t.inv[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-  return t;
 }
 
 }  // namespace
@@ -1021,15 +858,7 @@ static int system_impl(const vk_color_view* keyframe, const vk_color_view* frame
   const int partials = group_count_for(keyframe->width * keyframe->height, P.group_pixels);
   launch_color_partials(P, translation_enabled, partials, workspace, vk_s(stream));
   VK_LAUNCH_CHECK();
-  PoseArgs A;
-  A.frame_Tcd = identity;
-  A.key_Twc = identity;
-  A.pose = nullptr;
-  A.state = nullptr;
-  A.update_out = nullptr;
-  A.mirror = Mirror{nullptr, 0, nullptr};
-  hipLaunchKernelGGL(color_final_kernel, dim3(1), dim3(256), 0, vk_s(stream), workspace, partials,
-      translation_enabled, hessian, gradient, A);
+  launch_system_sums(workspace, partials, translation_enabled, hessian, gradient, vk_s(stream));
   VK_LAUNCH_CHECK();
   return VK_OK;
 }
@@ -1081,10 +910,31 @@ static int track_impl(const vk_color_view* keyframe, const vk_color_view* frame,
   VK_REQUIRE(frame_Tcd && keyframe_Twc && pose_dev && workspace && system && state_dev && iterations > 0);
   P.Tcm_dev = &pose_dev->Tcm;
   P.state = state_dev;
-  float* hessian = system;
-  float* gradient = system + 36;
   const int partials = group_count_for(keyframe->width * keyframe->height, P.group_pixels);
   hipStream_t s = vk_s(stream);
+  const Mirror mirror = begin_mirror(poll);
+
+  if (!reduce)
+  {
+    // the whole loop in one launch (color_loop_kernel)
+    ColorLoopParams L;
+    L.frame_Tcd = *frame_Tcd;
+    L.key_Twc = *keyframe_Twc;
+    L.pose = pose_dev;
+    L.groups = partials;
+    L.hessian = system;
+    L.gradient = system + 36;
+    L.state = state_dev;
+    L.update_out = update_dev;
+    L.mirror = mirror;
+    if (light)
+      return translation_enabled
+          ? launch_loop(color_loop_kernel<true, true>, kColorThreads, P, L, iterations, 0, true, workspace, s)
+          : launch_loop(color_loop_kernel<true, false>, kColorThreads, P, L, iterations, 0, true, workspace, s);
+    return translation_enabled
+        ? launch_loop(color_loop_kernel<false, true>, kColorThreads, P, L, iterations, 0, true, workspace, s)
+        : launch_loop(color_loop_kernel<false, false>, kColorThreads, P, L, iterations, 0, true, workspace, s);
+  }
 
   PoseArgs A;
   A.frame_Tcd = *frame_Tcd;
@@ -1092,70 +942,13 @@ static int track_impl(const vk_color_view* keyframe, const vk_color_view* frame,
   A.pose = pose_dev;
   A.state = state_dev;
   A.update_out = update_dev;
-  const bool chunked = polling(poll);
-  A.mirror = begin_mirror(poll);
-  PoseArgs sums_only = A;
-  sums_only.mirror = Mirror{nullptr, 0, nullptr};
-  sums_only.pose = nullptr;
-  sums_only.state = nullptr;
-  sums_only.update_out = nullptr;
-
-  if (!reduce)
-  {
-    // the whole loop in one launch (color_loop_kernel)
-    VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);   // the exchange holds 64-bit words
-    ColorLoopParams L;
-    L.frame_Tcd = *frame_Tcd;
-    L.key_Twc = *keyframe_Twc;
-    L.pose = pose_dev;
-    L.groups = partials;
-    L.fresh_state = 0;
-    L.hessian = hessian;
-    L.gradient = gradient;
-    L.state = state_dev;
-    L.update_out = update_dev;
-    L.mirror = A.mirror;
-    if (light)
-      return translation_enabled ? launch_color_loop_of<true, true>(P, L, iterations, workspace, s)
-                                 : launch_color_loop_of<true, false>(P, L, iterations, workspace, s);
-    return translation_enabled ? launch_color_loop_of<false, true>(P, L, iterations, workspace, s)
-                               : launch_color_loop_of<false, false>(P, L, iterations, workspace, s);
-  }
-
+  A.mirror = mirror;
   hipLaunchKernelGGL(color_prepare_kernel, dim3(1), dim3(64), 0, s, A);
   VK_LAUNCH_CHECK();
-
-  for (int it = 0; it < iterations; ++it)
-  {
-    launch_color_partials(P, translation_enabled, partials, workspace, s);
-
-    if (reduce)
-    {
-      // multi-GPU rig: sum the packed system over ranks before every rank solves it
-      hipLaunchKernelGGL(color_final_kernel, dim3(1), dim3(256), 0, s, workspace, partials, translation_enabled,
-          hessian, gradient, sums_only);
-      VK_LAUNCH_CHECK();
-      const int rr = reduce(system, 48, reduce_user, stream);
-      if (rr != 0) return rr;
-      hipLaunchKernelGGL(color_solve_kernel, dim3(1), dim3(64), 0, s, hessian, gradient, translation_enabled, A);
-    }
-    else
-    {
-      hipLaunchKernelGGL(color_final_kernel, dim3(1), dim3(256), 0, s, workspace, partials, translation_enabled,
-          hessian, gradient, A);
-    }
-    VK_LAUNCH_CHECK();
-    // stop enqueuing once the loop has converged (tracker.cpp:162), see vk_icp_track: the look is
-    // at the state one chunk back, so a chunk of launches is always queued behind it
-    if (chunked && (it + 1) % poll->chunk == 0 && it + 1 >= 2 * poll->chunk && it + 1 < iterations &&
-        wait_for_steps(A.mirror, it + 1 - poll->chunk, s)) break;
-  }
-  if (A.mirror.host_pose)
-  {
-    hipLaunchKernelGGL(color_publish_pose_kernel, dim3(1), dim3(64), 0, s, A.mirror, pose_dev);
-    VK_LAUNCH_CHECK();
-  }
-  return VK_OK;
+  return staged_loop(iterations, translation_enabled, partials, workspace, system, reduce, reduce_user, poll, mirror,
+      &pose_dev->depth_to_world, stream,
+      [&](hipStream_t s) { launch_color_partials(P, translation_enabled, partials, workspace, s); },
+      [&](hipStream_t s) { hipLaunchKernelGGL(color_solve_kernel, dim3(1), dim3(64), 0, s, system, system + 36, translation_enabled, A); });
 }
 
 VK_API int vk_color_tracker_track(const vk_color_view* keyframe, const vk_color_view* frame,

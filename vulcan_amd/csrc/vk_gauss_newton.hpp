@@ -518,6 +518,51 @@ __device__ __forceinline__ void solve_step(const float* hessian, const float* gr
   for (int i = 0; i < N; ++i) update[i] = -x[i];
 }
 
+// Element l = c * 4 + r of the increment Tinc(update) (column-major). depth_tracker.cpp:33-53 has
+// Tinc(1,2) = +update[0], color_tracker.cpp:45-65 a proper skew matrix with
+// Tinc(1,2) = -update[0]: SIGN12 is that sign. With a constant l the selects fold to one term.
+template <int SIGN12>
+__device__ __forceinline__ float tinc_element(const float (&update)[6], int l)
+{
+  float t = (l % 5 == 0) ? 1.0f : 0.0f;
+  t = (l == 4) ? -update[2] : t;  t = (l == 8) ? +update[1] : t;  t = (l == 12) ? +update[3] : t;
+  t = (l == 1) ? +update[2] : t;  t = (l == 9) ? (SIGN12 > 0 ? +update[0] : -update[0]) : t;  t = (l == 13) ? +update[4] : t;
+  t = (l == 2) ? -update[1] : t;  t = (l == 6) ? +update[0] : t;  t = (l == 14) ? +update[5] : t;
+  return t;
+}
+
+// ref: tracker.cpp:124-163 + depth_tracker.cpp:33-53 / color_tracker.cpp:45-67, one lane: the update
+// from the system and M = Tinc(update) * X (X: the depth tracker's pose matrix, the colour
+// trackers' depth_to_world^-1); the new pose is rigid_from(M)
+template <int N, int SIGN12>
+__device__ __forceinline__ void pose_matrix(const float* hessian, const float* gradient, const float (&X)[16],
+    float (&M)[16], float (&update)[6])
+{
+  solve_step<N>(hessian, gradient, update);
+  float Tinc[16];
+#pragma unroll
+  for (int l = 0; l < 16; ++l) Tinc[l] = tinc_element<SIGN12>(update, l);
+  matmul4(Tinc, X, M);
+}
+
+// column-major 4x4 -> rows 0..2 (make_rt, on the device)
+__device__ __forceinline__ Rt rt_from_colmajor(const float* m)
+{
+  Rt t;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) t.r[r * 4 + c] = m[c * 4 + r];
+  return t;
+}
+
+inline vk_transform identity_transform()
+{
+  vk_transform t;
+  for (int i = 0; i < 16; ++i) t.m[i] = t.inv[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+  return t;
+}
+
 // depth_tracker.cpp:57-84 / color_tracker.cpp:67-95: re-orthonormalise the
 // rotation columns of M and rebuild the rigid transform Translate(t) * Rotate(R)
 // together with its inverse (transform.h:62-66,74-99,146-159).
@@ -720,7 +765,191 @@ __device__ __forceinline__ void finish_step(const float (&update)[6], int32_t* s
   }
 }
 
+// ---- the whole Gauss-Newton loop in one launch ------------------------------------
+//
+// History: two launches per step (r01: partials, then sum + solve), one launch per step
+// (r02: every workgroup finishes the previous step itself), and now one launch per LOOP:
+// the workgroups exchange their sums inside the launch ("partials exchanged inside a launch"
+// above), every workgroup adds all of them in the fixed order and solves the 6x6 system
+// itself — same instructions, same inputs, bit-identical poses everywhere — and goes on to
+// the next step at the new pose. What that removes per step: the launch (~4.5 us on this
+// part), the cold start of the caches (the images now stay in L2 for the whole loop; the
+// depth tracker's frame pixels of a lane stay in its registers), the empty launches after
+// convergence and the host's polling for it (tracker.cpp:162 is a `break` again). Workgroup 0
+// alone publishes pose, system and state, once, at the end.
+//
+// The body of both trackers' loop kernels (track_loop_kernel, vk_icp.hip; color_loop_kernel,
+// vk_color_tracker.hip), THREADS wide. P: the tracker's image parameters; L: its loop parameters
+// (exchange, iterations, state, mirror, ... by name). What is a tracker's own comes from its step:
+//   kTranslation, kSign12   N = 6 or 3; the sign of Tinc(1,2) (tinc_element)
+//   pose                    LDS, 16 floats: the matrix the pixels are evaluated at
+//   base                    LDS, 16 floats: the matrix Tinc multiplies
+//   ends_at_start(L)        a launch that must not start (after the converged test)
+//   load(P, L)              the pose state into LDS, before the first barrier
+//   prepare(L)              after the first barrier, before the first step
+//   accumulate(P, T, g, acc)   the 27 sums of pixel group g at pose T, onto acc
+//   exchanged(L, ...)       after the workgroups' sums are added; false ends the loop
+//   advance(rigid, scratch) first wave: from element (lane & 15) of the new rigid_from(M) to that
+//                           element of the next `pose`; updates the rest of the pose state
+//   write_pose(L, steps, M) workgroup 0 after the loop: the pose from the last step's M
+//   host_pose(L)            the pose left for vk_track_wait
+template <int THREADS, typename Params, typename Loop, typename Step>
+__device__ __forceinline__ void gauss_newton_loop(const Params& P, const Loop& L, Step& S)
+{
+  constexpr int N = Step::kTranslation ? 6 : 3;
+  __shared__ float lds[THREADS / 64][kSysStride];
+  __shared__ float slices[kSysSlices][kSysStride];
+  __shared__ float sums[48];
+  __shared__ float last[16 + 6];          // workgroup 0: M (see below) and update of the last step
+  __shared__ float solve_scratch[64];     // wave_solve_step / wave_rigid_from / the step's own products
+  __shared__ int stop, failed;
+
+  // tracker.cpp:162 / Tracker::CreateState: a state that already says "converged" ends the call
+  const int steps_before = L.fresh_state ? 0 : L.state[0];
+  if (!L.fresh_state && L.state[1])           // uniform over the grid: nobody waits for anybody
+  {
+    // converged earlier: the pose stands. Aborted earlier (a level of a coarse-to-fine Track):
+    // no pose is published, the host sees the Track fail and runs it again, launch per stage
+    if (blockIdx.x == 0 && L.last_launch && L.state[1] != VK_TRACK_ABORTED) publish_host_pose(L.mirror, S.host_pose(L));
+    return;
+  }
+  if (S.ends_at_start(L)) return;
+  if (L.force_abort)
+  {
+    if (blockIdx.x == 0 && threadIdx.x == 0) L.state[1] = VK_TRACK_ABORTED;
+    return;
+  }
+
+  S.load(P, L);
+  if (threadIdx.x == 0) { stop = 0; failed = 0; }
+  __syncthreads();
+  S.prepare(L);
+
+  const bool publisher = blockIdx.x == 0;
+  int steps = 0;
+  for (int it = 0; it < L.iterations; ++it)
+  {
+    VK_STAMP(0);
+    const Rt pose = rt_from_colmajor(S.pose);
+    for (int group = blockIdx.x; group < L.groups; group += gridDim.x)
+    {
+      if (group != (int)blockIdx.x) __syncthreads();   // the previous group's sums have left the LDS
+      float acc[27];
+#pragma unroll
+      for (int i = 0; i < 27; ++i) acc[i] = 0.0f;
+      S.accumulate(P, pose, group, acc);
+      VK_STAMP(1);
+      publish_partial<THREADS / 64>(acc, lds, L.exchange, it, group);
+    }
+    VK_STAMP(2);
+    VK_STAMP(3);
+    if (!gather_partials<THREADS>(L.exchange, it, Step::kTranslation, publisher ? L.hessian : nullptr,
+            publisher ? L.gradient : nullptr, slices, sums, &failed))
+      break;
+    if (!S.exchanged(L, it, sums, &failed, publisher)) break;
+    steps = it + 1;
+    VK_STAMP(4);
+
+    if (threadIdx.x < 64)
+    {
+      // solve + pose update across the lanes of the first wave (wave_solve_step): the bits of
+      // pose_matrix<N> + rigid_from on one lane. The pixels only ever need `pose`; the rest of the
+      // pose (a second 4x4 product per step or more) is made once, after the loop, from the last M.
+      float update[6];
+      wave_solve_step<N>(sums, solve_scratch, update);
+      const float tinc = tinc_element<Step::kSign12>(update, (int)threadIdx.x & 15);
+      if (threadIdx.x < 16) solve_scratch[threadIdx.x] = tinc;
+      wave_lds_fence();
+      const float M_lane = matmul4_lane(solve_scratch, S.base, (int)threadIdx.x);     // Tinc * base
+      wave_lds_fence();
+      const float next = S.advance(wave_rigid_from(M_lane, solve_scratch), solve_scratch);
+      float sq = 0.0f;
+#pragma unroll
+      for (int i = 0; i < N; ++i) sq += update[i] * update[i];
+      if (threadIdx.x < 16)
+      {
+        S.pose[threadIdx.x] = next;
+        if (publisher) last[threadIdx.x] = M_lane;
+      }
+      if (threadIdx.x == 0)
+      {
+        stop = (sqrtf(sq) < 1E-6f) ? 1 : 0;
+        if (publisher)
+        {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) last[16 + i] = update[i];
+        }
+      }
+    }
+    __syncthreads();
+    VK_STAMP(5);
+    if (stop) break;             // tracker.cpp:162
+  }
+
+  if (failed)
+  {
+    // some workgroup's sums never came (see kExchangeTimeout): every workgroup ends up here
+    if (threadIdx.x == 0) L.state[1] = VK_TRACK_ABORTED;
+    return;
+  }
+  if (!publisher) return;
+  S.write_pose(L, steps, last);
+  if (steps > 0)
+  {
+    if (threadIdx.x < 6 && L.update_out) L.update_out[threadIdx.x] = last[16 + threadIdx.x];
+    if (threadIdx.x == 0)
+    {
+      const int iterations = steps_before + steps;
+      L.state[0] = iterations;
+      L.state[1] = stop;
+      if (L.mirror.word)
+        __hip_atomic_store(L.mirror.word, ((unsigned long long)(L.mirror.epoch & 0xffffu) << 48) |
+            ((unsigned long long)(uint32_t)(stop & 1) << 32) | (uint32_t)iterations,
+            __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  if (L.last_launch)
+  {
+    __syncthreads();   // the pose stores are visible to the 32 lanes that copy them out
+    publish_host_pose(L.mirror, S.host_pose(L));
+  }
+}
+
 // ---- host side of the chunked loop ------------------------------------------------
+
+// A loop kernel (gauss_newton_loop) for `iterations` steps on `s`: one launch per kExchangeSteps
+// (ten tag bits name the step; a later launch returns at once if the state says the loop has
+// converged), each on a fresh epoch of the exchange area `workspace`, over as many workgroups as
+// can be resident at once. L: the kernel's loop parameters with everything but the exchange, the
+// timing and the per-launch fields below set. fresh_state: LoopParams::fresh_state of the first
+// launch; ends_track: the last launch leaves the pose for vk_track_wait.
+template <typename Kernel, typename Params, typename Loop>
+int launch_loop(Kernel kernel, int threads, const Params& P, Loop& L, int iterations, int fresh_state, bool ends_track,
+    float* workspace, hipStream_t s)
+{
+  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);   // the exchange holds 64-bit words
+  const int capacity = resident_workgroups(kernel, threads);
+  if (capacity <= 0) return VK_ERR_ARGUMENT;
+  const int grid = L.groups < capacity ? L.groups : capacity;
+  for (int done = 0; done < iterations; done += kExchangeSteps)
+  {
+    L.exchange.words = reinterpret_cast<unsigned long long*>(workspace);
+    L.exchange.count = L.groups;
+    { const int rc = vk_loop_epoch_begin(workspace, exchange_floats(L.groups) * sizeof(float), s, &L.exchange.epoch);  if (rc != VK_OK) return rc; }
+    VK_LOOP_TIMING_ATTACH(L, s);
+    L.iterations = iterations - done < kExchangeSteps ? iterations - done : kExchangeSteps;
+    L.fresh_state = (fresh_state && done == 0) ? fresh_state : 0;
+    L.force_abort = vk_forced_loop_abort();
+    L.last_launch = (ends_track && done + kExchangeSteps >= iterations) ? 1 : 0;
+    Params Pk = P;
+    vk_loop_launch_begin(s);
+    const hipError_t le = launch_loop_kernel(kernel, grid, threads, s, Pk, L);
+    vk_loop_launch_end(s);
+    VK_CHECK(le);
+    VK_LAUNCH_CHECK();
+  }
+  return VK_OK;
+}
 
 // After the steps up to `target` have been enqueued on `s`: wait until the mirror shows that
 // many steps or a converged loop, and say whether the loop had converged BY step `target`
@@ -765,6 +994,48 @@ inline Mirror begin_mirror(const vk_track_poll* poll)
   m.epoch = (uint32_t)host[2];
   m.host_pose = poll->host_pose;
   return m;
+}
+
+// vk_icp.hip: the second stage into hessian / gradient (system_final_kernel), and the pose to the
+// caller's pinned memory (publish_pose_kernel), for both trackers
+void launch_system_sums(const float* workspace, int partials, int translation_enabled, float* hessian, float* gradient,
+    hipStream_t s);
+void launch_publish_pose(const Mirror& mirror, const vk_transform* pose, hipStream_t s);
+
+// The loop with a `reduce` hook (a multi-GPU rig: the packed system is summed over the ranks
+// before every rank solves it), launch per stage: per step the partials (`partials(s)`), their
+// sums into system[0, 48), reduce(system), the one-lane solve and pose update (`solve(s)`). Then
+// the pose goes to the caller's pinned memory if it asked for it.
+template <typename Partials, typename Solve>
+int staged_loop(int iterations, int translation_enabled, int partials, float* workspace, float* system,
+    vk_icp_reduce_fn reduce, void* reduce_user, const vk_track_poll* poll, const Mirror& mirror,
+    const vk_transform* pose, void* stream, Partials launch_partials, Solve launch_solve)
+{
+  hipStream_t s = vk_s(stream);
+  const bool chunked = polling(poll);
+  for (int it = 0; it < iterations; ++it)
+  {
+    launch_partials(s);
+    launch_system_sums(workspace, partials, translation_enabled, system, system + 36, s);
+    VK_LAUNCH_CHECK();
+    const int rr = reduce(system, 48, reduce_user, stream);
+    if (rr != 0) return rr;
+    launch_solve(s);
+    VK_LAUNCH_CHECK();
+
+    // tracker.cpp:162: the reference leaves its loop once |update| < 1e-6. Steps enqueued
+    // after that point are no-ops, but each still costs its launches; so the host looks
+    // at the mirror every `chunk` steps — at the state one chunk back, so a chunk of launches
+    // is always queued behind it — and stops enqueuing when the loop has converged.
+    if (chunked && (it + 1) % poll->chunk == 0 && it + 1 >= 2 * poll->chunk && it + 1 < iterations &&
+        wait_for_steps(mirror, it + 1 - poll->chunk, s)) break;
+  }
+  if (mirror.host_pose)
+  {
+    launch_publish_pose(mirror, pose, s);
+    VK_LAUNCH_CHECK();
+  }
+  return VK_OK;
 }
 
 // ---- how an image's pixels are grouped into partial sums --------------------------

@@ -37,16 +37,6 @@ struct IcpParams
   int group_pixels;             // frame pixels per partial sum (group_pixels_for)
 };
 
-__device__ __forceinline__ Rt rt_from_colmajor(const float* m)
-{
-  Rt t;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) t.r[r * 4 + c] = m[c * 4 + r];
-  return t;
-}
-
 // ref: depth_tracker.cu:18-94 Evaluate<translation_enabled>; returns false when
 // the pixel contributes nothing (residual 0, Jacobian 0).
 // what a frame pixel contributes that does not depend on the pose being solved for: its
@@ -154,9 +144,6 @@ __global__ __launch_bounds__(256) void jacobian_kernel(IcpParams P, float* __res
 #pragma unroll
   for (int i = 0; i < 6; ++i) out[i] = J[i];
 }
-
-__device__ void solve_update(const float* hessian, const float* gradient, int translation_enabled,
-    vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror);
 
 // ref: depth_tracker.cu:144-268. Slot layout of a partial: [0,6) J^T r,
 // [6,27) packed lower triangle of J^T J in (r, c<=r) row-major order.
@@ -308,58 +295,28 @@ __global__ __launch_bounds__(kIcpThreads) void system_partial_kernel(IcpParams P
   store_partial<kIcpThreads / 64>(acc, lds, workspace);
 }
 
-// Second stage: one workgroup. With `Twc` non-null it also solves and updates the
-// pose, so a Gauss-Newton iteration is two launches.
+// Second stage, both trackers' (launch_system_sums): one workgroup.
 __global__ __launch_bounds__(256) void system_final_kernel(const float* __restrict__ workspace,
-    int partials, int translation_enabled, float* __restrict__ hessian, float* __restrict__ gradient,
-    vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
+    int partials, int translation_enabled, float* __restrict__ hessian, float* __restrict__ gradient)
 {
   __shared__ float slices[kSysSlices][kSysStride];
-  __shared__ float sums[48];   // hessian[36] | gradient[6]: the solve reads them from LDS
-  if (state && state[1]) return;   // converged: the system was not recomputed, keep the last one
+  __shared__ float sums[48];
   sum_partials(workspace, partials, translation_enabled, hessian, gradient, slices, sums);
-  if (Twc && threadIdx.x == 0) solve_update(sums, sums + 36, translation_enabled, Twc, state, update_out, mirror);
 }
 
 // ---- pose update on the device ------------------------------------------------
 
 // ref: tracker.cpp:124-163 + depth_tracker.cpp:22-86. One lane; 6x6 is too
 // small to spread.
-// the new pose (out_m, out_i) from the system and the old pose matrix
-// M = Tinc(update) * old pose matrix; the new pose is rigid_from(M)
-template <int N>
-__device__ __forceinline__ void pose_matrix(const float* hessian, const float* gradient, const float (&old_m)[16],
-    float (&M)[16], float (&update)[6])
-{
-  solve_step<N>(hessian, gradient, update);
-
-  // depth_tracker.cpp:33-53, including Tinc(1,2) = +update[0]
-  float Tinc[16];
-  Tinc[0] = 1.0f;        Tinc[4] = -update[2]; Tinc[8] = +update[1];  Tinc[12] = +update[3];
-  Tinc[1] = +update[2];  Tinc[5] = 1.0f;       Tinc[9] = +update[0];  Tinc[13] = +update[4];
-  Tinc[2] = -update[1];  Tinc[6] = +update[0]; Tinc[10] = 1.0f;       Tinc[14] = +update[5];
-  Tinc[3] = 0.0f;        Tinc[7] = 0.0f;       Tinc[11] = 0.0f;       Tinc[15] = 1.0f;
-
-  matmul4(Tinc, old_m, M);
-}
-
-template <int N>
-__device__ __forceinline__ void pose_step(const float* hessian, const float* gradient, const float (&old_m)[16],
-    float (&out_m)[16], float (&out_i)[16], float (&update)[6])
-{
-  float M[16];
-  pose_matrix<N>(hessian, gradient, old_m, M, update);
-  rigid_from(M, out_m, out_i);
-}
-
 template <int N>
 __device__ __forceinline__ void solve_update_n(const float* hessian, const float* gradient,
     vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
 {
-  float update[6], old_m[16], out_m[16], out_i[16];
+  float update[6], old_m[16], M[16], out_m[16], out_i[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) old_m[i] = Twc->m[i];
-  pose_step<N>(hessian, gradient, old_m, out_m, out_i, update);
+  pose_matrix<N, +1>(hessian, gradient, old_m, M, update);     // M = Tinc(update) * old pose matrix
+  rigid_from(M, out_m, out_i);
 #pragma unroll
   for (int i = 0; i < 16; ++i) { Twc->m[i] = out_m[i]; Twc->inv[i] = out_i[i]; }
   finish_step<N>(update, state, update_out, mirror);
@@ -380,24 +337,13 @@ __global__ void solve_update_kernel(const float* __restrict__ hessian, const flo
     solve_update(hessian, gradient, translation_enabled, Twc, state, update_out, mirror);
 }
 
-// ---- the whole Gauss-Newton loop in one launch ------------------------------------
-//
-// History: two launches per step (r01: partials, then sum + solve), one launch per step
-// (r02: every workgroup finishes the previous step itself), and now one launch per LOOP:
-// the workgroups exchange their sums inside the launch (vk_gauss_newton.hpp, "partials
-// exchanged inside a launch"), every workgroup adds all of them in the fixed order and
-// solves the 6x6 system itself — same instructions, same inputs, bit-identical poses
-// everywhere — and goes on to the next step at the new pose. What that removes per step:
-// the launch (~4.5 us on this part), the cold start of the caches (the images now stay
-// in L2 for the whole loop; the frame pixels of a lane stay in its registers), the
-// empty launches after convergence and the host's polling for it (tracker.cpp:162 is a
-// `break` again). Workgroup 0 alone publishes pose, system and state, once, at the end.
+// ---- the whole Gauss-Newton loop in one launch (gauss_newton_loop, vk_gauss_newton.hpp) ----
 struct LoopParams
 {
   Exchange exchange;             // {tag, value} words of the launch's workgroups
   VK_LOOP_TIMING_FIELD
   vk_transform* pose;            // in: the pose to start from; out: the pose after the loop
-  int groups;                    // 1024-pixel groups of the frame (gridDim.x <= groups)
+  int groups;                    // pixel groups of the frame (gridDim.x <= groups)
   int iterations;
   int fresh_state;               // 1: the loop starts at {0 steps, not converged} whatever `state` holds;
                                  // 2: the same, unless an earlier level of this Track was aborted
@@ -411,66 +357,46 @@ struct LoopParams
   Mirror mirror;
 };
 
+// The depth tracker's part of a step: the pose matrix in LDS is what the pixels use and what
+// Tinc multiplies (depth_tracker.cpp:33-53); its inverse is made once, after the loop.
 template <bool TRANSLATION>
-__global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, LoopParams L)
+struct DepthStep
 {
-  constexpr int N = TRANSLATION ? 6 : 3;
-  __shared__ float lds[kIcpThreads / 64][kSysStride];
-  __shared__ float slices[kSysSlices][kSysStride];
-  __shared__ float sums[48];
-  __shared__ float pose_m[16];
-  __shared__ float result[16 + 6];        // workgroup 0: M (see below) and update of the last step
-  __shared__ float solve_scratch[64];     // wave_solve_step / wave_rigid_from
-  __shared__ int stop, failed;
+  static constexpr bool kTranslation = TRANSLATION;
+  static constexpr int kSign12 = +1;       // Tinc(1,2) = +update[0] (tinc_element)
+  float* pose;
+  const float* base;
+  bool resident;
+  FramePixel px[kIcpPixels];
 
-  // tracker.cpp:162 / Tracker::CreateState: a state that already says "converged" ends the call
-  const int steps_before = L.fresh_state ? 0 : L.state[0];
-  if (!L.fresh_state && L.state[1])           // uniform over the grid: nobody waits for anybody
-  {
-    if (blockIdx.x == 0 && L.last_launch && L.state[1] != VK_TRACK_ABORTED) publish_host_pose(L.mirror, L.pose);
-    return;
-  }
+  __device__ __forceinline__ explicit DepthStep(float* pose_m) : pose(pose_m), base(pose_m) {}
+
   // an aborted level ends the whole Track: the next level must not start from the pose it left
   // behind and report success (the host then runs the Track again, launch per stage)
-  if (L.fresh_state == 2 && L.state[1] == VK_TRACK_ABORTED) return;
-  if (L.force_abort)
+  __device__ __forceinline__ bool ends_at_start(const LoopParams& L) const
   {
-    if (blockIdx.x == 0 && threadIdx.x == 0) L.state[1] = VK_TRACK_ABORTED;
-    return;
+    return L.fresh_state == 2 && L.state[1] == VK_TRACK_ABORTED;
   }
 
-  // with one group of at most kIcpPixels trips per workgroup the lane's frame pixels never
-  // change: loaded once, kept in registers over all steps
-  const bool resident = (int)gridDim.x >= L.groups && P.group_pixels <= kIcpPixels * kIcpThreads;
-  FramePixel px[kIcpPixels];
-  if (resident) load_pixels(P, blockIdx.x, 0, px);
-
-  if (threadIdx.x < 16) pose_m[threadIdx.x] = L.pose->m[threadIdx.x];
-  if (threadIdx.x == 0) { stop = 0; failed = 0; }
-  __syncthreads();
-
-  const bool publisher = blockIdx.x == 0;
-  int steps = 0;
-  for (int it = 0; it < L.iterations; ++it)
+  __device__ __forceinline__ void load(const IcpParams& P, const LoopParams& L)
   {
-    VK_STAMP(0);
-    const Rt Twc = rt_from_colmajor(pose_m);
-    for (int group = blockIdx.x; group < L.groups; group += gridDim.x)
-    {
-      if (group != (int)blockIdx.x) __syncthreads();   // the previous group's sums have left the LDS
-      float acc[27];
-#pragma unroll
-      for (int i = 0; i < 27; ++i) acc[i] = 0.0f;
-      if (resident) accumulate_pixels<TRANSLATION>(P, Twc, group, 0, px, acc);
-      else accumulate_group<TRANSLATION>(P, Twc, group, acc);
-      VK_STAMP(1);
-      publish_partial<kIcpThreads / 64>(acc, lds, L.exchange, it, group);
-    }
-    VK_STAMP(2);
-    VK_STAMP(3);
-    if (!gather_partials<kIcpThreads>(L.exchange, it, TRANSLATION, publisher ? L.hessian : nullptr,
-            publisher ? L.gradient : nullptr, slices, sums, &failed))
-      break;
+    // with one group of at most kIcpPixels trips per workgroup the lane's frame pixels never
+    // change: loaded once, kept in registers over all steps
+    resident = (int)gridDim.x >= L.groups && P.group_pixels <= kIcpPixels * kIcpThreads;
+    if (resident) load_pixels(P, blockIdx.x, 0, px);
+    if (threadIdx.x < 16) pose[threadIdx.x] = L.pose->m[threadIdx.x];
+  }
+
+  __device__ __forceinline__ void prepare(const LoopParams& L) {}
+
+  __device__ __forceinline__ void accumulate(const IcpParams& P, const Rt& Twc, int group, float (&acc)[27])
+  {
+    if (resident) accumulate_pixels<TRANSLATION>(P, Twc, group, 0, px, acc);
+    else accumulate_group<TRANSLATION>(P, Twc, group, acc);
+  }
+
+  __device__ __forceinline__ bool exchanged(const LoopParams& L, int it, float* sums, int* failed, bool publisher)
+  {
     if (L.rig.world > 0)
     {
       // a rigid rig: this view's sums go to every rank, every rank's come back (vk_rig_protocol.h);
@@ -486,7 +412,7 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
         const bool arrived = rig_gather(L.rig.areas[L.rig.rank], L.rig.world, L.rig.sequence, it, (int)threadIdx.x, total,
             [](const unsigned long long* at) { return __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); },
             [deadline] { __builtin_amdgcn_s_sleep(VK_POLL_GAP); return (unsigned long long)wall_clock64() > deadline; });
-        if (!arrived) failed = 1;
+        if (!arrived) *failed = 1;
         else
         {
           sums[threadIdx.x < 6 ? 36 + threadIdx.x : threadIdx.x - 6] = total;
@@ -498,87 +424,35 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
         }
       }
       __syncthreads();
-      if (failed) break;
+      if (*failed) return false;
     }
-    steps = it + 1;
-    VK_STAMP(4);
-
-    if (threadIdx.x < 64)
-    {
-      // solve + pose update across the lanes of the first wave (wave_solve_step): the bits of
-      // pose_matrix<N> + rigid_from on one lane. The pixels only ever need the pose's matrix; its
-      // inverse (a second 4x4 product per step) is made once, after the loop, from the last M.
-      float update[6];
-      wave_solve_step<N>(sums, solve_scratch, update);
-      // depth_tracker.cpp:33-53, including Tinc(1,2) = +update[0]; element l = c * 4 + r
-      const int l = (int)threadIdx.x & 15;
-      float tinc = (l % 5 == 0) ? 1.0f : 0.0f;
-      tinc = (l == 4) ? -update[2] : tinc;  tinc = (l == 8) ? +update[1] : tinc;  tinc = (l == 12) ? +update[3] : tinc;
-      tinc = (l == 1) ? +update[2] : tinc;  tinc = (l == 9) ? +update[0] : tinc;  tinc = (l == 13) ? +update[4] : tinc;
-      tinc = (l == 2) ? -update[1] : tinc;  tinc = (l == 6) ? +update[0] : tinc;  tinc = (l == 14) ? +update[5] : tinc;
-      if (threadIdx.x < 16) solve_scratch[threadIdx.x] = tinc;
-      wave_lds_fence();
-      const float M_lane = matmul4_lane(solve_scratch, pose_m, (int)threadIdx.x);     // Tinc * old pose
-      wave_lds_fence();
-      const float out = wave_rigid_from(M_lane, solve_scratch);
-      float sq = 0.0f;
-#pragma unroll
-      for (int i = 0; i < N; ++i) sq += update[i] * update[i];
-      if (threadIdx.x < 16)
-      {
-        pose_m[threadIdx.x] = out;
-        if (publisher) result[threadIdx.x] = M_lane;
-      }
-      if (threadIdx.x == 0)
-      {
-        stop = (sqrtf(sq) < 1E-6f) ? 1 : 0;
-        if (publisher)
-        {
-#pragma unroll
-          for (int i = 0; i < 6; ++i) result[16 + i] = update[i];
-        }
-      }
-    }
-    __syncthreads();
-    VK_STAMP(5);
-    if (stop) break;             // tracker.cpp:162
+    return true;
   }
 
-  if (failed)
+  __device__ __forceinline__ float advance(float rigid, float* scratch) { return rigid; }
+
+  __device__ __forceinline__ void write_pose(const LoopParams& L, int steps, const float* M_last)
   {
-    // some workgroup's sums never came (see kExchangeTimeout): every workgroup ends up here
-    if (threadIdx.x == 0) L.state[1] = VK_TRACK_ABORTED;
-    return;
-  }
-  if (!publisher) return;
-  if (steps > 0)
-  {
-    if (threadIdx.x == 0)
+    if (steps > 0 && threadIdx.x == 0)
     {
       float M[16], out_m[16], out_i[16];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) M[i] = result[i];
+      for (int i = 0; i < 16; ++i) M[i] = M_last[i];
       rigid_from(M, out_m, out_i);
 #pragma unroll
       for (int i = 0; i < 16; ++i) { L.pose->m[i] = out_m[i]; L.pose->inv[i] = out_i[i]; }
     }
-    if (threadIdx.x < 6 && L.update_out) L.update_out[threadIdx.x] = result[16 + threadIdx.x];
-    if (threadIdx.x == 0)
-    {
-      const int iterations = steps_before + steps;
-      L.state[0] = iterations;
-      L.state[1] = stop;
-      if (L.mirror.word)
-        __hip_atomic_store(L.mirror.word, ((unsigned long long)(L.mirror.epoch & 0xffffu) << 48) |
-            ((unsigned long long)(uint32_t)(stop & 1) << 32) | (uint32_t)iterations,
-            __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
   }
-  if (L.last_launch)
-  {
-    __syncthreads();   // lane 0's pose stores are visible to the 32 lanes that copy them out
-    publish_host_pose(L.mirror, L.pose);
-  }
+
+  __device__ __forceinline__ const vk_transform* host_pose(const LoopParams& L) const { return L.pose; }
+};
+
+template <bool TRANSLATION>
+__global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, LoopParams L)
+{
+  __shared__ float pose_m[16];
+  DepthStep<TRANSLATION> step(pose_m);
+  gauss_newton_loop<kIcpThreads>(P, L, step);
 }
 
 // ------------------------------------------------------------------ pyramid ----
@@ -796,56 +670,45 @@ void launch_partials(const IcpParams& P, int translation_enabled, int partials, 
     hipLaunchKernelGGL(system_partial_kernel<false>, dim3(partials), dim3(kIcpThreads), 0, s, P, workspace);
 }
 
-// the rig's launch-per-stage loop ends with this when the caller wants the pose in host memory
+// the launch-per-stage loops of both trackers end with this when the caller wants the pose in host memory
 __global__ void publish_pose_kernel(Mirror mirror, const vk_transform* pose)
 {
   publish_host_pose(mirror, pose);
 }
 
-// the non-rig loop: one launch (track_loop_kernel)
-int launch_loop(const IcpParams& P, vk_transform* Twc_dev, int iterations, int translation_enabled, int groups,
-    float* workspace, float* hessian, float* gradient, int32_t* state_dev, float* update_dev, Mirror mirror,
-    int fresh_state, bool ends_track, hipStream_t s, const vk_rig_exchange* rig = nullptr)
+// the depth loop: one launch (track_loop_kernel)
+int launch_track_loop(const IcpParams& P, vk_transform* Twc_dev, int iterations, int translation_enabled, int groups,
+    float* workspace, float* system, int32_t* state_dev, float* update_dev, Mirror mirror, int fresh_state,
+    bool ends_track, hipStream_t s, const vk_rig_exchange* rig = nullptr)
 {
-  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);   // the exchange holds 64-bit words
-  const int capacity = translation_enabled ? resident_workgroups(track_loop_kernel<true>, kIcpThreads)
-                                           : resident_workgroups(track_loop_kernel<false>, kIcpThreads);
-  if (capacity <= 0) return VK_ERR_ARGUMENT;
-  const int grid = groups < capacity ? groups : capacity;
   LoopParams L;
   L.pose = Twc_dev;
   L.groups = groups;
-  L.hessian = hessian;
-  L.gradient = gradient;
+  L.hessian = system;
+  L.gradient = system + 36;
   L.state = state_dev;
   L.update_out = update_dev;
   L.mirror = mirror;
   memset(&L.rig, 0, sizeof(L.rig));
   if (rig) L.rig = *rig;
-  // ten tag bits name the step: a longer loop continues in another launch (which returns at
-  // once if the state says the loop has converged)
-  for (int done = 0; done < iterations; done += kExchangeSteps)
-  {
-    L.exchange.words = reinterpret_cast<unsigned long long*>(workspace);
-    L.exchange.count = groups;
-    { const int rc = vk_loop_epoch_begin(workspace, exchange_floats(groups) * sizeof(float), s, &L.exchange.epoch);  if (rc != VK_OK) return rc; }
-    VK_LOOP_TIMING_ATTACH(L, s);
-    L.iterations = iterations - done < kExchangeSteps ? iterations - done : kExchangeSteps;
-    L.fresh_state = (fresh_state && done == 0) ? fresh_state : 0;
-    L.force_abort = vk_forced_loop_abort();
-    L.last_launch = (ends_track && done + kExchangeSteps >= iterations) ? 1 : 0;
-    IcpParams Pk = P;
-    vk_loop_launch_begin(s);
-    const hipError_t le = translation_enabled ? launch_loop_kernel(track_loop_kernel<true>, grid, kIcpThreads, s, Pk, L)
-                                              : launch_loop_kernel(track_loop_kernel<false>, grid, kIcpThreads, s, Pk, L);
-    vk_loop_launch_end(s);
-    VK_CHECK(le);
-    VK_LAUNCH_CHECK();
-  }
-  return VK_OK;
+  return translation_enabled
+      ? launch_loop(track_loop_kernel<true>, kIcpThreads, P, L, iterations, fresh_state, ends_track, workspace, s)
+      : launch_loop(track_loop_kernel<false>, kIcpThreads, P, L, iterations, fresh_state, ends_track, workspace, s);
 }
 
 }  // namespace
+
+void vk::launch_system_sums(const float* workspace, int partials, int translation_enabled, float* hessian, float* gradient,
+    hipStream_t s)
+{
+  hipLaunchKernelGGL(system_final_kernel, dim3(1), dim3(256), 0, s, workspace, partials, translation_enabled, hessian,
+      gradient);
+}
+
+void vk::launch_publish_pose(const Mirror& mirror, const vk_transform* pose, hipStream_t s)
+{
+  hipLaunchKernelGGL(publish_pose_kernel, dim3(1), dim3(64), 0, s, mirror, pose);
+}
 
 extern "C" {
 
@@ -893,12 +756,8 @@ int vk_icp_compute_system(const vk_icp_view* keyframe, const vk_transform* Twm,
     int translation_enabled, float* workspace, float* hessian, float* gradient, void* stream)
 {
   IcpParams P;
-  vk_transform identity;
-  if (!Twc && Twc_dev)
-  {
-    for (int i = 0; i < 16; ++i) identity.m[i] = identity.inv[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    Twc = &identity;
-  }
+  const vk_transform identity = identity_transform();
+  if (!Twc && Twc_dev) Twc = &identity;
   const int rc = fill_icp(P, keyframe, Twm, frame, Twc);
   if (rc != VK_OK) return rc;
   VK_REQUIRE(workspace && hessian && gradient);
@@ -906,9 +765,7 @@ int vk_icp_compute_system(const vk_icp_view* keyframe, const vk_transform* Twm,
   const int partials = group_count_for(frame->width * frame->height, P.group_pixels);
   launch_partials(P, translation_enabled, partials, workspace, vk_s(stream));
   VK_LAUNCH_CHECK();
-  hipLaunchKernelGGL(system_final_kernel, dim3(1), dim3(256), 0, vk_s(stream), workspace, partials,
-      translation_enabled, hessian, gradient, (vk_transform*)nullptr, (int32_t*)nullptr, (float*)nullptr,
-      Mirror{nullptr, 0, nullptr});
+  launch_system_sums(workspace, partials, translation_enabled, hessian, gradient, vk_s(stream));
   VK_LAUNCH_CHECK();
   return VK_OK;
 }
@@ -919,50 +776,24 @@ int vk_icp_track(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_
     const vk_track_poll* poll, void* stream)
 {
   IcpParams P;
-  vk_transform identity;
-  for (int i = 0; i < 16; ++i) identity.m[i] = identity.inv[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+  const vk_transform identity = identity_transform();
   const int rc = fill_icp(P, keyframe, Twm, frame, &identity);
   if (rc != VK_OK) return rc;
   VK_REQUIRE(Twc_dev && workspace && system && state_dev && iterations > 0);
   P.Twc_dev = Twc_dev;
   P.state = state_dev;
-  float* hessian = system;
-  float* gradient = system + 36;
   const int partials = group_count_for(frame->width * frame->height, P.group_pixels);
-  hipStream_t s = vk_s(stream);
-  const bool chunked = polling(poll);
   const Mirror mirror = begin_mirror(poll);
-
   if (!reduce)
-    return launch_loop(P, Twc_dev, iterations, translation_enabled, partials, workspace, hessian, gradient,
-        state_dev, update_dev, mirror, /*fresh_state*/ 0, /*ends_track*/ true, s);
-
-  for (int it = 0; it < iterations; ++it)
-  {
-    launch_partials(P, translation_enabled, partials, workspace, s);
-
-    // multi-GPU rig: sum the packed system over ranks before every rank solves it
-    hipLaunchKernelGGL(system_final_kernel, dim3(1), dim3(256), 0, s, workspace, partials, translation_enabled,
-        hessian, gradient, (vk_transform*)nullptr, (int32_t*)nullptr, (float*)nullptr, Mirror{nullptr, 0, nullptr});
-    VK_LAUNCH_CHECK();
-    const int rr = reduce(system, 48, reduce_user, stream);
-    if (rr != 0) return rr;
-    hipLaunchKernelGGL(solve_update_kernel, dim3(1), dim3(64), 0, s, hessian, gradient, translation_enabled,
-        Twc_dev, state_dev, update_dev, mirror);
-    VK_LAUNCH_CHECK();
-
-    // tracker.cpp:162: the reference leaves its loop once |update| < 1e-6. Steps enqueued
-    // after that point are no-ops, but each still costs its launches; so the host looks
-    // at the mirror every `chunk` steps and stops enqueuing when the loop has converged.
-    if (chunked && (it + 1) % poll->chunk == 0 && it + 1 >= 2 * poll->chunk && it + 1 < iterations &&
-        wait_for_steps(mirror, it + 1 - poll->chunk, s)) break;
-  }
-  if (mirror.host_pose)
-  {
-    hipLaunchKernelGGL(publish_pose_kernel, dim3(1), dim3(64), 0, s, mirror, Twc_dev);
-    VK_LAUNCH_CHECK();
-  }
-  return VK_OK;
+    return launch_track_loop(P, Twc_dev, iterations, translation_enabled, partials, workspace, system, state_dev,
+        update_dev, mirror, /*fresh_state*/ 0, /*ends_track*/ true, vk_s(stream));
+  return staged_loop(iterations, translation_enabled, partials, workspace, system, reduce, reduce_user, poll, mirror,
+      Twc_dev, stream,
+      [&](hipStream_t s) { launch_partials(P, translation_enabled, partials, workspace, s); },
+      [&](hipStream_t s) {
+        hipLaunchKernelGGL(solve_update_kernel, dim3(1), dim3(64), 0, s, system, system + 36, translation_enabled,
+            Twc_dev, state_dev, update_dev, mirror);
+      });
 }
 
 // the pose travels in the dispatch packet: no staging copy, no host synchronisation
@@ -1071,15 +902,14 @@ static int pyramid_track(const vk_icp_view* keyframe, const vk_transform* Twm, c
     const vk_icp_view* views[2][2] = {{&half[0], &half[1]}, {keyframe, frame}};
     const int steps[2] = {15, 20};
     const Mirror mirror = begin_mirror(poll);
-    vk_transform identity;
-    for (int i = 0; i < 16; ++i) identity.m[i] = identity.inv[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    const vk_transform identity = identity_transform();
     for (int level = 0; level < 2; ++level)
     {
       IcpParams P;
       const int rc = fill_icp(P, views[level][0], Twm, views[level][1], &identity);
       if (rc != VK_OK) return rc;
-      const int rl = launch_loop(P, Twc_dev, steps[level], 1, group_count_for(views[level][1]->width * views[level][1]->height, P.group_pixels),
-          workspace, system, system + 36, state_dev, update_dev, mirror, /*fresh_state*/ level == 0 ? 1 : 2, /*ends_track*/ level == 1, s);
+      const int rl = launch_track_loop(P, Twc_dev, steps[level], 1, group_count_for(views[level][1]->width * views[level][1]->height, P.group_pixels),
+          workspace, system, state_dev, update_dev, mirror, /*fresh_state*/ level == 0 ? 1 : 2, /*ends_track*/ level == 1, s);
       if (rl != VK_OK) return rl;
     }
     return VK_OK;
@@ -1136,8 +966,7 @@ int vk_icp_track_rig(const vk_icp_view* keyframe, const vk_transform* Twm, const
     int32_t* state_dev, float* update_dev, const vk_rig_exchange* rig, const vk_track_poll* poll, void* stream)
 {
   IcpParams P;
-  vk_transform identity;
-  for (int i = 0; i < 16; ++i) identity.m[i] = identity.inv[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+  const vk_transform identity = identity_transform();
   const int rc = fill_icp(P, keyframe, Twm, frame, &identity);
   if (rc != VK_OK) return rc;
   VK_REQUIRE(Twc_dev && workspace && system && state_dev && iterations > 0 && iterations <= 1000);
@@ -1147,8 +976,8 @@ int vk_icp_track_rig(const vk_icp_view* keyframe, const vk_transform* Twm, const
   P.Twc_dev = Twc_dev;
   P.state = state_dev;
   const int partials = group_count_for(frame->width * frame->height, P.group_pixels);
-  return launch_loop(P, Twc_dev, iterations, translation_enabled, partials, workspace, system, system + 36,
-      state_dev, update_dev, begin_mirror(poll), /*fresh_state*/ 0, /*ends_track*/ true, vk_s(stream), rig);
+  return launch_track_loop(P, Twc_dev, iterations, translation_enabled, partials, workspace, system, state_dev,
+      update_dev, begin_mirror(poll), /*fresh_state*/ 0, /*ends_track*/ true, vk_s(stream), rig);
 }
 
 int vk_track_wait(const vk_track_poll* poll, void* stream)
