@@ -173,12 +173,12 @@ def test_timing_events_are_used_up_by_a_call_that_fails(api):
 
 # --------------------------------- the next Track's pyramid behind the raycast --
 
-def test_pyramid_made_behind_the_raycast_equals_the_pyramid_launch(api, orc):
-    """vk_trace_ahead_pyramid: the raycast's launch also makes the NEXT Track's pyramid — the next input
-    frame's normal image and half-resolution level, the raycast's own normal image and half-resolution level (behind the
-    raycast's row counters) — and vk_icp_pyramid_track_built then launches the two loops only. Against Tracer.trace +
-    PyramidTracker.track (the pyramid launch): the same raycast, the same four images, the same pyramid buffer, the same pose,
-    bit for bit; the normal images are the oracle's; the record serves once and names its images."""
+def test_pyramid_ahead_calls_are_the_trace_and_the_pyramid_launch(api, orc):
+    """vk_trace_ahead_pyramid / vk_icp_pyramid_track_built (ABI 7; the pyramid that rode behind the raycast is retired,
+    tools/patches/README.md): the first is vk_trace_ahead — the raycast, its normal image, nothing of the next frame — and
+    leaves the record invalid; the second is vk_icp_pyramid_track_frame with its pyramid launch. Against Tracer.trace +
+    PyramidTracker.track: the same raycast, the same normal images (the oracle's), the same pyramid buffer, the same pose,
+    bit for bit; a record made valid by hand, even one that names the right images, is not used and is cleared."""
     import torch
     import bench
     lib = api.lib()
@@ -205,7 +205,7 @@ def test_pyramid_made_behind_the_raycast_equals_the_pyramid_launch(api, orc):
     pose_a = track_a.track(next_a, compute_normals=True)
     sync()
 
-    # ---- the riding form, through the C ABI
+    # ---- the same through the two ABI-7 calls
     key_b = api.Frame(torch.zeros((bench.H, bench.W), dtype=torch.float32, device="cuda"), k, poses[0],
                       color=torch.zeros((bench.H, bench.W, 3), dtype=torch.float32, device="cuda"),
                       normals=torch.full((bench.H, bench.W, 3), -7.0, dtype=torch.float32, device="cuda"))
@@ -215,6 +215,7 @@ def test_pyramid_made_behind_the_raycast_equals_the_pyramid_launch(api, orc):
     n = int(lib.vk_icp_pyramid_floats(bench.W, bench.H, bench.W, bench.H))
     pyramid = torch.full((n,), -5.0, dtype=torch.float32, device="cuda")
     built = T.PyramidAhead()
+    built.valid = 1
     next_view, key_view = t._view(next_b), t._view(key_b)
     vb = tracer.view_bounds
     vb.valid = 0
@@ -222,41 +223,45 @@ def test_pyramid_made_behind_the_raycast_equals_the_pyramid_launch(api, orc):
                                          key_b.color.data_ptr(), key_b.normals.data_ptr(), C.byref(next_view), pyramid.data_ptr(),
                                          C.byref(built), api.stream()), "vk_trace_ahead_pyramid")
     sync()
-    assert built.valid == 1 and built.key_depths == key_b.depth.data_ptr() and built.frame_normals == next_b.normals.data_ptr()
+    assert built.valid == 0
     assert torch.equal(key_b.depth, key_a.depth) and torch.equal(key_b.color, key_a.color)
     want_key_normals = orc.compute_normals(key_a.depth.cpu().numpy(), k)
     assert np.array_equal(key_b.normals.cpu().numpy(), want_key_normals, equal_nan=True)
-    assert np.array_equal(next_b.normals.cpu().numpy(), orc.compute_normals(inputs[1][0], k), equal_nan=True)
-    assert torch.equal(next_b.normals, next_a.normals)
-    assert np.array_equal(pyramid.cpu().numpy(), track_a._pyramid.cpu().numpy()[:n], equal_nan=True), "the half-resolution level differs"
+    assert bool((next_b.normals == -7.0).all()), "the next frame's normal image was written"
+    assert bool((pyramid == -5.0).all()), "the pyramid buffer was written"
     poll = t._poll()
-    t.state.zero_()
     start = poses[0]
-    api.check(lib.vk_icp_pyramid_track_built(C.byref(key_view), C.byref(key_b.depth_to_world), C.byref(next_view), t.pose.data_ptr(),
-                                             C.byref(start), 1 | 2, C.byref(built), pyramid.data_ptr(),
-                                             t._workspace(next_b).data_ptr(), t.system.data_ptr(), t.state.data_ptr(),
-                                             t.update.data_ptr(), None, None, poll, api.stream()), "vk_icp_pyramid_track_built")
-    pose_b = t._wait_pose()
-    assert built.valid == 0                                                 # served once
-    assert bytes(pose_b) == bytes(pose_a)
-    # a record for OTHER images is not used: the call is then vk_icp_pyramid_track_frame, with its pyramid launch
-    built.valid = 1
-    built.frame_depths = key_b.depth.data_ptr()
-    pyramid.fill_(-5.0)
-    next_b.normals.fill_(-7.0)
-    t.state.zero_()
-    api.check(lib.vk_icp_pyramid_track_built(C.byref(key_view), C.byref(key_b.depth_to_world), C.byref(next_view), t.pose.data_ptr(),
-                                             C.byref(start), 1, C.byref(built), pyramid.data_ptr(),
-                                             t._workspace(next_b).data_ptr(), t.system.data_ptr(), t.state.data_ptr(),
-                                             t.update.data_ptr(), None, None, poll, api.stream()), "vk_icp_pyramid_track_built")
-    assert bytes(t._wait_pose()) == bytes(pose_a) and built.valid == 0
-    assert torch.equal(next_b.normals, next_a.normals)
+
+    def track_built():
+        t.state.zero_()
+        api.check(lib.vk_icp_pyramid_track_built(C.byref(key_view), C.byref(key_b.depth_to_world), C.byref(next_view), t.pose.data_ptr(),
+                                                 C.byref(start), 1, C.byref(built), pyramid.data_ptr(),
+                                                 t._workspace(next_b).data_ptr(), t.system.data_ptr(), t.state.data_ptr(),
+                                                 t.update.data_ptr(), None, None, poll, api.stream()), "vk_icp_pyramid_track_built")
+        pose_b = t._wait_pose()
+        assert built.valid == 0
+        assert bytes(pose_b) == bytes(pose_a)
+        assert torch.equal(next_b.normals, next_a.normals)
+        assert np.array_equal(pyramid.cpu().numpy(), track_a._pyramid.cpu().numpy()[:n], equal_nan=True), "the half-resolution level differs"
+
+    track_built()
+    # a record made valid by hand — for other images, then naming exactly these — is not used: the pyramid launch runs
+    for frame_depths in (key_b.depth.data_ptr(), next_b.depth.data_ptr()):
+        built.key_depths, built.key_normals = key_b.depth.data_ptr(), key_b.normals.data_ptr()
+        built.frame_depths, built.frame_normals = frame_depths, next_b.normals.data_ptr()
+        built.pyramid = pyramid.data_ptr()
+        built.key_width, built.key_height, built.frame_width, built.frame_height = bench.W, bench.H, bench.W, bench.H
+        built.valid = 1
+        pyramid.fill_(-5.0)
+        next_b.normals.fill_(-7.0)
+        track_built()
 
 
-def test_tracked_loop_with_the_pyramid_behind_the_raycast_equals_the_loop_without(api, monkeypatch):
-    """bench.FrameLoop('rgbd-icp') — the step bench.py times — with the pyramid riding behind the raycast (VK_BENCH_PYRAMID_AHEAD=1:
-    built and measured to lose, so off in reported runs) and with the pyramid launch in front of the loops: six frames, every tracked pose, the volume, the table
-    and the raycast images bit for bit."""
+def test_tracked_loop_through_the_pyramid_ahead_calls_equals_the_loop_without(api, monkeypatch):
+    """bench.FrameLoop('rgbd-icp') — the step bench.py times — through the ABI-7 pyramid-ahead calls (VK_BENCH_PYRAMID_AHEAD=1:
+    the ride is retired, so they are the raycast with its own normals launch and then the pyramid launch) and through
+    vk_trace_ahead + vk_icp_pyramid_track_frame: six frames, every tracked pose, the volume, the table and the raycast images
+    bit for bit."""
     import torch
     import bench
     frames = 6
@@ -272,7 +277,7 @@ def test_tracked_loop_with_the_pyramid_behind_the_raycast_equals_the_loop_withou
         for i in range(frames):
             loop.step(i)
             if ahead and 0 < i < frames - 1:
-                assert loop.built.valid == 1, "the raycast did not carry the next Track's pyramid"
+                assert loop.built.valid == 0, "the raycast carried the next Track's pyramid"
         sync()
         vol = loop.vols[0]["vol"]
         states.append(([bytes(p) for p in loop.tracked_poses], list(loop.gn_steps), vol.voxels.clone(), vol.hash_entries.clone(),

@@ -10,7 +10,7 @@ import sys
 from collections import defaultdict
 
 KINDS = (("track_loop", "L"), ("pyramid_level", "P"), ("create_requests", "R"), ("handle_visibility", "H"), ("integrate_pipelined", "I"),
-         ("compute_points", "T"), ("trace_and_pyramid", "TP"), ("trace_and_request", "TR"), ("compute_normals", "N"), ("frame_mask", "M"))
+         ("compute_points", "T"), ("trace_and_request", "TR"), ("compute_normals", "N"), ("frame_mask", "M"))
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = []
 for r in csv.DictReader(open(f)):

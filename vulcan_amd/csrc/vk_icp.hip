@@ -821,12 +821,9 @@ size_t vk_icp_pyramid_floats(int key_width, int key_height, int frame_width, int
   return 4 * ((size_t)(key_width / 2) * (key_height / 2) + (size_t)(frame_width / 2) * (frame_height / 2));
 }
 
-// `level_built`: the half-resolution level and both normal images were made behind the previous raycast
-// (vk_trace_ahead_pyramid): no pyramid launch
 static int pyramid_track(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_icp_view* frame,
     vk_transform* Twc_dev, const vk_transform* Twc_start, int frame_normals_due, float* pyramid, float* workspace, float* system,
-    int32_t* state_dev, float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user, const vk_track_poll* poll, void* stream,
-    bool level_built = false, bool frame_side_only = false)
+    int32_t* state_dev, float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user, const vk_track_poll* poll, void* stream)
 {
   VK_REQUIRE(keyframe && Twm && frame && Twc_dev && pyramid && workspace && system && state_dev);
   VK_REQUIRE(keyframe->depths && keyframe->normals && frame->depths && frame->normals);
@@ -881,18 +878,8 @@ static int pyramid_track(const vk_icp_view* keyframe, const vk_transform* Twm, c
   }
   L.pose_out = Twc_start ? Twc_dev : nullptr;
   if (Twc_start) L.pose_start = *Twc_start;
-  if (!level_built || frame_side_only)
-  {
-    // (frame_side_only: the record has the frame's level only, so the frame's workgroups leave at once)
-    if (level_built) L.dst_w[1] = L.dst_h[1] = 0;
-    hipLaunchKernelGGL(pyramid_level_kernel, dim3((gw + 63) / 64, (gh + 3) / 4, 2 + due), dim3(256), 0, s, L);
-    VK_LAUNCH_CHECK();
-  }
-  else if (Twc_start)
-  {
-    hipLaunchKernelGGL(store_transform_kernel, dim3(1), dim3(64), 0, s, Twc_dev, *Twc_start);
-    VK_LAUNCH_CHECK();
-  }
+  hipLaunchKernelGGL(pyramid_level_kernel, dim3((gw + 63) / 64, (gh + 3) / 4, 2 + due), dim3(256), 0, s, L);
+  VK_LAUNCH_CHECK();
 
   // :79-83 half level, 15 steps; :85-89 full level, 20 steps, from the pose the half level left.
   // Tracker::CreateState (tracker.cpp:107-110) starts every Track at iteration 0.
@@ -944,17 +931,10 @@ int vk_icp_pyramid_track_built(const vk_icp_view* keyframe, const vk_transform* 
     float* workspace, float* system, int32_t* state_dev, float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user,
     const vk_track_poll* poll, void* stream)
 {
-  VK_REQUIRE(keyframe && frame);
-  // the record names the images and the buffer the level was built from / into, and serves once
-  const bool level_built = built && built->valid == 1 && built->pyramid == pyramid &&
-      built->key_depths == keyframe->depths && built->key_normals == keyframe->normals &&
-      built->frame_depths == frame->depths && built->frame_normals == frame->normals &&
-      built->key_width == keyframe->width && built->key_height == keyframe->height &&
-      built->frame_width == frame->width && built->frame_height == frame->height;
-  const bool frame_side_only = level_built && built->pad_ == 1;
+  // vk_trace_ahead_pyramid leaves every record invalid (vk.h): none is used, and one made valid by hand is cleared
   if (built) built->valid = 0;
-  return pyramid_track(keyframe, Twm, frame, Twc_dev, Twc_start, level_built ? (frame_side_only ? 2 : 0) : frame_normals_due, pyramid,
-      workspace, system, state_dev, update_dev, reduce, reduce_user, poll, stream, level_built, frame_side_only);
+  return vk_icp_pyramid_track_frame(keyframe, Twm, frame, Twc_dev, Twc_start, frame_normals_due, pyramid, workspace, system,
+      state_dev, update_dev, reduce, reduce_user, poll, stream);
 }
 
 int vk_reduce_nothing(float*, int, void*, void*) { return 0; }

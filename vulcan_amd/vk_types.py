@@ -199,7 +199,7 @@ class RequestsAhead(C.Structure):
 
 
 class PyramidAhead(C.Structure):
-    """vk_pyramid_ahead (vk.h): the images and the buffer a Track's pyramid was built from / into behind the raycast"""
+    """vk_pyramid_ahead (vk.h): ABI 7's record of the retired pyramid ride; the library leaves it invalid"""
     _fields_ = [("key_depths", C.c_void_p), ("key_normals", C.c_void_p), ("frame_depths", C.c_void_p), ("frame_normals", C.c_void_p),
                 ("pyramid", C.c_void_p), ("key_width", C.c_int32), ("key_height", C.c_int32), ("frame_width", C.c_int32),
                 ("frame_height", C.c_int32), ("valid", C.c_int32), ("pad_", C.c_int32)]
