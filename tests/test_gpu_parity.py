@@ -486,6 +486,81 @@ def test_icp_track_converges(api, orc, icp_frames):
     np.testing.assert_allclose(got.matrix() @ got.inverse_matrix(), np.eye(4), atol=1e-5)
 
 
+def _without_parameter(packed, gradient, n, drop):
+    """The packed n x n system with row and column `drop` zeroed (and that gradient entry): rank n - 1."""
+    H = np.zeros((n, n), np.float32)
+    H[np.tril_indices(n)] = packed[: n * (n + 1) // 2]
+    H[drop, :] = 0
+    H[:, drop] = 0
+    g = np.array(gradient[:n], np.float32)
+    g[drop] = 0
+    return H[np.tril_indices(n)].copy(), g
+
+
+@pytest.fixture(scope="module")
+def curved_pair(orc):
+    """The pair of test_icp_track_converges on the host: a gently curved keyframe (all six parameters
+    observable) and the same surface seen from a slightly wrong pose."""
+    w, h = 640, 480
+    k = T.Projection.make(547, 547, 320, 240)
+    y, x = np.mgrid[0:h, 0:w]
+    key_depth = (1.0 + 0.05 * np.cos(3 * x / w) * np.sin(2 * y / h)).astype(np.float32)
+    start = T.Transform.translate(0.002, -0.001, 0.003) * T.Transform.rotate(0.999995, 0.002, -0.0015, 0.001)
+    orc.set_threads(16)
+    hk = orc.HostFrame(key_depth, k, T.Transform.identity())
+    hf = orc.HostFrame(key_depth, k, start)
+    hk.compute_normals()
+    hf.compute_normals()
+    return hk, hf
+
+
+@pytest.mark.parametrize("translation", (True, False), ids=("translation", "rotation_only"))
+@pytest.mark.parametrize("system", ("real", "zero", "rank_deficient"))
+def test_icp_solve_update_matches(api, orc, curved_pair, system, translation):
+    """vk_icp_solve_update against orc.icp_solve_update on the same packed system: the update, Twc.m and
+    Twc.inv bit for bit, and state = {1 step, converged iff |update| < 1e-6} (tracker.cpp:124-163,
+    depth_tracker.cpp:22-86). The system of a real frame pair, an all-zero one (no correspondence: the
+    pose must stand) and a rank-deficient one (one parameter unobservable: a zero pivot in the LDL^T)."""
+    import torch
+    hk, hf = curved_pair
+    n = 6 if translation else 3
+    count = n * (n + 1) // 2
+    Hs, g = orc.icp_system(hk, hf, translation)
+    packed, grad = np.asarray(Hs, np.float32)[:count].copy(), np.asarray(g, np.float32)[:n].copy()
+    if system == "zero":
+        packed[:], grad[:] = 0, 0
+    elif system == "rank_deficient":
+        packed, grad = _without_parameter(packed, grad, n, n - 2)
+    else:
+        diagonal = packed[[i * (i + 1) // 2 + i for i in range(n)]]
+        assert np.all(np.isfinite(packed)) and np.all(diagonal > 0) and np.all(grad != 0)
+    start = hf.depth_to_world
+    want, want_update, norm = orc.icp_solve_update(packed, grad, start, translation)
+
+    dh = torch.zeros(36, dtype=torch.float32, device="cuda")
+    dh[:count] = torch.from_numpy(packed)
+    dg = torch.zeros(6, dtype=torch.float32, device="cuda")       # a buffer of its own, not hessian + 36
+    dg[:n] = torch.from_numpy(grad)
+    pose = torch.from_numpy(np.frombuffer(bytes(start), dtype=np.uint8).copy()).cuda()
+    state = torch.zeros(2, dtype=torch.int32, device="cuda")
+    upd = torch.full((6,), 7.0, dtype=torch.float32, device="cuda")
+    api.check(api.lib().vk_icp_solve_update(api._ptr(dh), api._ptr(dg), int(translation), api._ptr(pose),
+                                            api._ptr(state), api._ptr(upd), api.stream()), "vk_icp_solve_update")
+    sync()
+    got = T.Transform.from_buffer_copy(pose.cpu().numpy().tobytes())
+    bits = lambda v: np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    print(f"{system} translation={translation}: |update| {norm:.3e}, "
+          f"update max dev {np.abs(upd.cpu().numpy() - want_update).max():.3e}, "
+          f"m {np.abs(np.array(got.m[:]) - np.array(want.m[:])).max():.3e}, "
+          f"inv {np.abs(np.array(got.inv[:]) - np.array(want.inv[:])).max():.3e}")
+    assert np.array_equal(bits(upd.cpu().numpy()), bits(want_update))
+    assert np.array_equal(bits(got.m[:]), bits(want.m[:]))
+    assert np.array_equal(bits(got.inv[:]), bits(want.inv[:]))
+    assert state.cpu().numpy().tolist() == [1, 1 if norm < 1e-6 else 0]
+    if system == "zero":
+        assert norm == 0 and np.all(want_update == 0)
+
+
 # ------------------------------------------- full-size properties (5 mm, 640x480) --
 
 def test_full_size_properties(api, orc):

@@ -3,7 +3,7 @@
 //
 // Same shape as the depth tracker (vk_icp.hip): keyframe pixels in groups defined by the
 // image, the 27 sums reduced by DPP row operations and a fixed-order second stage, the 6x6
-// solve and the pose update done by one lane out of registers. Track() is ONE launch for
+// solve and the pose update done by one wave out of registers. Track() is ONE launch for
 // the whole Gauss-Newton loop (color_loop_kernel; three launches per step only with the
 // rig's reduce hook) after one launch that prepares the images (color_begin_kernel).
 // The reference zero-fills, accumulates with 27 float atomics per thread block and
@@ -492,32 +492,22 @@ __device__ __forceinline__ void derive_tcm(const vk_transform& frame_Tcd, const 
   for (int i = 0; i < 16; ++i) { pose->Tcm.m[i] = out_m[i]; pose->Tcm.inv[i] = out_i[i]; }
 }
 
-// ref: tracker.cpp:124-163 + color_tracker.cpp:34-96, one lane: the update from the system, the
-// new depth_to_world (m, inv) from the old inverse, then Tcm
+// ref: tracker.cpp:124-163 + color_tracker.cpp:34-96. One wave solves and makes M = Tinc(update) * Twd^-1
+// (:67, staged_pose_step); lane 0 makes the new depth_to_world (m, inv) from it, then Tcm
 template <int N>
-__device__ __forceinline__ void color_solve_update_n(const float* hessian, const float* gradient,
+__device__ __forceinline__ void color_solve(const float* hessian, const float* gradient,
     const vk_transform& frame_Tcd, const vk_transform& key_Twc, vk_color_pose* pose, int32_t* state,
     float* update_out, Mirror mirror)
 {
-  float update[6], old_i[16], M[16], twd_m[16], twd_i[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) old_i[i] = pose->depth_to_world.inv[i];
-  pose_matrix<N, -1>(hessian, gradient, old_i, M, update);     // :67  M = Tinc * Twd^-1
+  float update[6], M[16], twd_m[16], twd_i[16];
+  staged_pose_step<N, -1>(hessian, gradient, pose->depth_to_world.inv, M, update);
+  if (threadIdx.x != 0) return;
   rigid_from(M, twd_i, twd_m);         // :69-95 world -> depth, re-orthonormalised; .Inverse() swaps the two
 #pragma unroll
   for (int i = 0; i < 16; ++i) { pose->depth_to_world.m[i] = twd_m[i]; pose->depth_to_world.inv[i] = twd_i[i]; }
 
   derive_tcm(frame_Tcd, key_Twc, pose);
   finish_step<N>(update, state, update_out, mirror);
-}
-
-__device__ void color_solve_update(const float* hessian, const float* gradient, int translation_enabled,
-    const vk_transform& frame_Tcd, const vk_transform& key_Twc, vk_color_pose* pose, int32_t* state,
-    float* update_out, Mirror mirror)
-{
-  if (state && state[1]) return;  // converged earlier: tracker.cpp:162
-  if (translation_enabled) color_solve_update_n<6>(hessian, gradient, frame_Tcd, key_Twc, pose, state, update_out, mirror);
-  else color_solve_update_n<3>(hessian, gradient, frame_Tcd, key_Twc, pose, state, update_out, mirror);
 }
 
 struct PoseArgs
@@ -529,11 +519,12 @@ struct PoseArgs
   Mirror mirror;   // pinned host {iterations, converged}, or null (vk_track_poll)
 };
 
-__global__ void color_solve_kernel(const float* __restrict__ hessian, const float* __restrict__ gradient,
+__global__ __launch_bounds__(64) void color_solve_kernel(const float* __restrict__ hessian, const float* __restrict__ gradient,
     int translation_enabled, PoseArgs A)
 {
-  if (threadIdx.x == 0 && blockIdx.x == 0)
-    color_solve_update(hessian, gradient, translation_enabled, A.frame_Tcd, A.key_Twc, A.pose, A.state, A.update_out, A.mirror);
+  if (A.state && A.state[1]) return;  // converged earlier: tracker.cpp:162 (the same answer in every lane)
+  if (translation_enabled) color_solve<6>(hessian, gradient, A.frame_Tcd, A.key_Twc, A.pose, A.state, A.update_out, A.mirror);
+  else color_solve<3>(hessian, gradient, A.frame_Tcd, A.key_Twc, A.pose, A.state, A.update_out, A.mirror);
 }
 
 __global__ void color_prepare_kernel(PoseArgs A)

@@ -255,8 +255,8 @@ __device__ __forceinline__ void wave_lds_fence()
 
 
 // ---- Frame::ComputeNormals for one pixel (ref: frame.cu:9-122): `depth` at (x, y) and the four taps
-// two pixels away (0 = no measurement, or outside the image). Shared by compute_normals_kernel and
-// by the request pass of vk_volume_set_view_prepare when it computes the frame's normals on the way.
+// two pixels away (0 = no measurement, or outside the image). Called by pixel_normal below and by the
+// request pass of vk_volume_set_view_prepare, whose taps come from an LDS tile (vk_requests.hpp).
 template <typename K>
 __device__ __forceinline__ f3 normal_from_taps(const K& k, int x, int y, float depth,
     float left, float right, float up, float down)
@@ -276,6 +276,33 @@ __device__ __forceinline__ f3 normal_from_taps(const K& k, int x, int y, float d
   }
   return normal;
 }
+
+// A w x h depth image read through `load(index)` — a plain load (plain_depths), or the atomic one of the
+// raycast's trailing workgroups (normals_group, vk_trace.hip): the depth at (x, y), 0 outside the image ...
+template <typename Load>
+__device__ __forceinline__ float depth_or_zero(Load load, int w, int h, int x, int y)
+{
+  return (x >= 0 && x < w && y >= 0 && y < h) ? load(y * w + x) : 0.0f;
+}
+
+// ... and the normal of its pixel (x, y), whose own depth the caller has read: every normal image of
+// the library is made of these
+template <typename K, typename Load>
+__device__ __forceinline__ f3 pixel_normal(const K& k, Load load, int w, int h, int x, int y, float depth)
+{
+  const int pad = 2;
+  f3 normal = make3(0, 0, 0);
+  if (depth > 0)
+    normal = normal_from_taps(k, x, y, depth, depth_or_zero(load, w, h, x - pad, y), depth_or_zero(load, w, h, x + pad, y),
+        depth_or_zero(load, w, h, x, y - pad), depth_or_zero(load, w, h, x, y + pad));
+  return normal;
+}
+
+struct plain_depths
+{
+  const float* depths;
+  __device__ __forceinline__ float operator()(int index) const { return depths[index]; }
+};
 
 // ---- LightIntegrator's per-pixel preparation (ref: light_integrator.cu:16-94 frame mask,
 // :215-225 the per-pixel half of the colour kernel) — shared by frame_mask_kernel and by the

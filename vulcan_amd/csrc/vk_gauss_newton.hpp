@@ -421,64 +421,6 @@ __device__ __forceinline__ bool gather_partials(const Exchange& E, int step, int
   return true;
 }
 
-// LDL^T, no pivoting, float32 (the reference calls Eigen::LDLT — unpinned,
-// not vendored; agreement is to rounding). A zero pivot is handled the way
-// Eigen's LDLT handles it (the column of L is left at 0, and the solve sets
-// y[j] = 0 where |D[j]| <= FLT_MIN): an empty or rank-deficient system — no valid
-// correspondence, e.g. an all-hole frame — then yields update = 0, the step norm
-// is below 1e-6 and the pose is left untouched, instead of 0/0 = NaN poisoning
-// the pose (tracker.cpp:153-162). N is a template parameter and every
-// loop is unrolled so that L, D, y live in registers: with a run-time size the
-// arrays are indexed dynamically, land in scratch memory, and the one lane that
-// solves spends ~10 us waiting on it.
-template <int N>
-__device__ __forceinline__ void ldlt_solve(const float (&A)[N * N], const float (&b)[N], float (&x)[N])
-{
-  float L[N * N], D[N], y[N];
-#pragma unroll
-  for (int i = 0; i < N * N; ++i) L[i] = 0.0f;
-
-#pragma unroll
-  for (int j = 0; j < N; ++j)
-  {
-    float d = A[j * N + j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= L[j * N + k] * L[j * N + k] * D[k];
-    D[j] = d;
-    L[j * N + j] = 1.0f;
-
-#pragma unroll
-    for (int i = j + 1; i < N; ++i)
-    {
-      float s = A[i * N + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[i * N + k] * L[j * N + k] * D[k];
-      L[i * N + j] = (fabsf(d) > 0.0f) ? s / d : 0.0f;
-    }
-  }
-
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-  {
-    float s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s -= L[i * N + k] * y[k];
-    y[i] = s;
-  }
-
-#pragma unroll
-  for (int i = 0; i < N; ++i) y[i] = (fabsf(D[i]) > FLT_MIN) ? y[i] / D[i] : 0.0f;
-
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i)
-  {
-    float s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < N; ++k) s -= L[k * N + i] * x[k];
-    x[i] = s;
-  }
-}
-
 __device__ __forceinline__ void matmul4(const float (&A)[16], const float (&B)[16], float (&C)[16])  // matrix.h:297-318
 {
 #pragma unroll
@@ -493,31 +435,6 @@ __device__ __forceinline__ void matmul4(const float (&A)[16], const float (&B)[1
     }
 }
 
-// tracker.cpp:142-159: unpack the packed lower triangle, solve H x = g, update = -x
-// (entries beyond N stay 0)
-template <int N>
-__device__ __forceinline__ void solve_step(const float* hessian, const float* gradient, float (&update)[6])
-{
-  float H[N * N], g[N], x[N];
-  int index = 0;
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j)
-    {
-      H[i * N + j] = hessian[index];
-      H[j * N + i] = hessian[index];
-      ++index;
-    }
-#pragma unroll
-  for (int i = 0; i < N; ++i) g[i] = gradient[i];
-  ldlt_solve<N>(H, g, x);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) update[i] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < N; ++i) update[i] = -x[i];
-}
-
 // Element l = c * 4 + r of the increment Tinc(update) (column-major). depth_tracker.cpp:33-53 has
 // Tinc(1,2) = +update[0], color_tracker.cpp:45-65 a proper skew matrix with
 // Tinc(1,2) = -update[0]: SIGN12 is that sign. With a constant l the selects fold to one term.
@@ -529,20 +446,6 @@ __device__ __forceinline__ float tinc_element(const float (&update)[6], int l)
   t = (l == 1) ? +update[2] : t;  t = (l == 9) ? (SIGN12 > 0 ? +update[0] : -update[0]) : t;  t = (l == 13) ? +update[4] : t;
   t = (l == 2) ? -update[1] : t;  t = (l == 6) ? +update[0] : t;  t = (l == 14) ? +update[5] : t;
   return t;
-}
-
-// ref: tracker.cpp:124-163 + depth_tracker.cpp:33-53 / color_tracker.cpp:45-67, one lane: the update
-// from the system and M = Tinc(update) * X (X: the depth tracker's pose matrix, the colour
-// trackers' depth_to_world^-1); the new pose is rigid_from(M)
-template <int N, int SIGN12>
-__device__ __forceinline__ void pose_matrix(const float* hessian, const float* gradient, const float (&X)[16],
-    float (&M)[16], float (&update)[6])
-{
-  solve_step<N>(hessian, gradient, update);
-  float Tinc[16];
-#pragma unroll
-  for (int l = 0; l < 16; ++l) Tinc[l] = tinc_element<SIGN12>(update, l);
-  matmul4(Tinc, X, M);
 }
 
 // column-major 4x4 -> rows 0..2 (make_rt, on the device)
@@ -594,12 +497,10 @@ __device__ __forceinline__ void rigid_from(const float (&M)[16], float (&out_m)[
 
 // ---- the solve + pose update of one Gauss-Newton step, spread over the lanes of ONE wave ----
 //
-// solve_step / matmul4 / rigid_from above run on one lane: ~1000 dependent instructions of four
-// cycles each, 1.7 us of every step of the loop kernels, on the critical path of every workgroup.
-// Here the same operations — each element computed by exactly the same expression in the same
-// order, so the bits are those of the one-lane code — are laid across lanes: row i of the LDL^T
-// factorisation in lane i (the k-loop of an element stays sequential, the elements of a column
-// are independent), a 4x4 product with one output element per lane. Values cross lanes through
+// On one lane the step is ~1000 dependent instructions of four cycles each: 1.7 us of every step of
+// the loop kernels, on the critical path of every workgroup. Here it is laid across lanes: row i of
+// the LDL^T factorisation in lane i (the k-loop of an element stays sequential, the elements of a
+// column are independent), a 4x4 product with one output element per lane. Values cross lanes through
 // v_readlane (to scalar registers) and, for the transposed accesses, a few LDS words.
 __device__ __forceinline__ float lane_value(float v, int from)
 {
@@ -616,8 +517,16 @@ __device__ __forceinline__ float matmul4_lane(const float* A, const float* B, in
   return r;
 }
 
-// x with H x = g for the packed system in `sums` (LDS: hessian [0, 21), gradient [36, 42)); returns
-// update = -x in every lane (entries beyond N are 0). `scratch`: LDS, 64 floats. One whole wave.
+// tracker.cpp:142-159: x with H x = g for the packed system in `sums` (LDS: hessian [0, 21), gradient
+// [36, 42)); returns update = -x in every lane (entries beyond N are 0). `scratch`: LDS, 64 floats.
+// One whole wave.
+// LDL^T, no pivoting, float32 (the reference calls Eigen::LDLT — unpinned, not vendored; agreement
+// is to rounding). A zero pivot is handled the way Eigen's LDLT handles it (the column of L is left
+// at 0, and the solve sets y[j] = 0 where |D[j]| <= FLT_MIN): an empty or rank-deficient system — no
+// valid correspondence, e.g. an all-hole frame — then yields update = 0, the step norm is below 1e-6
+// and the pose is left untouched, instead of 0/0 = NaN poisoning the pose (tracker.cpp:153-162). N is
+// a template parameter and every loop is unrolled so that A, L, D live in registers: with a run-time
+// size the arrays are indexed dynamically and land in scratch memory.
 template <int N>
 __device__ __forceinline__ void wave_solve_step(const float* sums, float* scratch, float (&update)[6])
 {
@@ -680,6 +589,42 @@ __device__ __forceinline__ void wave_solve_step(const float* sums, float* scratc
   for (int i = 0; i < 6; ++i) update[i] = 0.0f;
 #pragma unroll
   for (int i = 0; i < N; ++i) update[i] = -x[i];
+}
+
+// ref: tracker.cpp:124-163 + depth_tracker.cpp:33-53 / color_tracker.cpp:45-67. From the sums in LDS to
+// element (lane & 15) of M = Tinc(update) * base, and `update` in every lane; the new pose is
+// rigid_from(M). `base`: LDS, 16 floats (the depth tracker's pose matrix, the colour trackers'
+// depth_to_world^-1); `scratch`: LDS, 64 floats. One whole wave.
+template <int N, int SIGN12>
+__device__ __forceinline__ float wave_pose_step(const float* sums, const float* base, float* scratch, float (&update)[6])
+{
+  const int lane = lane_id();
+  wave_solve_step<N>(sums, scratch, update);
+  const float tinc = tinc_element<SIGN12>(update, lane & 15);
+  if (lane < 16) scratch[lane] = tinc;
+  wave_lds_fence();
+  const float M_lane = matmul4_lane(scratch, base, lane);     // Tinc * base
+  wave_lds_fence();
+  return M_lane;
+}
+
+// The same step for the launch-per-stage solve kernels (solve_update_kernel, color_solve_kernel: one
+// wave): the system and the matrix Tinc multiplies come from memory, and every lane gets the whole of M.
+template <int N, int SIGN12>
+__device__ __forceinline__ void staged_pose_step(const float* hessian, const float* gradient, const float* base,
+    float (&M)[16], float (&update)[6])
+{
+  __shared__ float sums[48], matrix[16], scratch[64];
+  const int lane = lane_id();
+  if (lane < N * (N + 1) / 2) sums[lane] = hessian[lane];
+  if (lane < N) sums[36 + lane] = gradient[lane];
+  if (lane < 16) matrix[lane] = base[lane];
+  wave_lds_fence();
+  const float M_lane = wave_pose_step<N, SIGN12>(sums, matrix, scratch, update);
+  if (lane < 16) matrix[lane] = M_lane;
+  wave_lds_fence();
+#pragma unroll
+  for (int i = 0; i < 16; ++i) M[i] = matrix[i];
 }
 
 // rigid_from() with one element of the result per lane: `M_lane` = element (lane & 15) of M in the
@@ -801,7 +746,7 @@ __device__ __forceinline__ void gauss_newton_loop(const Params& P, const Loop& L
   __shared__ float slices[kSysSlices][kSysStride];
   __shared__ float sums[48];
   __shared__ float last[16 + 6];          // workgroup 0: M (see below) and update of the last step
-  __shared__ float solve_scratch[64];     // wave_solve_step / wave_rigid_from / the step's own products
+  __shared__ float solve_scratch[64];     // wave_pose_step / wave_rigid_from / the step's own products
   __shared__ int stop, failed;
 
   // tracker.cpp:162 / Tracker::CreateState: a state that already says "converged" ends the call
@@ -852,16 +797,10 @@ __device__ __forceinline__ void gauss_newton_loop(const Params& P, const Loop& L
 
     if (threadIdx.x < 64)
     {
-      // solve + pose update across the lanes of the first wave (wave_solve_step): the bits of
-      // pose_matrix<N> + rigid_from on one lane. The pixels only ever need `pose`; the rest of the
-      // pose (a second 4x4 product per step or more) is made once, after the loop, from the last M.
+      // solve + pose update across the lanes of the first wave. The pixels only ever need `pose`; the rest
+      // of the pose (a second 4x4 product per step or more) is made once, after the loop, from the last M.
       float update[6];
-      wave_solve_step<N>(sums, solve_scratch, update);
-      const float tinc = tinc_element<Step::kSign12>(update, (int)threadIdx.x & 15);
-      if (threadIdx.x < 16) solve_scratch[threadIdx.x] = tinc;
-      wave_lds_fence();
-      const float M_lane = matmul4_lane(solve_scratch, S.base, (int)threadIdx.x);     // Tinc * base
-      wave_lds_fence();
+      const float M_lane = wave_pose_step<N, Step::kSign12>(sums, S.base, solve_scratch, update);
       const float next = S.advance(wave_rigid_from(M_lane, solve_scratch), solve_scratch);
       float sq = 0.0f;
 #pragma unroll
@@ -1004,7 +943,7 @@ void launch_publish_pose(const Mirror& mirror, const vk_transform* pose, hipStre
 
 // The loop with a `reduce` hook (a multi-GPU rig: the packed system is summed over the ranks
 // before every rank solves it), launch per stage: per step the partials (`partials(s)`), their
-// sums into system[0, 48), reduce(system), the one-lane solve and pose update (`solve(s)`). Then
+// sums into system[0, 48), reduce(system), the solve and pose update (`solve(s)`, one wave). Then
 // the pose goes to the caller's pinned memory if it asked for it.
 template <typename Partials, typename Solve>
 int staged_loop(int iterations, int translation_enabled, int partials, float* workspace, float* system,

@@ -306,35 +306,27 @@ __global__ __launch_bounds__(256) void system_final_kernel(const float* __restri
 
 // ---- pose update on the device ------------------------------------------------
 
-// ref: tracker.cpp:124-163 + depth_tracker.cpp:22-86. One lane; 6x6 is too
-// small to spread.
+// ref: tracker.cpp:124-163 + depth_tracker.cpp:22-86. One wave solves and makes M = Tinc(update) * old
+// pose matrix (staged_pose_step); lane 0 re-orthonormalises it and writes pose, state and update.
 template <int N>
-__device__ __forceinline__ void solve_update_n(const float* hessian, const float* gradient,
+__device__ __forceinline__ void solve_update(const float* hessian, const float* gradient,
     vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
 {
-  float update[6], old_m[16], M[16], out_m[16], out_i[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) old_m[i] = Twc->m[i];
-  pose_matrix<N, +1>(hessian, gradient, old_m, M, update);     // M = Tinc(update) * old pose matrix
+  float update[6], M[16], out_m[16], out_i[16];
+  staged_pose_step<N, +1>(hessian, gradient, Twc->m, M, update);
+  if (threadIdx.x != 0) return;
   rigid_from(M, out_m, out_i);
 #pragma unroll
   for (int i = 0; i < 16; ++i) { Twc->m[i] = out_m[i]; Twc->inv[i] = out_i[i]; }
   finish_step<N>(update, state, update_out, mirror);
 }
 
-__device__ void solve_update(const float* hessian, const float* gradient,
+__global__ __launch_bounds__(64) void solve_update_kernel(const float* __restrict__ hessian, const float* __restrict__ gradient,
     int translation_enabled, vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
 {
-  if (state && state[1]) return;  // converged earlier: tracker.cpp:162
-  if (translation_enabled) solve_update_n<6>(hessian, gradient, Twc, state, update_out, mirror);
-  else solve_update_n<3>(hessian, gradient, Twc, state, update_out, mirror);
-}
-
-__global__ void solve_update_kernel(const float* __restrict__ hessian, const float* __restrict__ gradient,
-    int translation_enabled, vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
-{
-  if (threadIdx.x == 0 && blockIdx.x == 0)
-    solve_update(hessian, gradient, translation_enabled, Twc, state, update_out, mirror);
+  if (state && state[1]) return;  // converged earlier: tracker.cpp:162 (the same answer in every lane)
+  if (translation_enabled) solve_update<6>(hessian, gradient, Twc, state, update_out, mirror);
+  else solve_update<3>(hessian, gradient, Twc, state, update_out, mirror);
 }
 
 // ---- the whole Gauss-Newton loop in one launch (gauss_newton_loop, vk_gauss_newton.hpp) ----
@@ -457,6 +449,27 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
 
 // ------------------------------------------------------------------ pyramid ----
 
+// Image::Downsample / ColorImage::Downsample (image.cu:101-165) of an image of CHANNELS interleaved floats
+// per pixel. A destination pixel (dst_x, dst_y) is made of the 2x2 source pixels from (src_x, src_y) =
+// (2 dst_x, 2 dst_y): the nearest pick copies the first of them, the pixel nearest_source(); the box
+// averages the four, channel by channel
+__device__ __forceinline__ int nearest_source(int src_w, int src_x, int src_y)
+{
+  return src_y * src_w + src_x;
+}
+
+template <int CHANNELS>
+__device__ __forceinline__ float box_2x2(const float* src, int src_w, int src_x, int src_y, int c)
+{
+  float sample = 0;
+  sample += src[CHANNELS * ((src_y + 0) * src_w + (src_x + 1)) + c];
+  sample += src[CHANNELS * ((src_y + 0) * src_w + (src_x + 0)) + c];
+  sample += src[CHANNELS * ((src_y + 1) * src_w + (src_x + 1)) + c];
+  sample += src[CHANNELS * ((src_y + 1) * src_w + (src_x + 0)) + c];
+  sample *= 0.25f;
+  return sample;
+}
+
 // ref: image.cu:101-131
 __global__ __launch_bounds__(256) void downsample_kernel(int src_w, int dst_w, int dst_h,
     const float* __restrict__ src, float* __restrict__ dst, int nearest)
@@ -467,20 +480,8 @@ __global__ __launch_bounds__(256) void downsample_kernel(int src_w, int dst_w, i
 
   const int src_x = 2 * dst_x, src_y = 2 * dst_y;
   float sample = 0;
-
-  if (nearest)
-  {
-    sample = src[src_y * src_w + src_x];
-  }
-  else
-  {
-    sample += src[(src_y + 0) * src_w + (src_x + 1)];
-    sample += src[(src_y + 0) * src_w + (src_x + 0)];
-    sample += src[(src_y + 1) * src_w + (src_x + 1)];
-    sample += src[(src_y + 1) * src_w + (src_x + 0)];
-    sample *= 0.25f;
-  }
-
+  if (nearest) sample = src[nearest_source(src_w, src_x, src_y)];
+  else sample = box_2x2<1>(src, src_w, src_x, src_y, 0);
   dst[dst_y * dst_w + dst_x] = sample;
 }
 
@@ -498,24 +499,14 @@ __global__ __launch_bounds__(256) void downsample3_kernel(int src_w, int dst_w, 
   for (int c = 0; c < 3; ++c)
   {
     float sample = 0;
-    if (nearest)
-    {
-      sample = src[3 * (src_y * src_w + src_x) + c];
-    }
-    else
-    {
-      sample += src[3 * ((src_y + 0) * src_w + (src_x + 1)) + c];
-      sample += src[3 * ((src_y + 0) * src_w + (src_x + 0)) + c];
-      sample += src[3 * ((src_y + 1) * src_w + (src_x + 1)) + c];
-      sample += src[3 * ((src_y + 1) * src_w + (src_x + 0)) + c];
-      sample *= 0.25f;
-    }
+    if (nearest) sample = src[3 * nearest_source(src_w, src_x, src_y) + c];
+    else sample = box_2x2<3>(src, src_w, src_x, src_y, c);
     dst[3 * (dst_y * dst_w + dst_x) + c] = sample;
   }
 }
 
 // Frame::Downsample (frame.cpp:38-51) as one launch: blockIdx.z = 0 depth (nearest), 1 colour
-// (2x2 box), 2 normals (nearest); the same expressions as downsample_kernel / downsample3_kernel
+// (2x2 box), 2 normals (nearest, one 12-byte copy)
 struct FrameLevel
 {
   const float* src[3];
@@ -535,26 +526,17 @@ __global__ __launch_bounds__(256) void frame_downsample_kernel(FrameLevel L)
   float* dst = L.dst[job];
   if (job == 0)
   {
-    dst[dst_y * L.dst_w[job] + dst_x] = src[src_y * src_w + src_x];
+    dst[dst_y * L.dst_w[job] + dst_x] = src[nearest_source(src_w, src_x, src_y)];
   }
   else if (job == 2)
   {
-    const vf3 n = *reinterpret_cast<const vf3*>(src + 3 * (src_y * src_w + src_x));
+    const vf3 n = *reinterpret_cast<const vf3*>(src + 3 * nearest_source(src_w, src_x, src_y));
     *reinterpret_cast<vf3*>(dst + 3 * (dst_y * L.dst_w[job] + dst_x)) = n;
   }
   else
   {
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-    {
-      float sample = 0;
-      sample += src[3 * ((src_y + 0) * src_w + (src_x + 1)) + c];
-      sample += src[3 * ((src_y + 0) * src_w + (src_x + 0)) + c];
-      sample += src[3 * ((src_y + 1) * src_w + (src_x + 1)) + c];
-      sample += src[3 * ((src_y + 1) * src_w + (src_x + 0)) + c];
-      sample *= 0.25f;
-      dst[3 * (dst_y * L.dst_w[job] + dst_x) + c] = sample;
-    }
+    for (int c = 0; c < 3; ++c) dst[3 * (dst_y * L.dst_w[job] + dst_x) + c] = box_2x2<3>(src, src_w, src_x, src_y, c);
   }
 }
 
@@ -583,21 +565,11 @@ struct LevelParams
   vk_transform pose_start;
 };
 
-__device__ __forceinline__ float level_depth_at(const float* depths, int w, int h, int x, int y)
+// the normal of pixel (x, y) of a side's full-resolution depth image
+__device__ __forceinline__ f3 side_normal(const LevelParams& L, int side, int x, int y)
 {
-  return (x >= 0 && x < w && y >= 0 && y < h) ? depths[y * w + x] : 0.0f;
-}
-
-// the normal of pixel (x, y) of a full-resolution depth image: compute_normals_kernel's expressions (vk_trace.hip)
-__device__ __forceinline__ f3 level_normal(const float* depths, const vk_projection& k, int w, int h, int x, int y)
-{
-  const int pad = 2;
-  const float depth = depths[y * w + x];
-  f3 normal = make3(0, 0, 0);
-  if (depth > 0)
-    normal = normal_from_taps(k, x, y, depth, level_depth_at(depths, w, h, x - pad, y), level_depth_at(depths, w, h, x + pad, y),
-        level_depth_at(depths, w, h, x, y - pad), level_depth_at(depths, w, h, x, y + pad));
-  return normal;
+  const float* depths = L.src_depth[side];
+  return pixel_normal(L.k[side], plain_depths{depths}, L.src_w[side], L.src_h[side], x, y, depths[y * L.src_w[side] + x]);
 }
 
 __global__ __launch_bounds__(256) void pyramid_level_kernel(LevelParams L)
@@ -614,7 +586,7 @@ __global__ __launch_bounds__(256) void pyramid_level_kernel(LevelParams L)
     // a side's own normal image, every pixel
     const int side = L.due_side[blockIdx.z - 2];
     if (x >= L.src_w[side] || y >= L.src_h[side]) return;
-    const f3 n = level_normal(L.src_depth[side], L.k[side], L.src_w[side], L.src_h[side], x, y);
+    const f3 n = side_normal(L, side, x, y);
     float* out = L.normals_out[side] + 3 * ((size_t)y * L.src_w[side] + x);
     out[0] = n.x;  out[1] = n.y;  out[2] = n.z;
     return;
@@ -622,13 +594,15 @@ __global__ __launch_bounds__(256) void pyramid_level_kernel(LevelParams L)
   const int side = blockIdx.z;
   const int dst_x = x, dst_y = y;
   if (dst_x >= L.dst_w[side] || dst_y >= L.dst_h[side]) return;
+  // nearest_source(), written out: through the function one shift is scheduled earlier, and this kernel's
+  // code is held to the instruction
   const int src = (2 * dst_y) * L.src_w[side] + 2 * dst_x;
   const int dst = dst_y * L.dst_w[side] + dst_x;
   L.dst_depth[side][dst] = L.src_depth[side][src];
   vf3 n;
   if (L.normals_out[side])
   {
-    const f3 computed = level_normal(L.src_depth[side], L.k[side], L.src_w[side], L.src_h[side], 2 * dst_x, 2 * dst_y);
+    const f3 computed = side_normal(L, side, 2 * dst_x, 2 * dst_y);
     n = vf3{computed.x, computed.y, computed.z};
   }
   else n = *reinterpret_cast<const vf3*>(L.src_normals[side] + 3 * src);

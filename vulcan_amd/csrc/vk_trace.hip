@@ -326,11 +326,6 @@ __global__ __launch_bounds__(kPointsWaves * 64) void compute_points_kernel(Point
 // groups are then dispatched late and find most rows complete. Dispatched right behind the raycast's workgroups they wait
 // from the first microsecond on, and the launch lasted 46.3 us instead of 29 + 5 (sphere) and 84.4 instead of 69.7 + 5
 // (tracking scene): vk_trace_ahead keeps its two launches.
-__device__ __forceinline__ float depth_through(const float* depths, int w, int h, int x, int y)
-{
-  return (x >= 0 && x < w && y >= 0 && y < h) ? __hip_atomic_load(&depths[y * w + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-}
-
 // The wait is bounded, and its expiry has an OUTCOME (round 5): the group stores nothing — normals from depths that are
 // not all there would be wrong without anyone knowing — and says so in the word behind the counters and in the caller's
 // pinned word; the host side repairs and reports it (vk_trace_normals_settle, and the check at the start of trace_ahead).
@@ -361,13 +356,10 @@ __device__ __forceinline__ void normals_group(const PointParams& P, float* __res
   const int x = group_x * 64 + (threadIdx.x & 63);
   const int y = group_y * 4 + (threadIdx.x >> 6);
   if (x >= P.image_width || y >= P.image_height) return;
-  const int pad = 2;
-  const float depth = depth_through(P.depths, P.image_width, P.image_height, x, y);
-  f3 normal = make3(0, 0, 0);
-  if (depth > 0)
-    normal = normal_from_taps(P.k, x, y, depth,
-        depth_through(P.depths, P.image_width, P.image_height, x - pad, y), depth_through(P.depths, P.image_width, P.image_height, x + pad, y),
-        depth_through(P.depths, P.image_width, P.image_height, x, y - pad), depth_through(P.depths, P.image_width, P.image_height, x, y + pad));
+  // the depths where the raycast's waves wrote them through to
+  const auto written = [depths = P.depths](int i) { return __hip_atomic_load(&depths[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  const f3 normal = pixel_normal(P.k, written, P.image_width, P.image_height, x, y,
+      depth_or_zero(written, P.image_width, P.image_height, x, y));
   const int output = y * P.image_width + x;
   normals[3 * output + 0] = normal.x;
   normals[3 * output + 1] = normal.y;
@@ -406,11 +398,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VK_TR_WAVES
 
 // ------------------------------------------------------------------ normals ----
 
-__device__ __forceinline__ float depth_at(const float* depths, int w, int h, int x, int y)
-{
-  return (x >= 0 && x < w && y >= 0 && y < h) ? depths[y * w + x] : 0.0f;
-}
-
 // ref: frame.cu:9-122. The +-2 px taps are read through L1/L2 (each depth value
 // is used by 5 pixels of neighbouring rows/columns) instead of a 20x20 LDS tile.
 __global__ __launch_bounds__(256) void compute_normals_kernel(const float* __restrict__ depths,
@@ -420,13 +407,7 @@ __global__ __launch_bounds__(256) void compute_normals_kernel(const float* __res
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= image_width || y >= image_height) return;
 
-  const int pad = 2;
-  const float depth = depths[y * image_width + x];
-  f3 normal = make3(0, 0, 0);
-  if (depth > 0)
-    normal = normal_from_taps(k, x, y, depth,
-        depth_at(depths, image_width, image_height, x - pad, y), depth_at(depths, image_width, image_height, x + pad, y),
-        depth_at(depths, image_width, image_height, x, y - pad), depth_at(depths, image_width, image_height, x, y + pad));
+  const f3 normal = pixel_normal(k, plain_depths{depths}, image_width, image_height, x, y, depths[y * image_width + x]);
 
   const int output = y * image_width + x;
   normals[3 * output + 0] = normal.x;
@@ -451,7 +432,7 @@ __global__ __launch_bounds__(256) void filter_depths_kernel(int image_width, int
   for (int i = -pad; i <= pad; ++i)
     for (int j = -pad; j <= pad; ++j)
     {
-      const float dk = depth_at(src, image_width, image_height, x + j, y + i);
+      const float dk = depth_or_zero(plain_depths{src}, image_width, image_height, x + j, y + i);
       const float delta = d0 - dk;
       float sq = 0;
       sq += (float)i * (float)i;
