@@ -1175,6 +1175,50 @@ VK_API int vk_extract_mesh(const vk_volume* v, int all_allocated, int interpolat
     int32_t point_capacity, int32_t* faces, int32_t face_capacity, int32_t* counts_dev,
     void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ release -- */
+
+enum { VK_RELEASE_UNOBSERVED = 1, VK_RELEASE_NO_SURFACE = 2, VK_RELEASE_OUTSIDE_BOX = 4 };
+
+typedef struct vk_release_rule {
+  int32_t flags;              /* VK_RELEASE_* or'ed; 0: release nothing, repair only */
+  float   min_abs_distance;   /* NO_SURFACE: in units of the stored, normalised distance (-1, 1] */
+  int16_t keep_lo[3];         /* OUTSIDE_BOX: block coordinates, inclusive */
+  int16_t keep_hi[3];
+} vk_release_rule;
+
+/* Give voxel blocks back to the pool, compact the hash table and rebuild the free list — in one call, nothing read
+ * back, the result independent of timing. No upstream counterpart: ref: src/volume.cu:304-368 (HandleAllocationRequests)
+ * pops pool slots and bumps the excess pointer and never returns a slot, unlinks an entry or lowers the pointer; once
+ * the excess list is full it leaks one pool slot per refused request (:337-356) and, once the pool is empty, links
+ * excess entries it never writes ("ghosts", :344). The definition is this comment; tests/release_reference.py states it
+ * on the CPU and the device is held to it bit for bit.
+ * PRECONDITION (the caller's duty here; the class layers enforce it): the volume is between SetView calls —
+ * allocation_types all NONE, no frame announced (vk_requests_ahead) and its SetView outstanding.
+ * Released: a block (an entry with data >= 0 that is reachable from a main bucket along `next`) for which an enabled
+ * rule holds — UNOBSERVED: all 512 voxels have distance_weight == 0; NO_SURFACE: a voxel has distance_weight != 0 and
+ * no such voxel has fabsf(distance) < min_abs_distance; OUTSIDE_BOX: origin[a] < keep_lo[a] or origin[a] > keep_hi[a]
+ * for some a. Only stored values are compared, nothing is computed.
+ * Afterwards: (chains) for every main bucket b, ascending, the entries of its chain — entry b included — that hold a
+ * block which stays, in chain order: the first at entry b, the others at consecutive excess entries starting at
+ * main + sum over b' < b of max(survivors(b') - 1, 0), linked in that order, the last `next` -1; every other entry is
+ * HashEntry() (origin 0, pad 0, data -1, next -1); VK_CTR_EXCESS_PTR = main + survivors in excess entries.
+ * (visibility) a survivor's block_visibility byte moves with it, every other byte is VK_VISIBILITY_FALSE,
+ * VK_CTR_VISIBLE = 0, VK_CTR_BANDED = -1: the caller's next SetView rebuilds the visible list. (pool)
+ * free_voxel_blocks[k] = the k-th pool slot, ascending, that no survivor references, -1 behind them, VK_CTR_VOXEL_PTR =
+ * their number - 1 — slots upstream's allocator leaked come back; on a fresh volume this is Initialize's list.
+ * (voxels) the 512 voxels of every released block are Voxel::Empty() (distance 1, colour 0, weights 0: what the
+ * allocator assumes of a fresh slot); no other voxel byte changes. counts_dev: device int32[4] = {blocks released,
+ * blocks kept, excess entries in use, free slots}. VK_CTR_DROPPED and the other public counters are untouched.
+ * With flags == 0 the call is a pure repair: it removes ghosts, makes the excess entries dense and rebuilds the free
+ * list. Anything prepared ahead for the volume is VOID after the call and must be invalidated by the caller: the
+ * vk_view_bounds records (valid = 0), a vk_light_prep (valid = 0), and no vk_requests_ahead record may be valid.
+ * v->voxels 16-byte aligned. workspace: device, vk_volume_release_workspace_bytes(main, excess) bytes (0 for sizes that
+ * are not a volume's). Thirteen short launches on `stream` (the two ordered scans are vk_compact_offsets'); only released blocks' voxels are written
+ * and only allocated blocks' voxels are read (none when OUTSIDE_BOX is the only rule). */
+VK_API size_t vk_volume_release_workspace_bytes(int32_t main_block_count, int32_t excess_block_count);
+VK_API int vk_volume_release_blocks(const vk_volume* v, const vk_release_rule* rule,
+    int32_t* counts_dev /* [4] */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

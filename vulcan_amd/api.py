@@ -114,6 +114,8 @@ _SIGNATURES = {
     "vk_compact_offsets": ([_P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_extract_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_extract_mesh": ([_P, _I, _I, _P, C.c_int32, _P, C.c_int32, _P, _P, _P], _I),
+    "vk_volume_release_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
+    "vk_volume_release_blocks": ([_P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -465,6 +467,40 @@ class Volume:
         self._view_changed()
         check(lib().vk_requests_ahead_cancel(_ref(self.desc()), _ref(self.requests_ahead), int(rounds), stream()),
               "vk_requests_ahead_cancel")
+
+    _release_workspace = None   # device bytes of vk_volume_release_blocks, allocated by the first release_blocks
+    _release_counts = None
+
+    def release_blocks(self, unobserved=False, min_abs_distance=None, keep_box=None):
+        """vk_volume_release_blocks (not upstream): give back the blocks a rule names — `unobserved`: no voxel was ever
+        integrated; `min_abs_distance`: observed, but no observed voxel's stored distance (normalised to (-1, 1]) is
+        nearer the surface than this; `keep_box` = ((lo x, y, z), (hi x, y, z)) in block coordinates, inclusive: the
+        block's origin lies outside — then compact the hash table and rebuild the free list. With no rule: the repair
+        alone (ghost entries and leaked slots of an exhausted pool come back). Between SetView calls only: raises while
+        a frame is announced. The visible list is empty afterwards (the next set_view rebuilds it) and what was
+        prepared ahead for the volume is void. Returns (blocks released, blocks kept, excess entries in use, free
+        slots) from one blocking read."""
+        import torch
+        self._no_requests_pending("release_blocks")
+        rule = T.ReleaseRule()
+        if unobserved:
+            rule.flags |= T.VK_RELEASE_UNOBSERVED
+        if min_abs_distance is not None:
+            rule.flags |= T.VK_RELEASE_NO_SURFACE
+            rule.min_abs_distance = float(min_abs_distance)
+        if keep_box is not None:
+            rule.flags |= T.VK_RELEASE_OUTSIDE_BOX
+            rule.keep_lo[:] = [int(c) for c in keep_box[0]]
+            rule.keep_hi[:] = [int(c) for c in keep_box[1]]
+        if self._release_workspace is None:
+            self._release_workspace = _dev_bytes(lib().vk_volume_release_workspace_bytes(self.main, self.excess), self.device)
+            self._release_counts = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self._view_changed()
+        if self.light_prep is not None:
+            self.light_prep.valid = 0
+        check(lib().vk_volume_release_blocks(_ref(self.desc()), _ref(rule), _ptr(self._release_counts),
+                                             _ptr(self._release_workspace), stream()), "vk_volume_release_blocks")
+        return tuple(int(c) for c in self._release_counts.cpu().numpy())
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

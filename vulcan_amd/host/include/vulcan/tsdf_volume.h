@@ -36,6 +36,26 @@ enum AllocationType : uint8_t
   ALLOC_TYPE_EXCESS = 2,
 };
 
+// Not upstream: which blocks Volume::ReleaseBlocks gives back (vk_release_rule). A default-constructed rule releases
+// nothing: the call is then the repair alone.
+struct ReleaseRule
+{
+  bool unobserved = false;            // no voxel of the block was ever integrated
+  bool no_surface = false;            // observed, but no observed voxel's stored distance is below min_abs_distance
+  float min_abs_distance = 0.0f;      //   (stored distances are normalised to (-1, 1])
+  bool outside_box = false;           // the block's origin lies outside [keep_lo, keep_hi], block coordinates, inclusive
+  int16_t keep_lo[3] = {0, 0, 0};
+  int16_t keep_hi[3] = {0, 0, 0};
+};
+
+struct ReleaseCounts
+{
+  int released;         // blocks given back by this call
+  int kept;             // blocks in the volume afterwards
+  int excess_entries;   // excess hash entries in use afterwards
+  int free_slots;       // pool slots free afterwards
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -86,6 +106,14 @@ class Volume
     // frame.depth_to_world_transform is ignored. false: not possible in this state (a frame announced by Tracer::Trace, a
     // request stream, the three-launch test form) — nothing was launched, the caller calls SetView once it has the pose.
     bool SetViewAtDevicePose(const Frame& frame, const vk_transform* pose_device, int rounds = 1);
+
+    // Not upstream (src/volume.cu:304-368 never returns a slot): give the blocks `rule` names back to the pool, compact
+    // the hash table and rebuild the free list (vk_volume_release_blocks) — also the way back from an exhausted pool,
+    // whose leaked slots and never-written excess entries it recovers even with an empty rule. Between SetView calls
+    // only: throws while a frame announced by Tracer::Trace(keyframe, next_frame) is outstanding. The visible list is
+    // empty afterwards (the next SetView rebuilds it); the raycast bounds and the light preparation made ahead are void.
+    // One blocking readback (the four counts).
+    ReleaseCounts ReleaseBlocks(const ReleaseRule& rule);
 
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
@@ -142,6 +170,8 @@ class Volume
     Buffer<Visibility> block_visibility_;
     mutable Buffer<int> visible_blocks_;
     Buffer<int> counters_;
+    Buffer<unsigned char> release_workspace_;   // ReleaseBlocks: allocated by the first call
+    Buffer<int> release_counts_;
 
     Vector2f depth_range_;
     int max_block_count_;

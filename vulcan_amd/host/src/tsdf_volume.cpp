@@ -320,6 +320,41 @@ int Volume::GetAllocatedBlockCount() const
   return taken < max_block_count_ ? taken : max_block_count_;
 }
 
+ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
+{
+  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+  vk_release_rule r;
+  std::memset(&r, 0, sizeof(r));
+  r.flags = (rule.unobserved ? VK_RELEASE_UNOBSERVED : 0) | (rule.no_surface ? VK_RELEASE_NO_SURFACE : 0) |
+            (rule.outside_box ? VK_RELEASE_OUTSIDE_BOX : 0);
+  r.min_abs_distance = rule.min_abs_distance;
+  for (int a = 0; a < 3; ++a)
+  {
+    r.keep_lo[a] = rule.keep_lo[a];
+    r.keep_hi[a] = rule.keep_hi[a];
+  }
+  if (release_counts_.GetSize() == 0)
+  {
+    release_workspace_.Resize(vk_volume_release_workspace_bytes(main_block_count_, excess_block_count_));
+    release_counts_.Resize(4);
+  }
+  // what was made ahead for the old table and visible list is void
+  view_bounds_.valid = 0;
+  light_prep_.valid = 0;
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_release_blocks(&v, &r, release_counts_.GetData(), release_workspace_.GetData(), Device::GetStream()));
+  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
+  visible_count_stale_ = false;
+  int32_t counts[4];
+  release_counts_.CopyToHost(counts);
+  ReleaseCounts out;
+  out.released = counts[0];
+  out.kept = counts[1];
+  out.excess_entries = counts[2];
+  out.free_slots = counts[3];
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");

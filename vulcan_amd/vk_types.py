@@ -23,6 +23,7 @@ VK_ERR_UNSUPPORTED = -2                  # include/vk.h vk_status
 VISIBILITY_UNKNOWN, VISIBILITY_FALSE, VISIBILITY_TRUE = 0, 1, 2
 ALLOC_NONE, ALLOC_MAIN, ALLOC_EXCESS = 0, 1, 2
 BLOCK_RESOLUTION, BLOCK_VOXELS, PATCH_MAX_SIZE = 8, 512, 16
+VK_RELEASE_UNOBSERVED, VK_RELEASE_NO_SURFACE, VK_RELEASE_OUTSIDE_BOX = 1, 2, 4   # vk_release_rule.flags
 
 voxel_dtype = np.dtype([("distance", "<f4"), ("color", "<f4", (3,)),
                         ("distance_weight", "<i2"), ("color_weight", "<i2")])
@@ -196,6 +197,11 @@ class RequestsAhead(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("depth", C.c_void_p), ("prep", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("depth_projection", Projection), ("depth_to_world", Transform), ("content_id", C.c_uint64),
                 ("valid", C.c_int32), ("normals_made", C.c_int32), ("pose_on_device", C.c_int32), ("pad_", C.c_int32)]
+
+
+class ReleaseRule(C.Structure):
+    """vk_release_rule (vk.h): which blocks vk_volume_release_blocks gives back; flags 0 = repair only"""
+    _fields_ = [("flags", C.c_int32), ("min_abs_distance", C.c_float), ("keep_lo", C.c_int16 * 3), ("keep_hi", C.c_int16 * 3)]
 
 
 class PyramidAhead(C.Structure):
