@@ -481,6 +481,8 @@ __global__ __launch_bounds__(kPipeWavesPerGroup * 64) VK_INTEGRATE_WAVES void in
   __shared__ __attribute__((aligned(16))) int pool[kPoolInts];
   __shared__ __attribute__((aligned(8))) uint8_t changed_bytes[kPipeWavesPerGroup][kChangedBytes];
   __shared__ double reciprocal[kReciprocals];
+  // four workgroups per CU share its 160 KiB: one more word here would cost a quarter of the occupancy without a sound
+  static_assert(sizeof(pool) + sizeof(changed_bytes) + sizeof(reciprocal) <= 160 * 1024 / 4, "LDS of the integrate launch at four workgroups per CU");
 
   int group = (int)blockIdx.x, groups = (int)gridDim.x;
   if (AHEAD)

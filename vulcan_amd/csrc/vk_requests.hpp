@@ -1,7 +1,8 @@
 // vk_requests.hpp — the request pass of Volume::SetView (ref: src/volume.cu:87-301 CreateAllocationRequestsKernel,
 // :497-518): device code shared by vk_volume.hip (the pass as a launch of its own, and the later rounds, which probe the
 // same way) and vk_trace.hip (the pass of the NEXT frame as trailing workgroups of a raycast launch,
-// vk_trace_ahead_requests). Moved out of vk_volume.hip in round 4, unchanged.
+// vk_trace_ahead_requests). Every form of the pass takes requests_group, whose walk collects the crossed blocks per wave
+// and probes them at one site (request_walk).
 #pragma once
 
 #include "vk_common.hpp"
@@ -222,9 +223,13 @@ __device__ __forceinline__ int left_lane(int v)
   return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false);
 }
 
-#ifndef VK_REQUEST_PROBES
-#define VK_REQUEST_PROBES 6
-#endif
+// The visits a wave's rays make, before they are probed (request_walk): per wave kVisitSlots block coordinates in LDS, one
+// 4-byte array per axis (the hash needs all 32 bits of a coordinate; only entry_is and request_key truncate to int16).
+// 96 slots: a step of the walk adds at most 64 visits, the list is emptied when the next step's might not fit, i.e. never
+// below 33 entries — and four waves' lists fit in the row_min / row_max area of the PREP forms (requests_group).
+constexpr int kVisitSlots = 96;
+constexpr int kVisitWords = 3 * kVisitSlots;                // per wave
+constexpr int kVisitWalkCap = 6 + 4096;                     // blocks a ray visits at most: ends a walk on NaN / degenerate input
 
 struct RequestParams
 {
@@ -246,8 +251,17 @@ struct RequestParams
 // ref: volume.cu:87-301, the walk of one depth pixel (x, y). Called by WHOLE waves whose 64
 // lanes hold 64 consecutive pixels of one row (lanes past the image stay in: their neighbours
 // read their registers), so that the depth read is one coalesced 256-byte load.
+//
+// The walk never depends on what the hash table holds, so it only COLLECTS the blocks the wave's rays cross, in `visits`
+// (this wave's kVisitWords words of LDS), and the collected blocks are probed 64 at a time, one per lane, at ONE site:
+// hash, % K, the entry with its visibility byte, probe_block. Neighbouring pixels of a row cross the same blocks (a block
+// is ~11 px wide at 2 m), and everything a probe does - marking the entry visible, posting the max-key request, the posted
+// list, the retry set - is idempotent: a lane whose left neighbour visits the identical block in the same step of the walk
+// leaves the visit to it, and what remains is about one probe per distinct block per wave instead of one per ray, made in
+// full waves. The same visit collected twice (two steps, two batches, two waves) is probed twice, harmlessly. A list
+// that the next step might overfill is probed and restarted: no visit is dropped, however long the walk.
 template <int MARK>
-__device__ __forceinline__ void request_walk(const RequestParams& P, int x, int y, const Retry& retry)
+__device__ __forceinline__ void request_walk(const RequestParams& P, int x, int y, const Retry& retry, int* visits)
 {
   const vk_volume& v = P.v;
   const uint32_t K = (uint32_t)v.main_block_count;
@@ -297,119 +311,94 @@ __device__ __forceinline__ void request_walk(const RequestParams& P, int x, int 
   const float tdelta_y = (step_y * block_length) / direction.y;
   const float tdelta_z = (step_z * block_length) / direction.z;
 
-  // The walk itself never depends on what the hash table holds, so it is run
-  // first and its probes are issued together: the reference's loop (one dependent
-  // table read per crossed block, :174-299) becomes kProbe independent reads in
-  // flight. A 2*trunc segment crosses 3-4 blocks; walks longer than kProbe fall
-  // back to the step-by-step loop below.
-  constexpr int kProbe = VK_REQUEST_PROBES;
-  int sbx[kProbe], sby[kProbe], sbz[kProbe];
-  uint32_t shash[kProbe];
+  int* const list_x = visits;
+  int* const list_y = visits + kVisitSlots;
+  int* const list_z = visits + 2 * kVisitSlots;
+  const int lane = lane_id();
   bool walking = usable;
+  int listed = 0;                                   // wave-uniform, like everything that steers the loop
 
-  // the three products of the hash (volume.cu:168-180) follow the walk by addition:
-  // a step changes one coordinate by +-1, i.e. its product by +-prime (mod 2^32), which
-  // replaces three quarter-rate 32-bit multiplies per crossed block by one add
-  uint32_t hx = (uint32_t)bx * 73856093u, hy = (uint32_t)by * 19349669u, hz = (uint32_t)bz * 83492791u;
-  const uint32_t dhx = step_x < 0 ? 0u - 73856093u : 73856093u;
-  const uint32_t dhy = step_y < 0 ? 0u - 19349669u : 19349669u;
-  const uint32_t dhz = step_z < 0 ? 0u - 83492791u : 83492791u;
-
-#pragma unroll
-  for (int sidx = 0; sidx < kProbe; ++sidx)
+  for (int step = 0;; ++step)
   {
-    sbx[sidx] = bx; sby[sidx] = by; sbz[sidx] = bz;
-    shash[sidx] = walking ? (hx ^ hy ^ hz) % K : 0xffffffffu;
+    // this step's visits: the lanes still walking, less those whose left neighbour is at the same block
+    const bool left_walking = left_lane((int)walking) != 0;
+    const int left_x = left_lane(bx), left_y = left_lane(by), left_z = left_lane(bz);
+    const bool fresh = walking && !(lane > 0 && left_walking && left_x == bx && left_y == by && left_z == bz);
+    const unsigned long long fresh_mask = __ballot(fresh);
+    const int arriving = __popcll(fresh_mask);
+    const bool last = arriving == 0;                // (the lanes still walking always include a fresh one: the leftmost)
+
+    // ---- the one probe site: when this step's visits might not fit, and at the end
+    if (listed + arriving > kVisitSlots || last)
+    {
+      wave_lds_fence();
+      for (int first = 0; first < listed; first += 64)
+      {
+        const int at = first + lane;
+        if (at < listed)
+        {
+          const int px = list_x[at], py = list_y[at], pz = list_z[at];
+          const uint32_t hash_code = block_hash(px, py, pz, K);
+          // (the visibility byte of the bucket's main entry is asked for with the entry: most blocks are found there, and
+          // marking them visible would otherwise start with a read of its own)
+          const Entry entry = load_entry(v.hash_entries, hash_code);
+          const uint8_t byte = v.block_visibility[hash_code];
+          probe_block<MARK>(v, hash_code, entry, px, py, pz, retry, (int)byte, tag);
+        }
+      }
+      wave_lds_fence();
+      listed = 0;
+    }
+    if (last) break;
+
+    if (fresh)
+    {
+      const int at = listed + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fresh_mask >> 32),
+          __builtin_amdgcn_mbcnt_lo((uint32_t)fresh_mask, 0u));
+      list_x[at] = bx; list_y[at] = by; list_z[at] = bz;
+    }
+    listed += arriving;
 
     if (walking)
     {
       // :242-295 advance to the next block; `walking` drops when the end block is passed
       if (tmax_x < tmax_y)
       {
-        if (tmax_x < tmax_z) { bx += step_x; hx += dhx; if (bx == ex + step_x) walking = false; else tmax_x += tdelta_x; }
-        else                 { bz += step_z; hz += dhz; if (bz == ez + step_z) walking = false; else tmax_z += tdelta_z; }
+        if (tmax_x < tmax_z) { bx += step_x; if (bx == ex + step_x) walking = false; else tmax_x += tdelta_x; }
+        else                 { bz += step_z; if (bz == ez + step_z) walking = false; else tmax_z += tdelta_z; }
       }
       else
       {
-        if (tmax_y < tmax_z) { by += step_y; hy += dhy; if (by == ey + step_y) walking = false; else tmax_y += tdelta_y; }
-        else                 { bz += step_z; hz += dhz; if (bz == ez + step_z) walking = false; else tmax_z += tdelta_z; }
+        if (tmax_y < tmax_z) { by += step_y; if (by == ey + step_y) walking = false; else tmax_y += tdelta_y; }
+        else                 { bz += step_z; if (bz == ez + step_z) walking = false; else tmax_z += tdelta_z; }
       }
-    }
-  }
-
-  // Neighbouring pixels of a row cross the same blocks (a block is ~11 px wide at
-  // 2 m), and everything a probe does — marking the entry visible, posting the
-  // max-key request — is idempotent. A lane therefore skips a probe when the lane
-  // to its left makes the identical one in the same slot; what remains is about
-  // one probe per distinct block per wave instead of one per ray.
-  const int lane = lane_id();
-#pragma unroll
-  for (int sidx = 0; sidx < kProbe; ++sidx)
-  {
-    const uint32_t left_hash = (uint32_t)left_lane((int)shash[sidx]);
-    const int left_x = left_lane(sbx[sidx]), left_y = left_lane(sby[sidx]), left_z = left_lane(sbz[sidx]);
-    const bool same = lane > 0 && left_hash == shash[sidx] && left_x == sbx[sidx] && left_y == sby[sidx] && left_z == sbz[sidx];
-    if (same) shash[sidx] = 0xffffffffu;
-  }
-
-  // (the visibility byte of each bucket's main entry is asked for with the entry: most blocks are
-  // found there, and marking them visible would otherwise start with a read of its own)
-  Entry sent[kProbe];
-  uint8_t sbyte[kProbe];
-#pragma unroll
-  for (int sidx = 0; sidx < kProbe; ++sidx)
-  {
-    const uint32_t at = shash[sidx] == 0xffffffffu ? 0u : shash[sidx];
-    sent[sidx] = load_entry(v.hash_entries, at);
-    sbyte[sidx] = v.block_visibility[at];
-  }
-
-#pragma unroll
-  for (int sidx = 0; sidx < kProbe; ++sidx)
-  {
-    if (shash[sidx] == 0xffffffffu) continue;
-    probe_block<MARK>(v, shash[sidx], sent[sidx], sbx[sidx], sby[sidx], sbz[sidx], retry, (int)sbyte[sidx], tag);
-  }
-
-  // A segment of 2*trunc crosses a bounded number of blocks; the cap only
-  // guarantees that every wave exits on NaN / degenerate input.
-  for (int guard = 0; walking && guard < 4096; ++guard)
-  {
-    const uint32_t hash_code = block_hash(bx, by, bz, K);
-    probe_block<MARK>(v, hash_code, load_entry(v.hash_entries, hash_code), bx, by, bz, retry, -1, tag);
-
-    if (tmax_x < tmax_y)
-    {
-      if (tmax_x < tmax_z)
-      {
-        bx += step_x;
-        if (bx == ex + step_x) break;
-        tmax_x += tdelta_x;
-      }
-      else
-      {
-        bz += step_z;
-        if (bz == ez + step_z) break;
-        tmax_z += tdelta_z;
-      }
-    }
-    else
-    {
-      if (tmax_y < tmax_z)
-      {
-        by += step_y;
-        if (by == ey + step_y) break;
-        tmax_y += tdelta_y;
-      }
-      else
-      {
-        bz += step_z;
-        if (bz == ez + step_z) break;
-        tmax_z += tdelta_z;
-      }
+      // A segment of 2*trunc crosses a bounded number of blocks; the cap only
+      // guarantees that every wave exits on NaN / degenerate input.
+      if (step + 1 >= kVisitWalkCap) walking = false;
     }
   }
 }
+
+// LDS of one workgroup of the pass (requests_group): the depth tile, then row_min / row_max of the mask's window (PREP), and
+// the four waves' visit lists (request_walk). The lists lie over row_min / row_max, which are written only behind the barrier
+// that every wave reaches after its walk; the tile is not shared with them, so that a wave may store its part of the tile
+// while another still walks. PREP == 0 has the lists alone.
+template <int PREP>
+struct RequestLds
+{
+  static constexpr int HALO = (PREP == 2) ? 2 : 1;          // columns / rows in front of the workgroup's pixels
+  static constexpr int TW = 69 + HALO, TH = 9 + HALO, TS = 72;
+  static constexpr int kTileWords = PREP ? TH * TS : 0, kRowWords = PREP ? 2 * 10 * 64 : 0;
+  static constexpr int kListWords = 4 * kVisitWords;
+  static constexpr int kAreaWords = kTileWords + (kRowWords > kListWords ? kRowWords : kListWords);
+  static constexpr int kBytes = 4 * kAreaWords;
+  static_assert(!PREP || kListWords <= kRowWords, "the visit lists lie over row_min / row_max");
+};
+// a CU's 160 KiB among the workgroups that six waves per SIMD make resident: 24 waves, six workgroups of 256 threads
+constexpr int kLdsPerCU = 160 * 1024;
+constexpr int kRequestGroupsPerCU = 6;
+static_assert(kRequestGroupsPerCU * RequestLds<0>::kBytes <= kLdsPerCU && kRequestGroupsPerCU * RequestLds<1>::kBytes <= kLdsPerCU &&
+    kRequestGroupsPerCU * RequestLds<2>::kBytes <= kLdsPerCU, "LDS of the request pass at six workgroups per CU");
 
 // ref: volume.cu:87-301. One lane per depth pixel; the lanes of a wave cover a
 // 64x1 run of a row so the depth read is one coalesced 256-byte load.
@@ -436,10 +425,14 @@ __device__ __forceinline__ void requests_group(const RequestParams P, const Retr
 
   // PREP: the loads of the depth tile and of the pixel's colour and normal are issued first and
   // consumed after the request walk, which hides their latency
-  constexpr int HALO = (PREP == 2) ? 2 : 1;                 // columns / rows in front of the workgroup's pixels
-  constexpr int TW = 69 + HALO, TH = 9 + HALO, TS = 72;
+  using L = RequestLds<PREP>;
+  constexpr int HALO = L::HALO, TW = L::TW, TH = L::TH, TS = L::TS;
   constexpr int LOADS = (TW * TH + 255) / 256;
-  __shared__ float tile[PREP ? TH * TS : 1];
+  __shared__ int area[L::kAreaWords];
+  float* const tile = reinterpret_cast<float*>(area);
+  float* const row_min = reinterpret_cast<float*>(area + L::kTileWords);
+  float* const row_max = row_min + 10 * 64;
+  int* const visits = area + L::kTileWords + (int)(threadIdx.x >> 6) * kVisitWords;
   float staged[LOADS] = {};
   vf3 prep_rgb = {0.0f, 0.0f, 0.0f}, prep_n = {0.0f, 0.0f, 0.0f};
   if (PREP)
@@ -461,7 +454,7 @@ __device__ __forceinline__ void requests_group(const RequestParams P, const Retr
     }
   }
 
-  if (y < P.height) request_walk<DEFER ? MARK_DEFER : MARK_PLAIN>(P, x, y, retry);   // whole wave
+  if (y < P.height) request_walk<DEFER ? MARK_DEFER : MARK_PLAIN>(P, x, y, retry, visits);   // whole wave
 
   if (PREP)
   {
@@ -476,7 +469,6 @@ __device__ __forceinline__ void requests_group(const RequestParams P, const Retr
     // steps: the seven taps of a row once for every (row, centre column) the workgroup needs — 10 rows x 64 columns, 2.5 per
     // thread — then seven of those per pixel: 31 LDS reads and 49 min / max per thread instead of 49 and 98. The same set of
     // values goes through fminf / fmaxf, which do not care about the order.
-    __shared__ float row_min[10 * 64], row_max[10 * 64];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
     {

@@ -237,6 +237,11 @@ constexpr int kNormalLateWords = 16;      // one more line behind the counters: 
 // The raycast's waves above the request pass's in the launch they share (s_setprio, round 5): the launch is as long as its
 // slowest raycast wave, the request pass fills in. 37.75 -> 37.53 us in two alternating pairs of runs (the request pass's waves
 // raised instead: 38.2; a march's waves raised after 8 / 16 / 32 passes through the loop: nothing, either scene).
+// Five waves per SIMD. Since the request pass probes at one site (vk_requests.hpp: 63 VGPRs with the preparation, 96 before)
+// it is the raycast's four-wave form that sets the launch's registers: 88. Six waves (80 VGPRs) were measured and lost:
+// the request pass's scalar values spill into two VGPRs that the register allocator then keeps from the raycast as well,
+// which spills 12 - 20 bytes per lane to scratch memory, and the launch took 33.9 / 34.3 us against 33.5 / 33.6 at five
+// (tools/patches/r07_raycast_request_six_waves.patch, profiles/r07_request_probe_site.txt, docs/rounds/r07.md).
 #ifndef VK_TR_WAVES
 #define VK_TR_WAVES 5
 #endif
@@ -371,8 +376,8 @@ __device__ __forceinline__ void normals_group(const PointParams& P, float* __res
 // request pass's (64 x 4 pixels each, vk_requests.hpp), dispatched as the raycast's waves retire, the last the normals'
 // (`normals`, or nullptr). The raycast is as long as
 // its slowest wave (mean wave life 17 us, launch 31 us) and leaves most of the device idle for its
-// last third; as a launch of its own the request pass (17 us) would start only after that. The two touch disjoint state:
-// the raycast reads the table, the voxels and its bounds; the request pass reads the table and the visibility bytes and
+// last third; as a launch of its own the request pass (12 us; 17 before it probed at one site) would start only after
+// that. The two touch disjoint state: the raycast reads the table, the voxels and its bounds; the request pass reads the table and the visibility bytes and
 // writes visibility bytes, request flags and the light preparation's buffers.
 template <bool POOL32, int PREP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VK_TR_WAVES))) void trace_and_request_kernel(PointParams P,
@@ -380,6 +385,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VK_TR_WAVES
 {
   __shared__ int4 directories[4][kDirWords];
   __shared__ int normals_expired;
+  // (every role's LDS is allocated to every workgroup of the launch)
+  static_assert(kRequestGroupsPerCU * (int)(sizeof(directories) + sizeof(int) + RequestLds<PREP>::kBytes) <= kLdsPerCU,
+      "LDS of the raycast + request launch at six workgroups per CU");
   if ((int)blockIdx.x < trace_groups)
   {
     __builtin_amdgcn_s_setprio(2);
