@@ -1175,6 +1175,29 @@ VK_API int vk_extract_mesh(const vk_volume* v, int all_allocated, int interpolat
     int32_t point_capacity, int32_t* faces, int32_t face_capacity, int32_t* counts_dev,
     void* workspace, void* stream);
 
+/* vk_extract_mesh with a colour and a unit normal per vertex. No upstream counterpart — ref: src/extractor.cu:320-389
+ * (ExtractVertexPointsKernel writes a position per cut edge and nothing else) and include/vulcan/mesh.h:10-22 (Mesh and
+ * DeviceMesh hold points and faces): upstream has neither attribute, so this comment is the definition;
+ * tests/extract_attributes_reference.py states it on the CPU and the device is held to it bit for bit.
+ * points, faces, counts_dev, the capacities, the order and the workspace are vk_extract_mesh's, bit for bit; one launch
+ * follows its four. colors, normals: device float[3 * point_capacity]; either may be NULL and is then skipped (both
+ * NULL: this is vk_extract_mesh). The attributes of vertex i are written iff i < point_capacity.
+ * All arithmetic is fp32, one rounding per operation (no contraction); `/` and sqrtf are IEEE-rounded.
+ * Vertex i lies on the owned edge `axis` of cube (x, y, z) of a listed block: from lattice point a = (x, y, z) to
+ * b = a + e_axis, at t = d(a) / (d(a) - d(b)) when `interpolate`, else 0.5f — the point's own t. A lattice point q
+ * (-1 ... 9 per axis, so in one of up to 26 neighbouring blocks, each found by the chain walk of volume.cu:183-190) is
+ * KNOWN iff its block is allocated and its voxel's distance_weight != 0 (extractor.cu:202-205).
+ * Colour: ca, cb the stored color[3] of a and b, wa, wb their color_weight. Both != 0: c = ca + t * (cb - ca) per
+ * channel (sub, mul, add); only one != 0: that voxel's colour; neither: (0, 0, 0).
+ * Gradient at a lattice point p (a or b: always known), component k: p + e_k and p - e_k both known:
+ * (d(p + e_k) - d(p - e_k)) * 0.5f; only p + e_k known: d(p + e_k) - d(p); only p - e_k known: d(p) - d(p - e_k);
+ * neither: 0.0f. Normal: g = ga + t * (gb - ga) per component; n2 = (g.x * g.x + g.y * g.y) + g.z * g.z; n2 > 0:
+ * n = g / sqrtf(n2) (three divisions), else (0, 0, 0). It points to the positive-distance side, the side the faces
+ * look to. Every vertex is written by its owner cube alone: no atomics, the output does not depend on timing. */
+VK_API int vk_extract_mesh_attributes(const vk_volume* v, int all_allocated, int interpolate,
+    float* points, float* colors, float* normals, int32_t point_capacity,
+    int32_t* faces, int32_t face_capacity, int32_t* counts_dev, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ release -- */
 
 enum { VK_RELEASE_UNOBSERVED = 1, VK_RELEASE_NO_SURFACE = 2, VK_RELEASE_OUTSIDE_BOX = 4 };

@@ -114,6 +114,7 @@ _SIGNATURES = {
     "vk_compact_offsets": ([_P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_extract_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_extract_mesh": ([_P, _I, _I, _P, C.c_int32, _P, C.c_int32, _P, _P, _P], _I),
+    "vk_extract_mesh_attributes": ([_P, _I, _I, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P], _I),
     "vk_volume_release_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_volume_release_blocks": ([_P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
@@ -1253,17 +1254,23 @@ class PyramidTracker:
 
 
 class Mesh:
-    """vulcan::DeviceMesh (mesh.h:16-21): points [n, 3] float32, faces [m, 3] int32 on the device."""
+    """vulcan::DeviceMesh (mesh.h:16-21): points [n, 3] float32, faces [m, 3] int32 on the device; colors and normals
+    [n, 3] float32 when the extractor was asked for them (vk_extract_mesh_attributes), else None."""
 
-    def __init__(self, points, faces):
-        self.points, self.faces = points, faces
+    def __init__(self, points, faces, colors=None, normals=None):
+        self.points, self.faces, self.colors, self.normals = points, faces, colors, normals
 
     def host(self):
         return self.points.cpu().numpy(), self.faces.cpu().numpy()
 
+    def host_attributes(self):
+        """(colors, normals) as numpy arrays, None for what was not extracted"""
+        return (None if self.colors is None else self.colors.cpu().numpy(),
+                None if self.normals is None else self.normals.cpu().numpy())
+
 
 class Extractor:
-    """vulcan::Extractor (extractor.h:116-134): the whole volume in four launches."""
+    """vulcan::Extractor (extractor.h:116-134): the whole volume in four launches, five with attributes."""
 
     def __init__(self, volume):
         import torch
@@ -1274,10 +1281,11 @@ class Extractor:
         self.workspace = torch.empty(n, dtype=torch.uint8, device=volume.device)
         self.counts = torch.zeros(4, dtype=torch.int32, device=volume.device)
 
-    def extract(self, point_capacity=None, face_capacity=None):
+    def extract(self, point_capacity=None, face_capacity=None, colors=False, normals=False):
         """Extractor::Extract(DeviceMesh&). Capacities default to upstream's ResizeMesh bound
         for the visible blocks (extractor.cu:700-716: 3 points per voxel, 5 faces per cube),
-        capped; a second call with the reported totals follows when they did not suffice."""
+        capped; a second call with the reported totals follows when they did not suffice.
+        `colors` / `normals`: one colour / unit normal per vertex (vk_extract_mesh_attributes)."""
         import torch
         v = self.volume
         blocks = v.max if self.all_allocated else max(v.visible_count, 1)
@@ -1286,11 +1294,19 @@ class Extractor:
         for _ in range(2):
             points = torch.empty((pc, 3), dtype=torch.float32, device=v.device)
             faces = torch.empty((fc, 3), dtype=torch.int32, device=v.device)
-            check(lib().vk_extract_mesh(_ref(v.desc()), int(self.all_allocated), int(self.interpolate), _ptr(points), pc,
-                                        _ptr(faces), fc, _ptr(self.counts), _ptr(self.workspace), stream()), "vk_extract_mesh")
-            np_, nf, self.skipped, self.blocks = (int(c) for c in self.counts.cpu())
+            if colors or normals:
+                c = torch.empty((pc, 3), dtype=torch.float32, device=v.device) if colors else None
+                n = torch.empty((pc, 3), dtype=torch.float32, device=v.device) if normals else None
+                check(lib().vk_extract_mesh_attributes(_ref(v.desc()), int(self.all_allocated), int(self.interpolate),
+                                                       _ptr(points), _ptr(c), _ptr(n), pc, _ptr(faces), fc, _ptr(self.counts),
+                                                       _ptr(self.workspace), stream()), "vk_extract_mesh_attributes")
+            else:
+                c = n = None
+                check(lib().vk_extract_mesh(_ref(v.desc()), int(self.all_allocated), int(self.interpolate), _ptr(points), pc,
+                                            _ptr(faces), fc, _ptr(self.counts), _ptr(self.workspace), stream()), "vk_extract_mesh")
+            np_, nf, self.skipped, self.blocks = (int(k) for k in self.counts.cpu())
             if np_ <= pc and nf <= fc:
-                return Mesh(points[:np_], faces[:nf])
+                return Mesh(points[:np_], faces[:nf], None if c is None else c[:np_], None if n is None else n[:np_])
             pc, fc = max(np_, 1), max(nf, 1)
         raise VkError("vk_extract_mesh: capacities did not settle")
 

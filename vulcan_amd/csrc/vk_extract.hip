@@ -444,6 +444,133 @@ __global__ __launch_bounds__(kExtractThreads) void emit_kernel(ExtractParams P)
   }
 }
 
+// ---- per-vertex colour and normal (vk_extract_mesh_attributes, vk.h) -------------------
+// One more launch behind the four: the points pass keeps its 9^3 lattice and its registers,
+// this one stages the 11^3 lattice a central difference at the far ends of the owned edges
+// needs (-1 ... 9 per axis: up to 26 neighbouring blocks) and is left at once by every block
+// without a vertex. Lattice strides are 1, 11, 121: the 32 lanes of a half wave hold four
+// x rows of 8 at 0, 11, 22, 33 — row 3 shares eight banks of 32 with row 0 (2-way on those
+// lanes); the conflict-free stride, 24, would cost 11.6 KB for reads that only the cubes with
+// a vertex make. The colours are read from the pool for the two ends of actual vertices only.
+constexpr int kWide = 11 * 11 * 11;
+
+struct WideLattice
+{
+  float distance[kWide];
+  uint8_t known[kWide + 1];
+  int slot[27];       // pool slots of block + (m % 3 - 1, m / 3 % 3 - 1, m / 9 - 1)
+};
+
+__device__ __forceinline__ int wide_index(int x, int y, int z) { return (z + 1) * 121 + (y + 1) * 11 + (x + 1); }
+
+// component of the distance gradient at lattice point i (known) along the axis of `stride`
+__device__ __forceinline__ float lattice_gradient(const WideLattice& L, int i, int stride)
+{
+  const bool after = L.known[i + stride] != 0, before = L.known[i - stride] != 0;
+  const float d = L.distance[i], da = L.distance[i + stride], db = L.distance[i - stride];
+  if (after && before) return (da - db) * 0.5f;
+  if (after) return da - d;
+  if (before) return d - db;
+  return 0.0f;
+}
+
+__global__ __launch_bounds__(kExtractThreads) void attributes_kernel(ExtractParams P, float* colors, float* normals)
+{
+  __shared__ WideLattice L;
+  const int block = blockIdx.x;
+  if (block >= *P.list_count) return;
+  if (P.block_counts[2 * block + 0] == 0) return;
+  const Entry entry = load_entry(P.v.hash_entries, (uint32_t)P.list[block]);
+  if (threadIdx.x < 27)
+  {
+    const int m = threadIdx.x;
+    L.slot[m] = (m == 13) ? entry.data
+              : find_slot(P.v.hash_entries, (uint32_t)P.v.main_block_count, entry.ox + m % 3 - 1, entry.oy + (m / 3) % 3 - 1, entry.oz + m / 9 - 1);
+  }
+  __syncthreads();
+  const float* pool = reinterpret_cast<const float*>(P.v.voxels);
+  for (int i = threadIdx.x; i < kWide; i += kExtractThreads)
+  {
+    const int hx = i % 11 - 1, hy = (i / 11) % 11 - 1, hz = i / 121 - 1;
+    const int slot = L.slot[((hx + 8) >> 3) + 3 * ((hy + 8) >> 3) + 9 * ((hz + 8) >> 3)];
+    float d = 0.0f;
+    bool known = false;
+    if (slot >= 0)
+    {
+      const float* voxel = pool + ((size_t)slot * VK_BLOCK_VOXELS + (hz & 7) * 64 + (hy & 7) * 8 + (hx & 7)) * 5;
+      d = voxel[0];
+      known = (__float_as_uint(voxel[4]) & 0xffffu) != 0u;     // distance_weight
+    }
+    L.distance[i] = d;
+    L.known[i] = known ? 1 : 0;
+  }
+  __syncthreads();
+  const int first_vertex = P.block_offsets[2 * block + 0];
+
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+  {
+    const int cube = h * 256 + (int)threadIdx.x;
+    const int x = cube & 7, y = (cube >> 3) & 7, z = cube >> 6;
+    const uint32_t info = P.cube_info[(size_t)block * 512 + cube];
+    const uint32_t flags = info_flags(info);
+    if (!flags) continue;
+    const int ia = wide_index(x, y, z);
+    const float d0 = L.distance[ia];
+    const float* voxel_a = pool + ((size_t)entry.data * VK_BLOCK_VOXELS + cube) * 5;
+    int out = first_vertex + (int)info_voff(info);
+#pragma unroll
+    for (int axis = 0; axis < 3; ++axis)
+    {
+      if (!((flags >> axis) & 1u)) continue;
+      const int vertex = out++;
+      if (vertex >= P.point_capacity) continue;
+      const int bx = x + (axis == 0), by = y + (axis == 1), bz = z + (axis == 2);
+      const int ib = wide_index(bx, by, bz);
+      const float t = P.interpolate ? d0 / (d0 - L.distance[ib]) : 0.5f;
+      if (colors)
+      {
+        // b is known, so its block is there
+        const int slot_b = L.slot[13 + (bx >> 3) + 3 * (by >> 3) + 9 * (bz >> 3)];
+        const float* voxel_b = pool + ((size_t)slot_b * VK_BLOCK_VOXELS + (bz & 7) * 64 + (by & 7) * 8 + (bx & 7)) * 5;
+        const bool has_a = (__float_as_uint(voxel_a[4]) >> 16) != 0u;      // color_weight
+        const bool has_b = (__float_as_uint(voxel_b[4]) >> 16) != 0u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+        {
+          const float ca = voxel_a[1 + c], cb = voxel_b[1 + c];
+          float value = 0.0f;
+          if (has_a && has_b) value = ca + t * (cb - ca);
+          else if (has_a) value = ca;
+          else if (has_b) value = cb;
+          colors[3 * (size_t)vertex + c] = value;
+        }
+      }
+      if (normals)
+      {
+        float g[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+          const int stride = k == 0 ? 1 : (k == 1 ? 11 : 121);
+          const float ga = lattice_gradient(L, ia, stride), gb = lattice_gradient(L, ib, stride);
+          g[k] = ga + t * (gb - ga);
+        }
+        const float n2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+        float n[3] = {0.0f, 0.0f, 0.0f};
+        if (n2 > 0.0f)
+        {
+          const float length = sqrtf(n2);
+          n[0] = g[0] / length; n[1] = g[1] / length; n[2] = g[2] / length;
+        }
+        normals[3 * (size_t)vertex + 0] = n[0];
+        normals[3 * (size_t)vertex + 1] = n[1];
+        normals[3 * (size_t)vertex + 2] = n[2];
+      }
+    }
+  }
+}
+
 inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -495,6 +622,38 @@ int vk_extract_mesh(const vk_volume* v, int all_allocated, int interpolate, floa
   hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, s, P);
   VK_LAUNCH_CHECK();
   hipLaunchKernelGGL(emit_kernel, dim3(P.total), dim3(kExtractThreads), 0, s, P);
+  VK_LAUNCH_CHECK();
+  return VK_OK;
+}
+
+int vk_extract_mesh_attributes(const vk_volume* v, int all_allocated, int interpolate, float* points, float* colors,
+    float* normals, int32_t point_capacity, int32_t* faces, int32_t face_capacity, int32_t* counts_dev, void* workspace,
+    void* stream)
+{
+  const int status = vk_extract_mesh(v, all_allocated, interpolate, points, point_capacity, faces, face_capacity, counts_dev,
+      workspace, stream);
+  if (status != VK_OK || (!colors && !normals)) return status;
+  // what the four launches left in the workspace (the layout of vk_extract_mesh)
+  ExtractParams P;
+  P.v = *v;
+  P.all_allocated = all_allocated ? 1 : 0;
+  P.interpolate = interpolate ? 1 : 0;
+  P.total = v->main_block_count + v->excess_block_count;
+  const size_t total = (size_t)P.total;
+  char* at = static_cast<char*>(workspace);
+  P.list = reinterpret_cast<int32_t*>(at);            at += align_up(total * 4);
+  P.listed = reinterpret_cast<int32_t*>(at);          at += align_up(total * 4);
+  P.list_count = reinterpret_cast<int32_t*>(at);      at += align_up(4);
+  P.cube_info = reinterpret_cast<uint32_t*>(at);      at += align_up(total * 512 * 4);
+  P.tri_offset = reinterpret_cast<uint16_t*>(at);     at += align_up(total * 512 * 2);
+  P.block_counts = reinterpret_cast<int32_t*>(at);    at += align_up(total * 8);
+  P.block_offsets = reinterpret_cast<int32_t*>(at);
+  P.points = points;
+  P.faces = faces;
+  P.point_capacity = point_capacity;
+  P.face_capacity = face_capacity;
+  P.counts = counts_dev;
+  hipLaunchKernelGGL(attributes_kernel, dim3(P.total), dim3(kExtractThreads), 0, vk_s(stream), P, colors, normals);
   VK_LAUNCH_CHECK();
   return VK_OK;
 }

@@ -7,7 +7,10 @@
 //   integrator.Integrate(frame) -> tracer.Trace(keyframe)       (vulcan.cu:297-325)
 // The three SetView calls are one SetView(frame, 3) (same state, tsdf_volume.h).
 //
-//   fuse_sequence [frames=200] [mode=0|1|2|3] [stream=0|1] [split=0|1] [ahead=0|1]
+//   fuse_sequence [frames=200] [mode=0|1|2|3] [stream=0|1] [split=0|1] [ahead=0|1] [excess=8192] [mesh.ply]
+//     mesh.ply (8th argument): after the clock has stopped, the mesh of every allocated block with one colour and one
+//     normal per vertex (Extractor::SetColors / SetNormals) is written there; the colours are what the run fused
+//     (modes 2 and 3 fuse colour, modes 0 and 1 depth only: their colours are black)
 //     ahead = 1 (mode 0): every raycast also makes the NEXT frame's request pass, in its own launch
 //     (Tracer::Trace(keyframe, next_frame)); SetView is then left with its handle + visibility launch
 //     split = 1 (mode 0): SetView's request pass on a stream of its own, beside the previous frame's raycast
@@ -280,6 +283,17 @@ int main(int argc, char** argv)
   (void)vk_event_destroy(steady_from);
   (void)vk_event_destroy(steady_to);
   std::printf("final pose row0: %.5f %.5f %.5f %.5f\n", M(0, 0), M(0, 1), M(0, 2), M(0, 3));
+  if (argc > 7 && argv[7][0] != '\0')
+  {
+    Extractor extractor(volume);
+    extractor.SetAllAllocated(true);
+    extractor.SetColors(true);
+    extractor.SetNormals(true);
+    Mesh mesh;
+    extractor.Extract(mesh);
+    Exporter(argv[7]).Export(mesh);
+    std::printf("mesh %zu points, %zu faces with colours and normals -> %s\n", mesh.points.size(), mesh.faces.size(), argv[7]);
+  }
 
   double motion_translation = 0, motion_rotation = 0;
   PoseError(truth[frames - 1], truth[0], motion_translation, motion_rotation);

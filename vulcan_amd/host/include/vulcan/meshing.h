@@ -2,7 +2,8 @@
 // Extractor (ref: include/vulcan/extractor.h:116-134) and Exporter (ref: include/vulcan/
 // exporter.h). Upstream's BlockExtractor (extractor.h:46-114: one block per launch, blocking
 // copies between its stages, no faces) has no counterpart: the whole volume is one call into
-// the C ABI (vk_extract_mesh) whose only readback is the four totals.
+// the C ABI (vk_extract_mesh) whose only readback is the four totals. Upstream's meshes hold points and faces; here they
+// also hold one colour and one unit normal per vertex when the extractor is asked for them (vk_extract_mesh_attributes).
 #pragma once
 
 #include <memory>
@@ -21,12 +22,16 @@ struct Mesh          // mesh.h:9-14
 {
   std::vector<Vector3f> points;
   std::vector<Vector3i> faces;
+  std::vector<Vector3f> colors;    // empty, or one per point: the fused colour
+  std::vector<Vector3f> normals;   // empty, or one per point: unit length, towards the positive-distance side
 };
 
 struct DeviceMesh    // mesh.h:16-21
 {
   Buffer<Vector3f> points;
   Buffer<Vector3i> faces;
+  Buffer<Vector3f> colors;         // size 0 unless Extractor::SetColors(true)
+  Buffer<Vector3f> normals;        // size 0 unless Extractor::SetNormals(true)
 };
 
 class Extractor
@@ -47,6 +52,12 @@ class Extractor
     bool GetInterpolate() const { return interpolate_; }
     void SetInterpolate(bool on) { interpolate_ = on; }
 
+    // per-vertex attributes (vk.h: vk_extract_mesh_attributes), both off by default: Extract is then upstream's
+    bool GetColors() const { return colors_; }
+    void SetColors(bool on) { colors_ = on; }
+    bool GetNormals() const { return normals_; }
+    void SetNormals(bool on) { normals_ = on; }
+
     void Extract(DeviceMesh& mesh) const;
 
     void Extract(Mesh& mesh) const;
@@ -63,6 +74,8 @@ class Extractor
     std::shared_ptr<const Volume> volume_;
     bool all_allocated_;
     bool interpolate_;
+    bool colors_;
+    bool normals_;
     mutable int skipped_;
     mutable Buffer<unsigned char> workspace_;
     mutable Buffer<int> counts_;
@@ -76,7 +89,8 @@ class Exporter
 
     const std::string& GetFile() const;
 
-    // ASCII PLY, byte-compatible with src/exporter.cpp:19-71
+    // ASCII PLY, byte-compatible with src/exporter.cpp:19-71. mesh.normals of the points' size add nx ny nz behind z;
+    // mesh.colors of the points' size replace upstream's grey ramp by int(min(max(c, 0), 1) * 255 + 0.5) per channel
     void Export(const Mesh& mesh) const;
 
   protected:

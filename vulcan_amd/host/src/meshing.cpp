@@ -23,6 +23,8 @@ Extractor::Extractor(std::shared_ptr<const Volume> volume) :
   volume_(volume),
   all_allocated_(false),
   interpolate_(true),
+  colors_(false),
+  normals_(false),
   skipped_(0)
 {
   VULCAN_ASSERT_MSG(volume_, "extractor needs a volume");
@@ -41,8 +43,12 @@ void Extractor::ResizeMesh(DeviceMesh& mesh) const
   const size_t max_faces = 5 * 512 * blocks;
   if (mesh.points.GetCapacity() < max_points) mesh.points.Reserve(max_points);
   if (mesh.faces.GetCapacity() < max_faces) mesh.faces.Reserve(max_faces);
+  if (colors_ && mesh.colors.GetCapacity() < max_points) mesh.colors.Reserve(max_points);
+  if (normals_ && mesh.normals.GetCapacity() < max_points) mesh.normals.Reserve(max_points);
   mesh.points.Resize(0);
   mesh.faces.Resize(0);
+  mesh.colors.Resize(0);
+  mesh.normals.Resize(0);
 }
 
 void Extractor::Extract(DeviceMesh& mesh) const
@@ -60,10 +66,20 @@ void Extractor::Extract(DeviceMesh& mesh) const
   {
     if (mesh.points.GetCapacity() < point_capacity) mesh.points.Reserve(point_capacity);
     if (mesh.faces.GetCapacity() < face_capacity) mesh.faces.Reserve(face_capacity);
-    VK_ASSERT(vk_extract_mesh(&v, all_allocated_ ? 1 : 0, interpolate_ ? 1 : 0,
-        reinterpret_cast<float*>(mesh.points.GetData()), (int32_t)point_capacity,
-        reinterpret_cast<int32_t*>(mesh.faces.GetData()), (int32_t)face_capacity, counts_.GetData(),
-        workspace_.GetData(), Device::GetStream()));
+    if (colors_ && mesh.colors.GetCapacity() < point_capacity) mesh.colors.Reserve(point_capacity);
+    if (normals_ && mesh.normals.GetCapacity() < point_capacity) mesh.normals.Reserve(point_capacity);
+    if (colors_ || normals_)
+      VK_ASSERT(vk_extract_mesh_attributes(&v, all_allocated_ ? 1 : 0, interpolate_ ? 1 : 0,
+          reinterpret_cast<float*>(mesh.points.GetData()),
+          colors_ ? reinterpret_cast<float*>(mesh.colors.GetData()) : nullptr,
+          normals_ ? reinterpret_cast<float*>(mesh.normals.GetData()) : nullptr, (int32_t)point_capacity,
+          reinterpret_cast<int32_t*>(mesh.faces.GetData()), (int32_t)face_capacity, counts_.GetData(),
+          workspace_.GetData(), Device::GetStream()));
+    else
+      VK_ASSERT(vk_extract_mesh(&v, all_allocated_ ? 1 : 0, interpolate_ ? 1 : 0,
+          reinterpret_cast<float*>(mesh.points.GetData()), (int32_t)point_capacity,
+          reinterpret_cast<int32_t*>(mesh.faces.GetData()), (int32_t)face_capacity, counts_.GetData(),
+          workspace_.GetData(), Device::GetStream()));
     counts_.CopyToHost(counts);      // the only readback: four totals
     if ((size_t)counts[0] <= point_capacity && (size_t)counts[1] <= face_capacity) break;
     point_capacity = counts[0];
@@ -71,6 +87,8 @@ void Extractor::Extract(DeviceMesh& mesh) const
   }
   mesh.points.Resize(counts[0]);
   mesh.faces.Resize(counts[1]);
+  mesh.colors.Resize(colors_ ? counts[0] : 0);
+  mesh.normals.Resize(normals_ ? counts[0] : 0);
   skipped_ = counts[2];
 }
 
@@ -82,6 +100,10 @@ void Extractor::Extract(Mesh& mesh) const
   mesh.faces.resize(device.faces.GetSize());
   if (!mesh.points.empty()) device.points.CopyToHost(mesh.points.data());
   if (!mesh.faces.empty()) device.faces.CopyToHost(mesh.faces.data());
+  mesh.colors.resize(device.colors.GetSize());
+  mesh.normals.resize(device.normals.GetSize());
+  if (!mesh.colors.empty()) device.colors.CopyToHost(mesh.colors.data());
+  if (!mesh.normals.empty()) device.normals.CopyToHost(mesh.normals.data());
 }
 
 // ---- Exporter --------------------------------------------------------------------
@@ -94,12 +116,15 @@ const std::string& Exporter::GetFile() const { return file_; }
 // host_tests compare files byte for byte): the header below, then per vertex "x y z g g g" with the
 // coordinates in the stream's default float format (= %g) and g a grey value that upstream derives from z as
 // a debugging aid — 255 * min(1, (z - 0.35) / (zmax - 0.35)), truncated — then per face "3 i j k".
+// A mesh with attributes (no upstream counterpart; the bytes are vulcan_amd/io.py write_ply's): normals of the points' size
+// add "property float nx / ny / nz" behind z, printed as the coordinates are; colours of the points' size take the ramp's
+// place, each channel int(min(max(c, 0), 1) * 255 + 0.5) in float.
 // The whole file is formatted into one buffer and written once.
 namespace
 {
-const char* const kPlyHeader[] = {
-    "property float x", "property float y", "property float z",
-    "property uchar red", "property uchar green", "property uchar blue"};
+const char* const kPlyPosition[] = {"property float x", "property float y", "property float z"};
+const char* const kPlyNormal[] = {"property float nx", "property float ny", "property float nz"};
+const char* const kPlyColor[] = {"property uchar red", "property uchar green", "property uchar blue"};
 
 void append_number(std::string& text, float value)
 {
@@ -117,11 +142,15 @@ void Exporter::Export(const Mesh& mesh) const
 {
   const size_t vertices = mesh.points.size(), triangles = mesh.faces.size();
   std::string text;
-  text.reserve(160 + 48 * vertices + 40 * triangles);
+  text.reserve(240 + 96 * vertices + 40 * triangles);
   text += "ply\nformat ascii 1.0\nelement vertex ";
   append_number(text, (long long)vertices);
   text += '\n';
-  for (const char* line : kPlyHeader) { text += line; text += '\n'; }
+  const bool with_normals = vertices > 0 && mesh.normals.size() == vertices;
+  const bool with_colors = vertices > 0 && mesh.colors.size() == vertices;
+  for (const char* line : kPlyPosition) { text += line; text += '\n'; }
+  if (with_normals) for (const char* line : kPlyNormal) { text += line; text += '\n'; }
+  for (const char* line : kPlyColor) { text += line; text += '\n'; }
   text += "element face ";
   append_number(text, (long long)triangles);
   text += "\nproperty list uchar int vertex_indices\nend_header\n";
@@ -138,9 +167,19 @@ void Exporter::Export(const Mesh& mesh) const
     const float ramp = 255 * min(1.0f, (p[2] - near_z) / (far_z - near_z));
     const long long grey = std::isfinite(ramp) ? (long long)int(ramp) : 0;   // upstream: undefined when far_z == near_z
     for (int axis = 0; axis < 3; ++axis) { append_number(text, p[axis]); text += ' '; }
-    append_number(text, grey);  text += ' ';
-    append_number(text, grey);  text += ' ';
-    append_number(text, grey);  text += '\n';
+    if (with_normals)
+      for (int axis = 0; axis < 3; ++axis) { append_number(text, mesh.normals[i][axis]); text += ' '; }
+    for (int channel = 0; channel < 3; ++channel)
+    {
+      long long value = grey;
+      if (with_colors)
+      {
+        const float scaled = min(max(mesh.colors[i][channel], 0.0f), 1.0f) * 255.0f;
+        value = (long long)int(scaled + 0.5f);
+      }
+      append_number(text, value);
+      text += channel < 2 ? ' ' : '\n';
+    }
   }
   for (size_t i = 0; i < triangles; ++i)
   {

@@ -5,7 +5,9 @@ write_ply     vulcan::Exporter::Export (src/exporter.cpp:19-71), byte for byte: 
               `element vertex` with x y z and the red/green/blue debug colouring upstream
               marks "REMOVE" (a grey ramp over z from a fixed 0.35 to the largest z),
               `element face` as `3 i j k`; numbers as a C++ ostream prints floats.
-read_ply      the inverse, for tests.
+              With `colors` the fused colours are written instead of the ramp, with `normals`
+              nx / ny / nz follow z (both from Extractor.extract(colors=True, normals=True)).
+read_ply      the inverse, for tests; read_ply_attributes reads the header's property list.
 load_depth / save_depth, load_color / save_color
               Image::Load / Save and ColorImage::Load / Save (include/vulcan/image.h:100-133,
               228-253; src/image.cu:213-221,264-273) for the formats that need no OpenCV:
@@ -27,22 +29,43 @@ def _g(x):
     return "%g" % float(np.float32(x))
 
 
-def write_ply(path, points, faces):
+def write_ply(path, points, faces, colors=None, normals=None):
+    """Without attributes: upstream's bytes. `colors` [n, 3] in [0, 1] replace the grey ramp: each channel
+    int(min(max(c, 0), 1) * 255 + 0.5), in float32. `normals` [n, 3] add `property float nx / ny / nz` between z and
+    red, printed as the coordinates are."""
     points = np.asarray(points, dtype=np.float32).reshape(-1, 3)
     faces = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+    if colors is not None:
+        colors = np.asarray(colors, dtype=np.float32).reshape(-1, 3)
+        assert len(colors) == len(points)
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+        assert len(normals) == len(points)
     out = ["ply", "format ascii 1.0", f"element vertex {len(points)}", "property float x", "property float y",
-           "property float z", "property uchar red", "property uchar green", "property uchar blue",
-           f"element face {len(faces)}", "property list uchar int vertex_indices", "end_header"]
+           "property float z"]
+    if normals is not None:
+        out += ["property float nx", "property float ny", "property float nz"]
+    out += ["property uchar red", "property uchar green", "property uchar blue",
+            f"element face {len(faces)}", "property list uchar int vertex_indices", "end_header"]
     # exporter.cpp:38-56: dmax = largest z; dmin is overwritten with 0.35f
     F = np.float32
     dmin = F(0.35)
     dmax = points[:, 2].max() if len(points) else F(0)
+    if colors is not None:
+        bytes_ = (np.minimum(np.maximum(colors, F(0)), F(1)) * F(255) + F(0.5)).astype(np.int32)
     with np.errstate(divide="ignore", invalid="ignore"):
-        for p in points:
-            ratio = F(F(p[2] - dmin) / F(dmax - dmin))                 # exporter.cpp:62
-            value = F(255) * (ratio if ratio < F(1.0) else F(1.0))     # min(1.0f, ratio), math.h:9-15
-            color = int(value) if np.isfinite(value) else 0             # int(float) truncates; non-finite is undefined upstream
-            out.append(f"{_g(p[0])} {_g(p[1])} {_g(p[2])} {color} {color} {color}")
+        for i, p in enumerate(points):
+            line = f"{_g(p[0])} {_g(p[1])} {_g(p[2])}"
+            if normals is not None:
+                line += f" {_g(normals[i][0])} {_g(normals[i][1])} {_g(normals[i][2])}"
+            if colors is not None:
+                line += f" {bytes_[i][0]} {bytes_[i][1]} {bytes_[i][2]}"
+            else:
+                ratio = F(F(p[2] - dmin) / F(dmax - dmin))                 # exporter.cpp:62
+                value = F(255) * (ratio if ratio < F(1.0) else F(1.0))     # min(1.0f, ratio), math.h:9-15
+                color = int(value) if np.isfinite(value) else 0             # int(float) truncates; non-finite is undefined upstream
+                line += f" {color} {color} {color}"
+            out.append(line)
     for f in faces:
         out.append(f"3 {int(f[0])} {int(f[1])} {int(f[2])}")
     with open(path, "w") as fh:
@@ -61,6 +84,34 @@ def read_ply(path):
     colors = np.array([[int(t) for t in body[i].split()[3:6]] for i in range(nv)], dtype=np.int32).reshape(-1, 3)
     faces = np.array([[int(t) for t in body[nv + i].split()[1:4]] for i in range(nf)], dtype=np.int32).reshape(-1, 3)
     return verts, colors, faces
+
+
+def read_ply_attributes(path):
+    """A file of write_ply by its header's property list: (points, faces, colors, normals) — colors [n, 3] int32 from
+    red / green / blue, normals [n, 3] float32 from nx / ny / nz, None for what the header does not name."""
+    with open(path) as fh:
+        lines = fh.read().split("\n")
+    assert lines[0] == "ply" and lines[1] == "format ascii 1.0"
+    end = lines.index("end_header")
+    element, counts, names = None, {}, []
+    for line in lines[2:end]:
+        t = line.split()
+        if t[0] == "element":
+            element = t[1]
+            counts[element] = int(t[2])
+        elif t[0] == "property" and element == "vertex":
+            names.append(t[-1])
+    nv, nf = counts.get("vertex", 0), counts.get("face", 0)
+    body = lines[end + 1:]
+    table = np.array([[float(t) for t in body[i].split()] for i in range(nv)], dtype=np.float64).reshape(nv, len(names))
+
+    def columns(wanted, dtype):
+        if not all(w in names for w in wanted):
+            return None
+        return np.ascontiguousarray(table[:, [names.index(w) for w in wanted]].astype(dtype))
+    faces = np.array([[int(t) for t in body[nv + i].split()[1:4]] for i in range(nf)], dtype=np.int32).reshape(-1, 3)
+    return (columns(("x", "y", "z"), np.float32), faces, columns(("red", "green", "blue"), np.int32),
+            columns(("nx", "ny", "nz"), np.float32))
 
 
 # ---- Netpbm -------------------------------------------------------------------------
