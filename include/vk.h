@@ -797,6 +797,15 @@ VK_API int vk_icp_solve_update(const float* hessian, const float* gradient,
     int translation_enabled, vk_transform* Twc_dev, int32_t* state_dev,
     float* update_dev, void* stream);
 
+/* ref: src/tracker.cpp:124-163 Tracker::ComputeUpdate + src/depth_tracker.cpp:22-86 DepthTracker::ApplyUpdate for ONE
+ * CAMERA OF A RIGID RIG (see "A rigid multi-camera rig" below; the reference has one camera): the same solve and the
+ * same Tinc as vk_icp_solve_update, applied as *Twc_dev = rigid_from(D * Twc) with D = rigid_from(Tinc), the
+ * re-orthonormalisation of Tinc alone — a rigid motion that does not depend on the camera it is applied to. Every
+ * other argument, `state_dev` and the no-op after convergence as in vk_icp_solve_update. */
+VK_API int vk_icp_solve_update_rig(const float* hessian, const float* gradient,
+    int translation_enabled, vk_transform* Twc_dev, int32_t* state_dev,
+    float* update_dev, void* stream);
+
 /* Called between the system and the solve of every iteration with the packed
  * device system (48 floats: hessian[36], gradient[6], pad): a multi-GPU rig sums
  * it over ranks here (ncclAllReduce on `stream`). Returns 0 on success. */
@@ -880,7 +889,24 @@ VK_API int vk_icp_track(const vk_icp_view* keyframe, const vk_transform* Twm,
  * kept: one workgroup of every rank writes its 27 {tag, value} words straight into every peer's
  * memory (areas mapped over xGMI by vk_comm_exchange_attach, include/vk_comm.h), all workgroups
  * read their own GPU's area, add the ranks' words in rank order (the same bits everywhere) and
- * solve. Protocol and its proof obligations: vulcan_amd/csrc/vk_rig_protocol.h. */
+ * solve. Protocol and its proof obligations: vulcan_amd/csrc/vk_rig_protocol.h.
+ *
+ * THE RIG'S INCREMENT. The update x of the one solve must move every camera by the SAME world-frame
+ * rigid motion, or the rig bends. DepthTracker::ApplyUpdate (src/depth_tracker.cpp:33-84) does not
+ * do that when it is run per camera: Tinc(1,2) = +x[0] (upstream's sign, kept: SURVEY 2.5-11) makes
+ * Tinc no rotation to first order, and what the re-orthonormalisation of Tinc * Twc makes of its
+ * symmetric part depends on Twc. Cameras that are not parallel or opposed drift apart by O(|x[0]|)
+ * in the first steps, nothing in the common solve can pull them back, and the loop converges on a
+ * rig that is bent — 6 to 8 mm and 0.4 degrees for the ring of configs[4] from a 5 mm start
+ * (docs/rounds/r08.md; oracle: oracle.rig_track, tests/test_oracle_rig.py). The rig's Tracks therefore
+ * apply D = rigid_from(Tinc), Gram-Schmidt of Tinc alone — exp([x]) to first order, independent of
+ * the pose — as Twc_r = rigid_from(D * Twc_r):
+ *   vk_icp_track_rig with world > 1, vk_icp_track_rig_hook, vk_icp_solve_update_rig.
+ * Everything else keeps ApplyUpdate as upstream has it (the "camera form"), bit for bit: vk_icp_track
+ * with or without a `reduce` hook (a hook alone does not make a rig: vk_reduce_nothing is the fallback
+ * of plain Tracks), vk_icp_track_rig with world == 1, vk_icp_solve_update, and every
+ * vk_icp_pyramid_track* call — their `reduce` argument runs the camera form, so a rig that tracks
+ * coarse-to-fine through them is only right for parallel or opposed cameras. */
 #define VK_RIG_MAX_RANKS 8
 typedef struct vk_rig_exchange {
   unsigned long long* areas[VK_RIG_MAX_RANKS]; /* areas[r]: rank r's area as mapped into THIS process (areas[rank]:
@@ -897,12 +923,22 @@ VK_API size_t vk_rig_area_bytes(void);
 /* ref: src/tracker.cpp:53-63 Tracker::Track for DepthTracker on a rig: vk_icp_track (no `reduce`: the whole
  * loop is one launch per rank) with the ranks' sums added through `rig` after every step. Every rank
  * calls it for the same Track with the same sequence number, iterations (<= 1000) and
- * translation_enabled; world == 1 gives vk_icp_track's bits. A rank that waits two seconds for a peer
- * ends with VK_TRACK_ABORTED. */
+ * translation_enabled. world > 1 applies the rig's increment (above); world == 1 gives vk_icp_track's bits.
+ * A rank that waits two seconds for a peer ends with VK_TRACK_ABORTED. */
 VK_API int vk_icp_track_rig(const vk_icp_view* keyframe, const vk_transform* Twm,
     const vk_icp_view* frame, vk_transform* Twc_dev, int iterations,
     int translation_enabled, float* workspace, float* system, int32_t* state_dev,
     float* update_dev, const vk_rig_exchange* rig, const vk_track_poll* poll, void* stream);
+
+/* ref: src/tracker.cpp:53-63 Tracker::Track for DepthTracker on a rig whose sums are added by a `reduce` hook
+ * (required: an all-reduce over the ranks, e.g. vk_comm_reduce_hook): vk_icp_track with that hook — three launches
+ * per step, `poll` stops the enqueuing after convergence — whose solve applies the rig's increment (above). The
+ * opt-in of the hook path: vk_icp_track itself keeps the camera form whatever `reduce` is. Arguments as vk_icp_track. */
+VK_API int vk_icp_track_rig_hook(const vk_icp_view* keyframe, const vk_transform* Twm,
+    const vk_icp_view* frame, vk_transform* Twc_dev, int iterations,
+    int translation_enabled, float* workspace, float* system, int32_t* state_dev,
+    float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user, const vk_track_poll* poll,
+    void* stream);
 
 /* ref: src/pyramid_tracker.cpp:52-90 PyramidTracker<DepthTracker>::Track — the half-
  * resolution level of both frames (Frame::Downsample, src/frame.cpp:38-58: nearest
@@ -912,7 +948,9 @@ VK_API int vk_icp_track_rig(const vk_icp_view* keyframe, const vk_transform* Twm
  * upstream builds and never tracks (:64-77) is not built. `pyramid`: device float[vk_icp_pyramid_floats(...)] for the half-resolution
  * images; `workspace`: vk_icp_workspace_floats of the FULL frame size; the other
  * buffers as in vk_icp_track. state_dev is reset before each level and holds the
- * full-resolution level's {steps, converged} afterwards. Image sizes must be even. */
+ * full-resolution level's {steps, converged} afterwards. Image sizes must be even.
+ * `reduce` runs both levels launch per stage with the CAMERA form of the pose update (vk_icp_track's), also when the
+ * hook sums over the ranks of a rig: there is no coarse-to-fine rig Track yet ("THE RIG'S INCREMENT" above). */
 VK_API size_t vk_icp_pyramid_floats(int key_width, int key_height, int frame_width, int frame_height);
 VK_API int vk_icp_pyramid_track(const vk_icp_view* keyframe, const vk_transform* Twm,
     const vk_icp_view* frame, vk_transform* Twc_dev, float* pyramid, float* workspace,

@@ -97,6 +97,10 @@ void orc_ldlt_solve(int n, const float* A, const float* b, float* x);
 void orc_ldlt_solve_pivoted(int n, const float* A, const float* b, float* x);
 float orc_icp_solve_update(const float* hessian_packed, const float* gradient,
     int translation_enabled, vk_transform* Twc, float* update);
+/* one camera of a rigid rig: Twc <- rigid_from(D(update) * Twc) with D = rigid_from(Tinc) alone */
+void orc_icp_rig_increment(const float* update, vk_transform* D);
+float orc_icp_solve_update_rig(const float* hessian_packed, const float* gradient,
+    int translation_enabled, vk_transform* Twc, float* update);
 
 /* known-answer hooks (tests/test_oracle_kats.py) */
 /* colour tracker (oracle_color_tracker.c) */

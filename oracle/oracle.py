@@ -38,6 +38,7 @@ def lib():
             so = build()
         _LIB = C.CDLL(so)
         _LIB.orc_icp_solve_update.restype = C.c_float
+        _LIB.orc_icp_solve_update_rig.restype = C.c_float
     return _LIB
 
 
@@ -309,13 +310,24 @@ def ldlt_solve(A, b, pivoted=False):
     return x
 
 
-def icp_solve_update(hessian_packed, gradient, Twc, translation_enabled=True):
+def icp_solve_update(hessian_packed, gradient, Twc, translation_enabled=True, increment="camera"):
+    """Solve and apply: "camera" is ApplyUpdate as upstream has it, Twc <- rigid_from(Tinc * Twc); "rig" applies the
+    pose-independent motion D = rigid_from(Tinc), Twc <- rigid_from(D * Twc) (orc_icp_solve_update_rig)."""
     h = np.ascontiguousarray(hessian_packed, dtype=np.float32)
     g = np.ascontiguousarray(gradient, dtype=np.float32)
     out = T.Transform.from_matrices(Twc.matrix(), Twc.inverse_matrix())
     update = np.zeros(6, dtype=np.float32)
-    norm = lib().orc_icp_solve_update(_p(h), _p(g), int(translation_enabled), C.byref(out), _p(update))
+    fn = {"camera": lib().orc_icp_solve_update, "rig": lib().orc_icp_solve_update_rig}[increment]
+    norm = fn(_p(h), _p(g), int(translation_enabled), C.byref(out), _p(update))
     return out, update, float(norm)
+
+
+def icp_rig_increment(update):
+    """D(u) = rigid_from(Tinc(u)): the rigid motion the rig form applies for the update u."""
+    u = np.ascontiguousarray(update, dtype=np.float32)
+    out = T.Transform.identity()
+    lib().orc_icp_rig_increment(_p(u), C.byref(out))
+    return out
 
 
 def icp_track(key, frame, max_iterations=20, translation_enabled=True):
@@ -331,6 +343,45 @@ def icp_track(key, frame, max_iterations=20, translation_enabled=True):
             break
     frame.depth_to_world = pose
     return pose, it
+
+
+def packed_system(hessian, gradient):
+    """The device's 48-float system (vk.h: hessian[36], gradient[6], pad) from a view's float64 sums."""
+    system = np.zeros(48, dtype=np.float32)
+    system[:21] = hessian
+    system[36:42] = gradient
+    return system
+
+
+def rig_track(keys, frames, max_iterations=20, translation_enabled=True, increment="rig", record=None):
+    """Tracker::Track for a rigid rig of DepthTrackers (BASELINE configs[4]; the reference has one camera): per step
+    every view's system (icp_system, cast to float32 as the device publishes it), the 21 + 6 sums added over the views
+    in rank order in float32, ONE solve, applied to every camera's own pose; until max_iterations or |update| < 1e-6.
+    Updates every frame.depth_to_world; returns (poses, steps run, last update). With `record` (a list) every step
+    appends {"systems": [48 floats per view], "update": the 6 floats}. One view is icp_track, bit for bit, whatever
+    `increment` says: a rig of one camera is a plain tracker (as vk_icp_track_rig with world == 1 is vk_icp_track)."""
+    poses, it = [f.depth_to_world for f in frames], 0
+    if len(frames) == 1:
+        increment = "camera"
+    update = np.zeros(6, dtype=np.float32)
+    while it < max_iterations:
+        systems = []
+        for key, frame, pose in zip(keys, frames, poses):
+            frame.depth_to_world = pose
+            systems.append(packed_system(*icp_system(key, frame, translation_enabled)))
+        total = systems[0].copy()
+        for system in systems[1:]:
+            total = total + system                      # float32, rank order
+        solved = [icp_solve_update(total[:21], total[36:42], pose, translation_enabled, increment) for pose in poses]
+        poses, update, norm = [s[0] for s in solved], solved[0][1], solved[0][2]
+        if record is not None:
+            record.append({"systems": systems, "update": update.copy()})
+        it += 1
+        if norm < 1e-6:
+            break
+    for frame, pose in zip(frames, poses):
+        frame.depth_to_world = pose
+    return poses, it, update
 
 
 def pyramid_track(key, frame):

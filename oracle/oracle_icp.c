@@ -295,6 +295,23 @@ vk_transform orc_rigid_from(const float* M)
   return o_transform_mul(&T, &R);
 }
 
+/* depth_tracker.cpp:33-53; note Tinc(1,2) = +update[0] */
+static void tinc_from(const float* update, float* Tinc)
+{
+  Tinc[0 + 4 * 0] = 1.0f;       Tinc[0 + 4 * 1] = -update[2]; Tinc[0 + 4 * 2] = +update[1]; Tinc[0 + 4 * 3] = +update[3];
+  Tinc[1 + 4 * 0] = +update[2]; Tinc[1 + 4 * 1] = 1.0f;       Tinc[1 + 4 * 2] = +update[0]; Tinc[1 + 4 * 3] = +update[4];
+  Tinc[2 + 4 * 0] = -update[1]; Tinc[2 + 4 * 1] = +update[0]; Tinc[2 + 4 * 2] = 1.0f;       Tinc[2 + 4 * 3] = +update[5];
+  Tinc[3 + 4 * 0] = 0.0f;       Tinc[3 + 4 * 1] = 0.0f;       Tinc[3 + 4 * 2] = 0.0f;       Tinc[3 + 4 * 3] = 1.0f;
+}
+
+static float update_norm(const float* update, int n, float* update_out)
+{
+  float sq = 0;
+  for (int i = 0; i < n; ++i) sq += update[i] * update[i];
+  if (update_out) for (int i = 0; i < 6; ++i) update_out[i] = update[i];
+  return sqrtf(sq);
+}
+
 /* ref: tracker.cpp:124-163 ComputeUpdate + depth_tracker.cpp:22-86 ApplyUpdate */
 float orc_icp_solve_update(const float* hessian_packed, const float* gradient,
     int translation_enabled, vk_transform* Twc, float* update_out)
@@ -303,21 +320,45 @@ float orc_icp_solve_update(const float* hessian_packed, const float* gradient,
   float update[6];
   orc_solve_step(hessian_packed, gradient, translation_enabled, update);
 
-  /* depth_tracker.cpp:33-53; note Tinc(1,2) = +update[0] */
   float Tinc[16];
-  Tinc[0 + 4 * 0] = 1.0f;       Tinc[0 + 4 * 1] = -update[2]; Tinc[0 + 4 * 2] = +update[1]; Tinc[0 + 4 * 3] = +update[3];
-  Tinc[1 + 4 * 0] = +update[2]; Tinc[1 + 4 * 1] = 1.0f;       Tinc[1 + 4 * 2] = +update[0]; Tinc[1 + 4 * 3] = +update[4];
-  Tinc[2 + 4 * 0] = -update[1]; Tinc[2 + 4 * 1] = +update[0]; Tinc[2 + 4 * 2] = 1.0f;       Tinc[2 + 4 * 3] = +update[5];
-  Tinc[3 + 4 * 0] = 0.0f;       Tinc[3 + 4 * 1] = 0.0f;       Tinc[3 + 4 * 2] = 0.0f;       Tinc[3 + 4 * 3] = 1.0f;
+  tinc_from(update, Tinc);
 
   float M[16];
   o_matmul4(Tinc, Twc->m, M);  /* :55 */
   *Twc = orc_rigid_from(M);    /* :57-84 */
 
-  float sq = 0;
-  for (int i = 0; i < n; ++i) sq += update[i] * update[i];
-  if (update_out) for (int i = 0; i < 6; ++i) update_out[i] = update[i];
-  return sqrtf(sq);
+  return update_norm(update, n, update_out);
+}
+
+/* The rig's increment D(u) = rigid_from(Tinc(u)): Gram-Schmidt of Tinc ALONE, so the motion an update
+ * stands for does not depend on the pose it is applied to (ref: none — depth_tracker.cpp:33-84
+ * re-orthonormalises Tinc * Twc, which does; see orc_icp_solve_update_rig). */
+void orc_icp_rig_increment(const float* update, vk_transform* D)
+{
+  float Tinc[16];
+  tinc_from(update, Tinc);
+  *D = orc_rigid_from(Tinc);
+}
+
+/* ref: tracker.cpp:124-163 ComputeUpdate + depth_tracker.cpp:22-86 ApplyUpdate for one camera of a rigid
+ * rig (BASELINE configs[4]; the reference has one camera): the same solve and the same Tinc, applied as
+ * Twc <- rigid_from(rigid_from(Tinc) * Twc). Tinc(1,2) = +update[0] makes Tinc no rotation to first order,
+ * and what rigid_from(Tinc * Twc) makes of its symmetric part depends on Twc: the cameras of a rig would
+ * each turn one update into another world-frame motion and bend the rig. */
+float orc_icp_solve_update_rig(const float* hessian_packed, const float* gradient,
+    int translation_enabled, vk_transform* Twc, float* update_out)
+{
+  const int n = translation_enabled ? 6 : 3;
+  float update[6];
+  orc_solve_step(hessian_packed, gradient, translation_enabled, update);
+
+  vk_transform D;
+  orc_icp_rig_increment(update, &D);
+  float M[16];
+  o_matmul4(D.m, Twc->m, M);
+  *Twc = orc_rigid_from(M);
+
+  return update_norm(update, n, update_out);
 }
 
 /* ref: image.cu:101-131 DownsampleKernel<nearest>(float) */

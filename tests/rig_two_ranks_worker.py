@@ -29,7 +29,9 @@ def main():
     k = T.Projection.make(*(np.float32(0.5) * np.float32(v) for v in scenes.APP_INTRINSICS))
     y, x = np.mgrid[0:h, 0:w]
     depth = (1.5 + 0.08 * np.cos(3.0 * x / w + rank) * np.sin(2.0 * y / h + 0.5 * rank)).astype(np.float32)
-    rig_pose = scenes.yaw(360.0 * rank / world)                               # camera `rank` of the ring
+    # camera `rank` of the ring 0 / 90 degrees: cameras that are neither parallel nor opposed, so a per-camera pose
+    # update that is not one world-frame motion bends the rig (0 / 180, this worker's ring until round 8, hides that)
+    rig_pose = scenes.yaw(90.0 * rank)
     key = api.Frame(depth, k, rig_pose)
     key.compute_normals()
     errors = [T.Transform.translate(0.003, -0.002, 0.004) * T.Transform.rotate(0.999995, 0.002, -0.0015, 0.001),
@@ -52,6 +54,7 @@ def main():
         hooked = api.DepthTracker()
         hooked.keyframe = key
         hooked.reduce_hook = gloo_sum
+        hooked.rig_increment = True                                           # the hook path's opt-in; track_rig needs none
         want = []
         for e in errors:
             frame = api.Frame(depth, k, e * rig_pose, normals=key.normals)
@@ -83,6 +86,17 @@ def main():
         out["rig_steps"] = steps
         out["poses_equal_the_hook_path"] = got == want[:len(got)] and len(got) == len(errors)
         out["update_identical_on_all_ranks"] = bool(updates_equal) and all(updates_equal)
+        # every Track's pose against the rig oracle's for this camera (tests/golden/rig_views.json, made by
+        # tests/golden/make_rig_views.py from the same analytic scene): max |entry difference| per Track, both paths
+        golden = json.load(open(os.path.join(ROOT, "tests", "golden", "rig_views.json")))["rigs"]["pair_90_320x240"]
+        assert (golden["width"], golden["height"], golden["yaw_degrees"]) == (w, h, [90.0 * r for r in range(world)])
+
+        def from_fixture(poses):
+            return [float(np.abs(np.frombuffer(p, dtype=np.float32)[:16] - np.float32(t["poses"][rank])).max())
+                    for p, t in zip(poses, golden["tracks"])]
+        out["hook_pose_minus_fixture"] = from_fixture(want)
+        out["rig_pose_minus_fixture"] = from_fixture(got)
+        out["fixture_steps"] = [t["steps"] for t in golden["tracks"]]
         # the pose came back to the rig's: the ranks really solved ONE system
         if got:
             last = T.Transform.from_buffer_copy(got[-1])

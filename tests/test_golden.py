@@ -96,3 +96,28 @@ def test_oracle_reproduces_the_soak_drift_fixtures_first_report(orc, tmp_path):
     # and what the file says: the error grows steadily (the algorithm's creep), nothing is dropped in 2 000 frames
     assert golden[-1]["pose_error_max"]["translation_m"] > 1.8 * golden[0]["pose_error_max"]["translation_m"]
     assert all(r["dropped_requests"] == 0 for r in golden)
+
+
+def test_oracle_reproduces_the_rig_views_first_tracks(orc):
+    """tests/golden/rig_views.json (make_rig_views.py: the rig oracle's per-step systems and updates, final poses and step
+    counts for the 0/90 pair at 320 x 240 and the eight-camera ring at 160 x 120 — what tests/test_gpu_rig_oracle.py and the
+    two-process rig test hold the device to): the first Track of each rig, re-made, is the file's to the bit."""
+    import make_rig_views as rv
+    assert os.path.exists(rv.FILE), "run python tests/golden/make_rig_views.py"
+    assert os.path.getsize(rv.FILE) < 300 << 10
+    golden = rv.load()["rigs"]
+    assert sorted(golden) == sorted(rv.RECORDED)
+    got = rv.make(orc, first_only=True)
+    for name, (ring, w, h, count) in rv.RECORDED.items():
+        rig = golden[name]
+        assert (rig["ring"], rig["width"], rig["height"], len(rig["tracks"])) == (ring, w, h, count)
+        assert rig["yaw_degrees"] == list(rv.RINGS[ring])
+        assert got[name]["tracks"][0] == rig["tracks"][0], name            # JSON numbers of float32 values: exact
+        for track in rig["tracks"]:
+            views = len(rv.RINGS[ring])
+            assert track["steps"] == len(track["updates"]) == len(track["systems"]) and 2 <= track["steps"] < 20
+            assert all(len(step) == views and all(len(s) == 27 for s in step) for step in track["systems"])
+            assert len(track["poses"]) == views and all(len(p) == 16 for p in track["poses"])
+            # the last update is the one that ended the loop; the oracle's own distance from the truth
+            assert np.linalg.norm(np.float32(track["updates"][-1])) < 1e-6 <= np.linalg.norm(np.float32(track["updates"][-2]))
+            assert track["error"] < 5e-7 and track["rigidity"] < 5e-7

@@ -5,7 +5,8 @@ pool's single-GPU boxes do not have: both ranks use the one GPU (RCCL refuses th
 vk_comm_exchange_create / vk_comm_exchange_attach_handles), each loop kernel capped to a part of the device so that
 both are resident together (vk_test_hooks.loop_grid_cap). Three Tracks; the poses must equal — bit for bit — those of
 the reduce-hook path (the systems added by a gloo all-reduce between launches), and the last update must be the same
-on both ranks. If the two loops cannot be resident together the kernels give up after two seconds (VK_TRACK_ABORTED)
+on both ranks. The cameras stand at 0 and 90 degrees and both paths run the rig's increment (vk.h "THE RIG'S INCREMENT";
+the hook path by DepthTracker.rig_increment): every pose is also held to the rig oracle's, tests/golden/rig_views.json. If the two loops cannot be resident together the kernels give up after two seconds (VK_TRACK_ABORTED)
 and the test says so instead of hanging."""
 import json
 import os
@@ -51,5 +52,12 @@ def test_two_processes_exchange_through_mapped_areas():
         assert r["update_identical_on_all_ranks"], r
         assert r["sequence_after"] == 4                       # three Tracks from 1
         assert r["pose_error_after_track"] < 5e-4
+        # against the rig's oracle (tests/golden/rig_views.json): every Track of both paths within the project's bound
+        # for a free-running Track (2e-5 per entry, tests/test_gpu_parity.py)
+        print("rank", r["rank"], "hook path - fixture", r["hook_pose_minus_fixture"], "exchange path - fixture",
+              r["rig_pose_minus_fixture"], "steps", r["rig_steps"], "fixture", r["fixture_steps"])
+        assert len(r["hook_pose_minus_fixture"]) == len(r["rig_pose_minus_fixture"]) == 3
+        assert all(d <= 2e-5 for d in r["hook_pose_minus_fixture"]), r
+        assert all(d <= 2e-5 for d in r["rig_pose_minus_fixture"]), r
         assert all(2 <= s <= 20 for s in r["rig_steps"])
     assert results[0]["rig_steps"] == results[1]["rig_steps"]  # the same solve: the same number of steps

@@ -80,6 +80,7 @@ _SIGNATURES = {
     "vk_icp_workspace_floats": ([_I, _I], _SZ),
     "vk_icp_compute_system": ([_P, _P, _P, _P, _P, _I, _P, _P, _P, _P], _I),
     "vk_icp_solve_update": ([_P, _P, _I, _P, _P, _P, _P], _I),
+    "vk_icp_solve_update_rig": ([_P, _P, _I, _P, _P, _P, _P], _I),
     "vk_icp_track": ([_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_transform_upload": ([_P, _P, _P], _I),
     "vk_icp_pyramid_floats": ([_I, _I, _I, _I], _SZ),
@@ -89,6 +90,7 @@ _SIGNATURES = {
     "vk_reduce_nothing": ([_P, _I, _P, _P], _I),
     "vk_rig_area_bytes": ([], _SZ),
     "vk_icp_track_rig": ([_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_icp_track_rig_hook": ([_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_color_tracker_begin": ([_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P], _I),
     "vk_frame_downsample": ([_P, _P, _P, _P, _P], _I),
     "vk_volume_set_view_prepare": ([_P, _P, _P, _P], _I),
@@ -887,6 +889,10 @@ class DepthTracker(_PollMixin):
         self.update = torch.zeros(6, dtype=torch.float32, device=device)
         self.workspace = None
         self.reduce_hook = None              # e.g. an all-reduce over ranks
+        # True: this tracker is one camera of a rigid rig whose systems the hook (reduce_hook or comm) adds over the
+        # ranks, and the solve applies the rig's pose-independent increment (vk_icp_track_rig_hook, vk.h "THE RIG'S
+        # INCREMENT"). False: ApplyUpdate as upstream has it, whatever the hook does — a hook alone makes no rig
+        self.rig_increment = False
 
     @staticmethod
     def _view(frame):
@@ -941,11 +947,16 @@ class DepthTracker(_PollMixin):
         self.state.zero_()
         # one C call: the whole loop is one launch (with a reduce hook: 3 launches per step,
         # enqueuing stops once the loop has converged)
-        check(lib().vk_icp_track(_ref(self._view(self.keyframe)), _ref(self.keyframe.depth_to_world),
-                                 _ref(self._view(frame)), _ptr(self.pose), self.max_iterations,
-                                 int(self.translation_enabled), _ptr(self._workspace(frame)), _ptr(self.system),
-                                 _ptr(self.state), _ptr(self.update), *self._c_hook(), self._poll(), stream()),
-              "vk_icp_track")
+        hook, hook_user = self._c_hook()
+        rig = bool(self.rig_increment)
+        if rig and self.comm is None and self.reduce_hook is None:
+            raise ValueError("rig_increment needs the hook that adds the rig's systems (reduce_hook or comm)")
+        name = "vk_icp_track_rig_hook" if rig else "vk_icp_track"
+        check(getattr(lib(), name)(_ref(self._view(self.keyframe)), _ref(self.keyframe.depth_to_world),
+                                   _ref(self._view(frame)), _ptr(self.pose), self.max_iterations,
+                                   int(self.translation_enabled), _ptr(self._workspace(frame)), _ptr(self.system),
+                                   _ptr(self.state), _ptr(self.update), hook, hook_user, self._poll(), stream()),
+              name)
         out = self._wait_pose()
         frame.depth_to_world = out
         return out
@@ -953,7 +964,8 @@ class DepthTracker(_PollMixin):
 
 def track_rig(tracker, frame, exchange):
     """vk_icp_track_rig: DepthTracker::Track of one camera of a rigid rig, the ranks' normal systems
-    added inside the one-launch loop through `exchange` (a T.RigExchange, vulcan_amd.comm)."""
+    added inside the one-launch loop through `exchange` (a T.RigExchange, vulcan_amd.comm). With more than
+    one rank the library applies the rig's increment; a rig of one rank is vk_icp_track."""
     check(lib().vk_transform_upload(_ptr(tracker.pose), _ref(frame.depth_to_world), stream()), "vk_transform_upload")
     tracker.state.zero_()
     check(lib().vk_icp_track_rig(_ref(tracker._view(tracker.keyframe)), _ref(tracker.keyframe.depth_to_world),

@@ -131,7 +131,12 @@ class Communicator:
         return system
 
     def track(self, tracker, frame):
+        """DepthTracker::Track on the rig with the ranks' systems added by the C hook between launches. With more than
+        one rank the tracker runs the rig's increment (DepthTracker.rig_increment, vk_icp_track_rig_hook); a
+        communicator of one rank leaves the tracker as it is."""
         tracker.comm = self
+        if self.world > 1 and hasattr(tracker, "rig_increment"):
+            tracker.rig_increment = True
         return tracker.track(frame)
 
     # -- the exchange inside the one-launch loop (vk_rig_exchange, vk_icp_track_rig)
@@ -177,7 +182,8 @@ class Communicator:
         """DepthTracker::Track on the rig with the ranks' sums exchanged inside the launch; every rank calls it
         for the same Track. The sequence number moves on HERE, on every rank, whether the Track ended with a pose or
         with VK_TRACK_ABORTED (vk_rig_protocol.h rig_next_sequence): a retry never meets the aborted attempt's words
-        under their own tags, and the ranks' numbers cannot drift apart."""
+        under their own tags, and the ranks' numbers cannot drift apart. With more than one rank the library applies
+        the rig's increment (vk_icp_track_rig, vk.h), with one it is vk_icp_track."""
         from . import api
         if self.exchange is None:
             self.attach_exchange()

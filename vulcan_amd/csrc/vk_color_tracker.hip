@@ -562,6 +562,7 @@ struct ColorStep
 {
   static constexpr bool kTranslation = TRANSLATION;
   static constexpr int kSign12 = -1;       // a proper skew matrix (tinc_element)
+  static constexpr bool kRig = false;      // a skew Tinc needs no rig form: the colour trackers do not bend a rig
   float* twd;        // LDS, depth_to_world: matrix, inverse
   float* pose;       // LDS, Tcm: matrix, inverse
   float* fixed_m;    // LDS, frame_Tcd.m, key_Twc.m: indexed per lane by the wave-wide products

@@ -595,12 +595,22 @@ __device__ __forceinline__ void wave_solve_step(const float* sums, float* scratc
 // element (lane & 15) of M = Tinc(update) * base, and `update` in every lane; the new pose is
 // rigid_from(M). `base`: LDS, 16 floats (the depth tracker's pose matrix, the colour trackers'
 // depth_to_world^-1); `scratch`: LDS, 64 floats. One whole wave.
-template <int N, int SIGN12>
+//
+// RIG (next to SIGN12, and like it a property of the tracker's step: Step::kRig): the increment of a camera of a rigid
+// multi-camera rig, M = D(update) * base with D = rigid_from(Tinc) — Gram-Schmidt of Tinc ALONE. With SIGN12 = +1 Tinc is
+// no rotation to first order, and what rigid_from(Tinc * base) makes of its symmetric part depends on `base`: applied to
+// the cameras of a rig, one update becomes a different world-frame motion per camera and the rig bends (docs/rounds/r08.md).
+// D does not depend on the pose. Instantiated for the rig's Tracks only (vk_icp_track_rig with world > 1,
+// vk_icp_track_rig_hook, vk_icp_solve_update_rig); every other step is the RIG = false code, unchanged.
+__device__ __forceinline__ float wave_rigid_from(float M_lane, float* scratch);
+
+template <int N, int SIGN12, bool RIG = false>
 __device__ __forceinline__ float wave_pose_step(const float* sums, const float* base, float* scratch, float (&update)[6])
 {
   const int lane = lane_id();
   wave_solve_step<N>(sums, scratch, update);
-  const float tinc = tinc_element<SIGN12>(update, lane & 15);
+  float tinc = tinc_element<SIGN12>(update, lane & 15);
+  if constexpr (RIG) tinc = wave_rigid_from(tinc, scratch);
   if (lane < 16) scratch[lane] = tinc;
   wave_lds_fence();
   const float M_lane = matmul4_lane(scratch, base, lane);     // Tinc * base
@@ -610,7 +620,7 @@ __device__ __forceinline__ float wave_pose_step(const float* sums, const float* 
 
 // The same step for the launch-per-stage solve kernels (solve_update_kernel, color_solve_kernel: one
 // wave): the system and the matrix Tinc multiplies come from memory, and every lane gets the whole of M.
-template <int N, int SIGN12>
+template <int N, int SIGN12, bool RIG = false>
 __device__ __forceinline__ void staged_pose_step(const float* hessian, const float* gradient, const float* base,
     float (&M)[16], float (&update)[6])
 {
@@ -620,7 +630,7 @@ __device__ __forceinline__ void staged_pose_step(const float* hessian, const flo
   if (lane < N) sums[36 + lane] = gradient[lane];
   if (lane < 16) matrix[lane] = base[lane];
   wave_lds_fence();
-  const float M_lane = wave_pose_step<N, SIGN12>(sums, matrix, scratch, update);
+  const float M_lane = wave_pose_step<N, SIGN12, RIG>(sums, matrix, scratch, update);
   if (lane < 16) matrix[lane] = M_lane;
   wave_lds_fence();
 #pragma unroll
@@ -727,6 +737,7 @@ __device__ __forceinline__ void finish_step(const float (&update)[6], int32_t* s
 // vk_color_tracker.hip), THREADS wide. P: the tracker's image parameters; L: its loop parameters
 // (exchange, iterations, state, mirror, ... by name). What is a tracker's own comes from its step:
 //   kTranslation, kSign12   N = 6 or 3; the sign of Tinc(1,2) (tinc_element)
+//   kRig                    the step applies the rig's pose-independent increment (wave_pose_step)
 //   pose                    LDS, 16 floats: the matrix the pixels are evaluated at
 //   base                    LDS, 16 floats: the matrix Tinc multiplies
 //   ends_at_start(L)        a launch that must not start (after the converged test)
@@ -800,7 +811,7 @@ __device__ __forceinline__ void gauss_newton_loop(const Params& P, const Loop& L
       // solve + pose update across the lanes of the first wave. The pixels only ever need `pose`; the rest
       // of the pose (a second 4x4 product per step or more) is made once, after the loop, from the last M.
       float update[6];
-      const float M_lane = wave_pose_step<N, Step::kSign12>(sums, S.base, solve_scratch, update);
+      const float M_lane = wave_pose_step<N, Step::kSign12, Step::kRig>(sums, S.base, solve_scratch, update);
       const float next = S.advance(wave_rigid_from(M_lane, solve_scratch), solve_scratch);
       float sq = 0.0f;
 #pragma unroll

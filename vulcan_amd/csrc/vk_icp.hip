@@ -308,12 +308,13 @@ __global__ __launch_bounds__(256) void system_final_kernel(const float* __restri
 
 // ref: tracker.cpp:124-163 + depth_tracker.cpp:22-86. One wave solves and makes M = Tinc(update) * old
 // pose matrix (staged_pose_step); lane 0 re-orthonormalises it and writes pose, state and update.
-template <int N>
+// RIG: M = rigid_from(Tinc(update)) * old pose matrix, the increment of a camera of a rigid rig (wave_pose_step).
+template <int N, bool RIG>
 __device__ __forceinline__ void solve_update(const float* hessian, const float* gradient,
     vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
 {
   float update[6], M[16], out_m[16], out_i[16];
-  staged_pose_step<N, +1>(hessian, gradient, Twc->m, M, update);
+  staged_pose_step<N, +1, RIG>(hessian, gradient, Twc->m, M, update);
   if (threadIdx.x != 0) return;
   rigid_from(M, out_m, out_i);
 #pragma unroll
@@ -325,8 +326,18 @@ __global__ __launch_bounds__(64) void solve_update_kernel(const float* __restric
     int translation_enabled, vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
 {
   if (state && state[1]) return;  // converged earlier: tracker.cpp:162 (the same answer in every lane)
-  if (translation_enabled) solve_update<6>(hessian, gradient, Twc, state, update_out, mirror);
-  else solve_update<3>(hessian, gradient, Twc, state, update_out, mirror);
+  if (translation_enabled) solve_update<6, false>(hessian, gradient, Twc, state, update_out, mirror);
+  else solve_update<3, false>(hessian, gradient, Twc, state, update_out, mirror);
+}
+
+// the stage solve of a rig's Track (vk_icp_solve_update_rig, vk_icp_track_rig_hook): a kernel of its own, so that
+// solve_update_kernel stays the instantiation plain tracking has always run
+__global__ __launch_bounds__(64) void solve_update_rig_kernel(const float* __restrict__ hessian, const float* __restrict__ gradient,
+    int translation_enabled, vk_transform* Twc, int32_t* state, float* update_out, Mirror mirror)
+{
+  if (state && state[1]) return;
+  if (translation_enabled) solve_update<6, true>(hessian, gradient, Twc, state, update_out, mirror);
+  else solve_update<3, true>(hessian, gradient, Twc, state, update_out, mirror);
 }
 
 // ---- the whole Gauss-Newton loop in one launch (gauss_newton_loop, vk_gauss_newton.hpp) ----
@@ -351,11 +362,12 @@ struct LoopParams
 
 // The depth tracker's part of a step: the pose matrix in LDS is what the pixels use and what
 // Tinc multiplies (depth_tracker.cpp:33-53); its inverse is made once, after the loop.
-template <bool TRANSLATION>
+template <bool TRANSLATION, bool RIG = false>
 struct DepthStep
 {
   static constexpr bool kTranslation = TRANSLATION;
   static constexpr int kSign12 = +1;       // Tinc(1,2) = +update[0] (tinc_element)
+  static constexpr bool kRig = RIG;        // a rig of more than one camera: the pose-independent increment (wave_pose_step)
   float* pose;
   const float* base;
   bool resident;
@@ -444,6 +456,16 @@ __global__ __launch_bounds__(kIcpThreads) void track_loop_kernel(IcpParams P, Lo
 {
   __shared__ float pose_m[16];
   DepthStep<TRANSLATION> step(pose_m);
+  gauss_newton_loop<kIcpThreads>(P, L, step);
+}
+
+// the same loop for a rank of a rig of more than one camera (vk_icp_track_rig, world > 1): a kernel of its own,
+// track_loop_kernel stays the instantiation plain tracking runs
+template <bool TRANSLATION>
+__global__ __launch_bounds__(kIcpThreads) void track_loop_rig_kernel(IcpParams P, LoopParams L)
+{
+  __shared__ float pose_m[16];
+  DepthStep<TRANSLATION, true> step(pose_m);
   gauss_newton_loop<kIcpThreads>(P, L, step);
 }
 
@@ -665,6 +687,10 @@ int launch_track_loop(const IcpParams& P, vk_transform* Twc_dev, int iterations,
   L.mirror = mirror;
   memset(&L.rig, 0, sizeof(L.rig));
   if (rig) L.rig = *rig;
+  if (rig && rig->world > 1)          // the cameras of a rig move by one pose-independent increment (DepthStep::kRig)
+    return translation_enabled
+        ? launch_loop(track_loop_rig_kernel<true>, kIcpThreads, P, L, iterations, fresh_state, ends_track, workspace, s)
+        : launch_loop(track_loop_rig_kernel<false>, kIcpThreads, P, L, iterations, fresh_state, ends_track, workspace, s);
   return translation_enabled
       ? launch_loop(track_loop_kernel<true>, kIcpThreads, P, L, iterations, fresh_state, ends_track, workspace, s)
       : launch_loop(track_loop_kernel<false>, kIcpThreads, P, L, iterations, fresh_state, ends_track, workspace, s);
@@ -744,10 +770,11 @@ int vk_icp_compute_system(const vk_icp_view* keyframe, const vk_transform* Twm,
   return VK_OK;
 }
 
-int vk_icp_track(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_icp_view* frame,
+// vk_icp_track and, with `rig_increment`, vk_icp_track_rig_hook
+static int icp_track(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_icp_view* frame,
     vk_transform* Twc_dev, int iterations, int translation_enabled, float* workspace, float* system,
     int32_t* state_dev, float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user,
-    const vk_track_poll* poll, void* stream)
+    const vk_track_poll* poll, void* stream, bool rig_increment)
 {
   IcpParams P;
   const vk_transform identity = identity_transform();
@@ -765,9 +792,28 @@ int vk_icp_track(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_
       Twc_dev, stream,
       [&](hipStream_t s) { launch_partials(P, translation_enabled, partials, workspace, s); },
       [&](hipStream_t s) {
-        hipLaunchKernelGGL(solve_update_kernel, dim3(1), dim3(64), 0, s, system, system + 36, translation_enabled,
-            Twc_dev, state_dev, update_dev, mirror);
+        hipLaunchKernelGGL(rig_increment ? solve_update_rig_kernel : solve_update_kernel, dim3(1), dim3(64), 0, s, system,
+            system + 36, translation_enabled, Twc_dev, state_dev, update_dev, mirror);
       });
+}
+
+int vk_icp_track(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_icp_view* frame,
+    vk_transform* Twc_dev, int iterations, int translation_enabled, float* workspace, float* system,
+    int32_t* state_dev, float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user,
+    const vk_track_poll* poll, void* stream)
+{
+  return icp_track(keyframe, Twm, frame, Twc_dev, iterations, translation_enabled, workspace, system, state_dev, update_dev,
+      reduce, reduce_user, poll, stream, /*rig_increment*/ false);
+}
+
+int vk_icp_track_rig_hook(const vk_icp_view* keyframe, const vk_transform* Twm, const vk_icp_view* frame,
+    vk_transform* Twc_dev, int iterations, int translation_enabled, float* workspace, float* system,
+    int32_t* state_dev, float* update_dev, vk_icp_reduce_fn reduce, void* reduce_user,
+    const vk_track_poll* poll, void* stream)
+{
+  VK_REQUIRE(reduce);     // the rig's sums come through the hook; without one there is no rig (vk_icp_track)
+  return icp_track(keyframe, Twm, frame, Twc_dev, iterations, translation_enabled, workspace, system, state_dev, update_dev,
+      reduce, reduce_user, poll, stream, /*rig_increment*/ true);
 }
 
 // the pose travels in the dispatch packet: no staging copy, no host synchronisation
@@ -970,6 +1016,16 @@ int vk_icp_solve_update(const float* hessian, const float* gradient, int transla
 {
   VK_REQUIRE(hessian && gradient && Twc_dev);
   hipLaunchKernelGGL(solve_update_kernel, dim3(1), dim3(64), 0, vk_s(stream), hessian, gradient,
+      translation_enabled, Twc_dev, state_dev, update_dev, Mirror{nullptr, 0, nullptr});
+  VK_LAUNCH_CHECK();
+  return VK_OK;
+}
+
+int vk_icp_solve_update_rig(const float* hessian, const float* gradient, int translation_enabled,
+    vk_transform* Twc_dev, int32_t* state_dev, float* update_dev, void* stream)
+{
+  VK_REQUIRE(hessian && gradient && Twc_dev);
+  hipLaunchKernelGGL(solve_update_rig_kernel, dim3(1), dim3(64), 0, vk_s(stream), hessian, gradient,
       translation_enabled, Twc_dev, state_dev, update_dev, Mirror{nullptr, 0, nullptr});
   VK_LAUNCH_CHECK();
   return VK_OK;

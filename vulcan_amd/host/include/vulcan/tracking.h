@@ -44,6 +44,10 @@ class Tracker
     // Multi-GPU rigs: called between ComputeSystem and the solve with the packed
     // device system (48 floats: hessian[36], gradient[6], pad[6]); the hook
     // all-reduces it in place on the compute stream.
+    // The hooked Track of this layer runs the CAMERA form of the pose update
+    // (vk_icp_track: ApplyUpdate as upstream has it), which moves a rig as one
+    // body only if its cameras are parallel or opposed; the rig's increment
+    // (vk.h "THE RIG'S INCREMENT", vk_icp_track_rig_hook) has no switch here yet.
     typedef void (*ReduceHook)(float* system_device, int count, void* user);
     void SetReduceHook(ReduceHook hook, void* user);
 
