@@ -1280,6 +1280,61 @@ VK_API size_t vk_volume_release_workspace_bytes(int32_t main_block_count, int32_
 VK_API int vk_volume_release_blocks(const vk_volume* v, const vk_release_rule* rule,
     int32_t* counts_dev /* [4] */, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------- merge -- */
+
+enum { VK_MERGE_SKIP_UNOBSERVED = 1, VK_MERGE_CONTINUE = 2 };
+
+typedef struct vk_merge_params {
+  int32_t flags;                /* VK_MERGE_* or'ed */
+  int32_t max_rounds;           /* >= 1 */
+  float   max_distance_weight;  /* 1 .. 32767 */
+  float   max_color_weight;     /* 1 .. 32767 */
+} vk_merge_params;
+
+/* Fuse volume `src` into volume `dst`: allocate in dst the blocks of src it lacks, then continue every voxel's running
+ * average with the source's value and weight — in one call, nothing read back, the result independent of timing. No
+ * upstream counterpart (its Volume is a process-wide singleton, src/volume.cu:17-21); ref: src/volume.cu:304-368 for the
+ * allocation (HandleAllocationRequests, reused as it is), src/depth_integrator.cu:55-59 and
+ * src/color_integrator.cu:109-118 for the running average (there the new sample has weight 1, here the source voxel's).
+ * The definition is this comment; tests/merge_reference.py states it on the CPU and the device is held to it bit for bit.
+ * PRECONDITIONS (the caller's duty; the class layers enforce them): both volumes are between SetView calls —
+ * allocation_types all NONE, no frame announced (vk_requests_ahead); src is only read. Checked on the host, VK_ERR_ARGUMENT
+ * with no device touched: a null argument or buffer, dst->voxels == src->voxels, voxel_length or truncation_length not
+ * bitwise equal, a voxel pool not 16-byte aligned, an unknown flag, max_rounds < 1, a cap outside 1 .. 32767.
+ * main_block_count and excess_block_count may differ between the two.
+ * (source blocks) an entry of src that is reachable from a main bucket along `next` and has data >= 0. With
+ * SKIP_UNOBSERVED a block all of whose 512 voxels have distance_weight == 0 and color_weight == 0 is ignored: neither
+ * requested nor fused (one extra read of the allocated part of the source pool).
+ * (presence) a block is present in dst when the chain of its bucket hash(origin) % dst->main_block_count holds an entry
+ * with data >= 0 and that origin. The empty main entry does not stand in for block (0,0,0).
+ * (allocation) at most max_rounds rounds. In a round every considered block that is absent posts one request in its dst
+ * bucket: VK_ALLOC_MAIN if that main entry has data == -1, else VK_ALLOC_EXCESS; the bucket goes to the largest key
+ * (type << 48 | z << 32 | y << 16 | x, the coordinates as uint16: what SetView's request pass writes, with pad = type);
+ * a MAIN request sets the bucket's block_visibility to TRUE (volume.cu:193-200). Then one handle pass, exactly
+ * vk_volume_handle_allocation_requests (exhaustion included: leaked slots, never-written excess entries). The rounds end
+ * with a round that posts nothing — it runs no handle pass — and after a round whose handle pass raised VK_CTR_DROPPED.
+ * (fusion) for every considered block present in dst after the rounds, voxel i of the source block into voxel i of the
+ * dst block, fp32, one rounding per operation, no contraction, IEEE division. If s.distance_weight != 0: wd =
+ * (float)d.distance_weight, ws = (float)s.distance_weight, sum = wd + ws; d.distance = wd == 0 ? s.distance :
+ * (wd * d.distance + ws * s.distance) / sum; d.distance_weight = (int16_t)fminf(max_distance_weight, sum). If
+ * s.color_weight != 0: the same per colour channel with the colour weights and max_color_weight. A field whose source
+ * weight is 0 keeps its bytes. Blocks still absent are left out. Each call fuses what it finds present: the same pair
+ * merged twice counts the source twice.
+ * (CONTINUE) `workspace` is the one the previous call for this pair left, neither volume's table has been changed
+ * since by anything but that call: the blocks that call left out are the considered blocks of this one (SKIP_UNOBSERVED
+ * has no further effect), what it fused is not fused again. A merge split into calls this way runs the same rounds and
+ * leaves the same state as one call with the rounds of all of them.
+ * (afterwards) VK_CTR_VISIBLE = 0, VK_CTR_BANDED = -1: the caller's next SetView rebuilds the visible list; VK_CTR_REQUESTS
+ * is the last handle pass's; anything prepared ahead for dst is VOID as after vk_volume_release_blocks. counts_dev:
+ * device int32[6] = {source blocks considered, blocks fused, blocks allocated by the call, source blocks left out,
+ * rounds that posted a request, source blocks skipped as unobserved}. workspace: device,
+ * vk_volume_merge_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's). 5 + 4 * max_rounds
+ * short launches on `stream` and one pass of one wave per source block over the two voxel pools. Moving a replica
+ * between devices is the caller's: both volumes' buffers are on the stream's device. */
+VK_API size_t vk_volume_merge_workspace_bytes(int32_t src_main, int32_t src_excess);
+VK_API int vk_volume_merge(const vk_volume* dst, const vk_volume* src, const vk_merge_params* p,
+    int32_t* counts_dev /* [6] */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

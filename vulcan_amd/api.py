@@ -119,6 +119,8 @@ _SIGNATURES = {
     "vk_extract_mesh_attributes": ([_P, _I, _I, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P], _I),
     "vk_volume_release_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_volume_release_blocks": ([_P, _P, _P, _P, _P], _I),
+    "vk_volume_merge_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
+    "vk_volume_merge": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -504,6 +506,48 @@ class Volume:
         check(lib().vk_volume_release_blocks(_ref(self.desc()), _ref(rule), _ptr(self._release_counts),
                                              _ptr(self._release_workspace), stream()), "vk_volume_release_blocks")
         return tuple(int(c) for c in self._release_counts.cpu().numpy())
+
+    _merge_workspace = None     # device bytes of vk_volume_merge, per source size, allocated by the first merge
+    _merge_counts = None
+
+    def _merge_call(self, other, flags, max_rounds, max_distance_weight, max_color_weight):
+        """one vk_volume_merge(self <- other): the six counts from one blocking read"""
+        import torch
+        self._no_requests_pending("merge")
+        other._no_requests_pending("merge")
+        size = (other.main, other.excess)
+        if self._merge_workspace is None or self._merge_workspace[0] != size:
+            if flags & T.VK_MERGE_CONTINUE:
+                raise VkError("merge: nothing to continue")
+            self._merge_workspace = (size, _dev_bytes(lib().vk_volume_merge_workspace_bytes(*size), self.device))
+            self._merge_counts = torch.zeros(6, dtype=torch.int32, device=self.device)
+        params = T.MergeParams(int(flags), int(max_rounds), float(max_distance_weight), float(max_color_weight))
+        self._view_changed()
+        if self.light_prep is not None:
+            self.light_prep.valid = 0
+        check(lib().vk_volume_merge(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(self._merge_counts),
+                                    _ptr(self._merge_workspace[1]), stream()), "vk_volume_merge")
+        return tuple(int(c) for c in self._merge_counts.cpu().numpy())
+
+    def merge(self, other, max_distance_weight=16, max_color_weight=16, skip_unobserved=False, max_rounds=8):
+        """vk_volume_merge (not upstream): fuse the volume `other` — same voxel and truncation length, on this device,
+        any bucket and pool size — into this one. The blocks this volume lacks are allocated (`max_rounds` rounds of
+        requests and handle pass per call), then every voxel's running average goes on with the other voxel's value and
+        weight, the weights capped as an integrator's are. `skip_unobserved`: blocks of `other` that no voxel was ever
+        integrated into are left where they are. Each block of `other` is fused once: while a call posted requests in
+        every round, dropped none and still left blocks out, the merge goes on with another call for those
+        (VK_MERGE_CONTINUE). Between SetView calls only: raises while either volume has a frame announced. `other` is
+        only read. The visible list is empty afterwards (the next set_view rebuilds it) and what was prepared ahead
+        for this volume is void. Returns (source blocks considered, fused, allocated, left out — the pool or the excess
+        list ran out —, rounds that posted a request, source blocks skipped as unobserved)."""
+        flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
+        dropped = int(self.read_counters()[T.VK_CTR_DROPPED])
+        counts = self._merge_call(other, flags, max_rounds, max_distance_weight, max_color_weight)
+        considered, fused, allocated, left_out, rounds, skipped = counts
+        while counts[4] == int(max_rounds) and counts[3] > 0 and int(self.read_counters()[T.VK_CTR_DROPPED]) == dropped:
+            counts = self._merge_call(other, flags | T.VK_MERGE_CONTINUE, max_rounds, max_distance_weight, max_color_weight)
+            fused, allocated, left_out, rounds = fused + counts[1], allocated + counts[2], counts[3], rounds + counts[4]
+        return considered, fused, allocated, left_out, rounds, skipped
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

@@ -56,6 +56,25 @@ struct ReleaseCounts
   int free_slots;       // pool slots free afterwards
 };
 
+// Not upstream: how Volume::Merge fuses another volume into this one (vk_merge_params)
+struct MergeOptions
+{
+  float max_distance_weight = 16.0f;  // the caps an integrator would apply (integrator.cu:7-13)
+  float max_color_weight = 16.0f;
+  bool skip_unobserved = false;       // leave out the source blocks no voxel of which was ever integrated
+  int max_rounds = 8;                 // allocation rounds per call of vk_volume_merge
+};
+
+struct MergeCounts
+{
+  int considered;       // blocks of the other volume the merge looked at
+  int fused;            // of those, fused into this volume
+  int allocated;        // blocks this volume did not have before
+  int left_out;         // blocks that found no room: the pool or the excess list ran out
+  int rounds;           // allocation rounds that posted a request
+  int skipped;          // blocks of the other volume skipped as unobserved
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -115,6 +134,15 @@ class Volume
     // One blocking readback (the four counts).
     ReleaseCounts ReleaseBlocks(const ReleaseRule& rule);
 
+    // Not upstream (its Volume is a process-wide singleton, src/volume.cu:17-21): fuse `other` — same voxel and truncation
+    // length, on this device, any bucket and pool size — into this volume (vk_volume_merge). The blocks this volume lacks
+    // are allocated, then every voxel's running average goes on with the other voxel's value and weight; every block of
+    // `other` is fused once, in as many calls of the entry point as its allocation rounds take. `other` is only read.
+    // Between SetView calls only: throws while either volume has a frame announced by Tracer::Trace(keyframe, next_frame).
+    // The visible list is empty afterwards (the next SetView rebuilds it); the raycast bounds and the light preparation
+    // made ahead are void. Blocking readbacks (the six counts, VK_CTR_DROPPED).
+    MergeCounts Merge(const Volume& other, const MergeOptions& options = MergeOptions());
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -172,6 +200,8 @@ class Volume
     Buffer<int> counters_;
     Buffer<unsigned char> release_workspace_;   // ReleaseBlocks: allocated by the first call
     Buffer<int> release_counts_;
+    Buffer<unsigned char> merge_workspace_;     // Merge: allocated by the first call, again for a source of another size
+    Buffer<int> merge_counts_;
 
     Vector2f depth_range_;
     int max_block_count_;

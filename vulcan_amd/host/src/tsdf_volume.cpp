@@ -355,6 +355,55 @@ ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
   return out;
 }
 
+MergeCounts Volume::Merge(const Volume& other, const MergeOptions& options)
+{
+  const char* announced = "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first";
+  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, announced);
+  VULCAN_ASSERT_MSG(other.requests_ahead_.valid != 1, announced);
+  VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
+  vk_merge_params p;
+  p.flags = options.skip_unobserved ? VK_MERGE_SKIP_UNOBSERVED : 0;
+  p.max_rounds = options.max_rounds;
+  p.max_distance_weight = options.max_distance_weight;
+  p.max_color_weight = options.max_color_weight;
+  const size_t bytes = vk_volume_merge_workspace_bytes(other.main_block_count_, other.excess_block_count_);
+  if (merge_workspace_.GetSize() != bytes) merge_workspace_.Resize(bytes);
+  if (merge_counts_.GetSize() == 0) merge_counts_.Resize(6);
+  // what was made ahead for the old table and visible list is void
+  view_bounds_.valid = 0;
+  light_prep_.valid = 0;
+  const vk_volume dst = ToVk(), src = other.ToVk();
+  int32_t counters[VK_CTR_PUBLIC];
+  GetCounters(counters);
+  const int32_t dropped = counters[VK_CTR_DROPPED];
+  MergeCounts out;
+  for (bool first = true;; first = false)
+  {
+    VK_ASSERT(vk_volume_merge(&dst, &src, &p, merge_counts_.GetData(), merge_workspace_.GetData(), Device::GetStream()));
+    int32_t counts[6];
+    merge_counts_.CopyToHost(counts);
+    if (first)
+    {
+      out.considered = counts[0];
+      out.skipped = counts[5];
+      out.fused = out.allocated = out.rounds = 0;
+    }
+    out.fused += counts[1];
+    out.allocated += counts[2];
+    out.left_out = counts[3];
+    out.rounds += counts[4];
+    // every block once: while a call posted in all its rounds, dropped nothing and still left blocks out, the next
+    // call goes on with those
+    GetCounters(counters);
+    if (!(counts[4] == p.max_rounds && counts[3] > 0 && counters[VK_CTR_DROPPED] == dropped)) break;
+    p.flags |= VK_MERGE_CONTINUE;
+  }
+  NotePoolExhaustion(counters[VK_CTR_DROPPED]);
+  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
+  visible_count_stale_ = false;
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");

@@ -24,6 +24,7 @@ VISIBILITY_UNKNOWN, VISIBILITY_FALSE, VISIBILITY_TRUE = 0, 1, 2
 ALLOC_NONE, ALLOC_MAIN, ALLOC_EXCESS = 0, 1, 2
 BLOCK_RESOLUTION, BLOCK_VOXELS, PATCH_MAX_SIZE = 8, 512, 16
 VK_RELEASE_UNOBSERVED, VK_RELEASE_NO_SURFACE, VK_RELEASE_OUTSIDE_BOX = 1, 2, 4   # vk_release_rule.flags
+VK_MERGE_SKIP_UNOBSERVED, VK_MERGE_CONTINUE = 1, 2                               # vk_merge_params.flags
 
 voxel_dtype = np.dtype([("distance", "<f4"), ("color", "<f4", (3,)),
                         ("distance_weight", "<i2"), ("color_weight", "<i2")])
@@ -202,6 +203,11 @@ class RequestsAhead(C.Structure):
 class ReleaseRule(C.Structure):
     """vk_release_rule (vk.h): which blocks vk_volume_release_blocks gives back; flags 0 = repair only"""
     _fields_ = [("flags", C.c_int32), ("min_abs_distance", C.c_float), ("keep_lo", C.c_int16 * 3), ("keep_hi", C.c_int16 * 3)]
+
+
+class MergeParams(C.Structure):
+    """vk_merge_params (vk.h): how vk_volume_merge fuses one volume into another"""
+    _fields_ = [("flags", C.c_int32), ("max_rounds", C.c_int32), ("max_distance_weight", C.c_float), ("max_color_weight", C.c_float)]
 
 
 class PyramidAhead(C.Structure):
