@@ -1335,6 +1335,59 @@ VK_API size_t vk_volume_merge_workspace_bytes(int32_t src_main, int32_t src_exce
 VK_API int vk_volume_merge(const vk_volume* dst, const vk_volume* src, const vk_merge_params* p,
     int32_t* counts_dev /* [6] */, void* workspace, void* stream);
 
+/* ----------------------------------------------------------- merge through a pose -- */
+
+typedef struct vk_merge_pose_params {
+  vk_merge_params merge;        /* flags (SKIP_UNOBSERVED, CONTINUE), max_rounds, the two caps: as vk_volume_merge */
+  vk_transform    pose;         /* T_dst_src: x_dst = m * x_src, metres; m and inv are both used as given */
+} vk_merge_pose_params;
+
+/* Fuse volume `src` into volume `dst` through a rigid pose: the two volumes need not share a world frame or a voxel
+ * lattice, every dst voxel takes a trilinear sample of src at its own centre carried back into src's frame. What
+ * vk_volume_merge leaves out ("resampling"). No upstream counterpart (its Volume is a process-wide singleton,
+ * src/volume.cu:17-21); ref: src/volume.cu:304-368 for the allocation, src/depth_integrator.cu:55-59 and
+ * src/color_integrator.cu:109-118 for the running average, oracle_integrate.c:12-15 for a voxel's centre (there in metres).
+ * The definition is this comment;
+ * tests/merge_pose_reference.py states it on the CPU and the device is held to it bit for bit. All arithmetic is fp32,
+ * one rounding per operation, no contraction, IEEE division.
+ * PRECONDITIONS and host checks: vk_volume_merge's, and every one of the 24 entries of rows 0-2 of pose.m and pose.inv is
+ * finite, else VK_ERR_ARGUMENT with no device touched. That m is rigid and inv its inverse is the caller's duty (the
+ * class layers build both from one Transform); with anything else the call stays inside its buffers and ends, and the
+ * counts of blocks may count a block more than once.
+ * (coordinates) voxel units. Voxel (x,y,z) of block B has centre c_a = (float)(8 B_a + i_a) + 0.5f; tm_a = m[12+a] /
+ * voxel_length, ti_a = inv[12+a] / voxel_length; fwd(c)_a = ((m[a] c_0 + m[4+a] c_1) + m[8+a] c_2) + tm_a, back(c) the
+ * same with inv and ti. Stored distances are in truncation lengths, which the volumes share: values are not rescaled.
+ * (source blocks) vk_volume_merge's, SKIP_UNOBSERVED included.
+ * (candidates) for a considered source block with origin o: the corners (float)(8 o_a + 8 s_a), s in {0,1}^3, through
+ * fwd; lo_a = (int)floorf(min_a * 0.125f), hi_a = (int)floorf(max_a * 0.125f) (fminf / fmaxf; the conversion saturates,
+ * NaN gives 0; both are then clamped to +-40000, which changes no block inside the int16 range), hi_a capped at lo_a + 2.
+ * A block B in [lo, hi]^3 with every coordinate in the int16 range is a candidate of o if and only if it has a voxel
+ * whose cell = floorf(back(c)) has 8 o_a <= cell_a <= 8 o_a + 7 on all three axes. The candidates of the call are the
+ * union over the considered source blocks, each dst block once.
+ * (allocation) vk_volume_merge's rounds with the candidates in the place of the source blocks: presence by the chain
+ * walk, one request per bucket and round, MAIN or EXCESS, the largest key wins, a MAIN request sets visibility TRUE, one
+ * vk_volume_handle_allocation_requests per round, the same two ends of the rounds.
+ * (fusion) for every candidate present after the rounds, every voxel: p = back(c), g_a = p_a - 0.5f, b_a = floorf(g_a),
+ * f_a = g_a - b_a. The lattice point b + s, s in {0,1}^3, is USED iff for every axis s_a == 0 or f_a != 0. Lattice point
+ * n is voxel (n mod 8) — index z*64 + y*8 + x — of source block floor(n / 8), found by the chain walk (absent when a
+ * coordinate leaves the int16 range). A distance sample exists iff every USED point's block is present and its
+ * distance_weight != 0; its value is the lerp a + f * (b - a) (sub, mul, add) along x, then y, then z, an axis with
+ * f == 0 taking its base value; its weight ws is (float) of the smallest distance_weight over the USED points. A colour
+ * sample likewise, per channel, with color_weight. Each sample continues the voxel's running average as vk_volume_merge
+ * does with a source voxel of that value and weight; a field without a sample keeps its bytes. A candidate that receives
+ * no sample at all stays allocated and Voxel::Empty(): vk_volume_release_blocks(VK_RELEASE_UNOBSERVED) gives such blocks
+ * back. One wave writes a dst block; no atomic touches a voxel.
+ * (CONTINUE) `workspace` is the previous call's for this pair and pose, no table changed since but by that call: the call
+ * considers the same source blocks and the same candidates, passes over the candidates already fused, and with the
+ * earlier calls runs the rounds and leaves the state of one call with as many rounds.
+ * (afterwards) as vk_volume_merge. counts_dev: device int32[8] = {source blocks considered, candidate dst blocks (of a
+ * CONTINUE call: those not fused before), candidates fused, blocks allocated by the call, candidates left out, rounds
+ * that posted, source blocks skipped as unobserved (0 in a CONTINUE call), voxels that took a distance sample}.
+ * workspace: device, vk_volume_merge_posed_workspace_bytes(...) bytes (0 for sizes that are not a volume's). */
+VK_API size_t vk_volume_merge_posed_workspace_bytes(int32_t src_main, int32_t src_excess, int32_t dst_main, int32_t dst_excess);
+VK_API int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_merge_pose_params* p,
+    int32_t* counts_dev /* [8] */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

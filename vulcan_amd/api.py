@@ -121,6 +121,8 @@ _SIGNATURES = {
     "vk_volume_release_blocks": ([_P, _P, _P, _P, _P], _I),
     "vk_volume_merge_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_volume_merge": ([_P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_merge_posed_workspace_bytes": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32], _SZ),
+    "vk_volume_merge_posed": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -529,7 +531,43 @@ class Volume:
                                     _ptr(self._merge_workspace[1]), stream()), "vk_volume_merge")
         return tuple(int(c) for c in self._merge_counts.cpu().numpy())
 
-    def merge(self, other, max_distance_weight=16, max_color_weight=16, skip_unobserved=False, max_rounds=8):
+    _merge_pose_workspace = None    # device bytes of vk_volume_merge_posed, per pair of sizes
+    _merge_pose_counts = None
+
+    def _merge_posed_call(self, other, pose, flags, max_rounds, max_distance_weight, max_color_weight):
+        """one vk_volume_merge_posed(self <- other through `pose`, a T.Transform): the eight counts from one blocking read"""
+        import torch
+        self._no_requests_pending("merge")
+        other._no_requests_pending("merge")
+        size = (other.main, other.excess, self.main, self.excess)
+        if self._merge_pose_workspace is None or self._merge_pose_workspace[0] != size:
+            if flags & T.VK_MERGE_CONTINUE:
+                raise VkError("merge: nothing to continue")
+            self._merge_pose_workspace = (size, _dev_bytes(lib().vk_volume_merge_posed_workspace_bytes(*size), self.device))
+            self._merge_pose_counts = torch.zeros(8, dtype=torch.int32, device=self.device)
+        params = T.MergePoseParams(T.MergeParams(int(flags), int(max_rounds), float(max_distance_weight), float(max_color_weight)), pose)
+        self._view_changed()
+        if self.light_prep is not None:
+            self.light_prep.valid = 0
+        check(lib().vk_volume_merge_posed(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(self._merge_pose_counts),
+                                          _ptr(self._merge_pose_workspace[1]), stream()), "vk_volume_merge_posed")
+        return tuple(int(c) for c in self._merge_pose_counts.cpu().numpy())
+
+    def _merge_posed(self, other, pose, max_distance_weight, max_color_weight, skip_unobserved, max_rounds):
+        if not isinstance(pose, T.Transform):
+            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))      # the inverse once, on the host
+        flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
+        dropped = int(self.read_counters()[T.VK_CTR_DROPPED])
+        counts = self._merge_posed_call(other, pose, flags, max_rounds, max_distance_weight, max_color_weight)
+        considered, candidates, fused, allocated, left_out, rounds, skipped, sampled = counts
+        while counts[5] == int(max_rounds) and counts[4] > 0 and int(self.read_counters()[T.VK_CTR_DROPPED]) == dropped:
+            counts = self._merge_posed_call(other, pose, flags | T.VK_MERGE_CONTINUE, max_rounds, max_distance_weight, max_color_weight)
+            fused, allocated, left_out = fused + counts[2], allocated + counts[3], counts[4]
+            rounds, sampled = rounds + counts[5], sampled + counts[7]
+        return considered, candidates, fused, allocated, left_out, rounds, skipped, sampled
+
+    def merge(self, other, pose=None, max_distance_weight=16, max_color_weight=16, skip_unobserved=False, max_rounds=8):
         """vk_volume_merge (not upstream): fuse the volume `other` — same voxel and truncation length, on this device,
         any bucket and pool size — into this one. The blocks this volume lacks are allocated (`max_rounds` rounds of
         requests and handle pass per call), then every voxel's running average goes on with the other voxel's value and
@@ -539,7 +577,14 @@ class Volume:
         (VK_MERGE_CONTINUE). Between SetView calls only: raises while either volume has a frame announced. `other` is
         only read. The visible list is empty afterwards (the next set_view rebuilds it) and what was prepared ahead
         for this volume is void. Returns (source blocks considered, fused, allocated, left out — the pool or the excess
-        list ran out —, rounds that posted a request, source blocks skipped as unobserved)."""
+        list ran out —, rounds that posted a request, source blocks skipped as unobserved).
+        `pose` (a 4x4 array or a Transform, T_self_other in metres): the two volumes do not share a frame or a lattice —
+        vk_volume_merge_posed: every voxel of the blocks of this volume that `other`'s blocks reach takes a trilinear
+        sample of `other`. Returns (source blocks considered, candidate blocks, candidates fused, blocks allocated,
+        candidates left out, rounds that posted, source blocks skipped as unobserved, voxels that took a distance
+        sample); a candidate no sample reaches stays allocated and empty (release_blocks(unobserved=True) frees those)."""
+        if pose is not None:
+            return self._merge_posed(other, pose, max_distance_weight, max_color_weight, skip_unobserved, max_rounds)
         flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
         dropped = int(self.read_counters()[T.VK_CTR_DROPPED])
         counts = self._merge_call(other, flags, max_rounds, max_distance_weight, max_color_weight)

@@ -16,6 +16,7 @@
 #include <vk.h>
 #include <vulcan/buffer.h>
 #include <vulcan/matrix.h>
+#include <vulcan/transform.h>
 
 namespace vulcan
 {
@@ -73,6 +74,19 @@ struct MergeCounts
   int left_out;         // blocks that found no room: the pool or the excess list ran out
   int rounds;           // allocation rounds that posted a request
   int skipped;          // blocks of the other volume skipped as unobserved
+};
+
+// Volume::Merge through a pose (vk_volume_merge_posed's eight counts, summed over the calls the rounds take)
+struct MergePoseCounts
+{
+  int considered;       // blocks of the other volume the merge looked at
+  int candidates;       // blocks of this volume those reach through the pose
+  int fused;            // of those, sampled into
+  int allocated;        // blocks this volume did not have before
+  int left_out;         // candidates that found no room: the pool or the excess list ran out
+  int rounds;           // allocation rounds that posted a request
+  int skipped;          // blocks of the other volume skipped as unobserved
+  int sampled;          // voxels that took a distance sample
 };
 
 class Block;
@@ -142,6 +156,11 @@ class Volume
     // The visible list is empty afterwards (the next SetView rebuilds it); the raycast bounds and the light preparation
     // made ahead are void. Blocking readbacks (the six counts, VK_CTR_DROPPED).
     MergeCounts Merge(const Volume& other, const MergeOptions& options = MergeOptions());
+    // ... through the rigid pose Tdst_src (x in this volume's frame = Tdst_src * x in `other`'s, metres): the two need not
+    // share a world frame or a voxel lattice (vk_volume_merge_posed). Every voxel of the blocks of this volume that `other`'s
+    // blocks reach takes a trilinear sample of `other` at its own centre carried back; a reached block no sample falls into
+    // stays allocated and empty (ReleaseBlocks with `unobserved` gives those back). Otherwise as Merge(other).
+    MergePoseCounts Merge(const Volume& other, const Transform& Tdst_src, const MergeOptions& options = MergeOptions());
 
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
@@ -202,6 +221,8 @@ class Volume
     Buffer<int> release_counts_;
     Buffer<unsigned char> merge_workspace_;     // Merge: allocated by the first call, again for a source of another size
     Buffer<int> merge_counts_;
+    Buffer<unsigned char> merge_pose_workspace_;   // Merge through a pose: again for another pair of sizes
+    Buffer<int> merge_pose_counts_;
 
     Vector2f depth_range_;
     int max_block_count_;

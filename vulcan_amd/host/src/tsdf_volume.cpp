@@ -404,6 +404,59 @@ MergeCounts Volume::Merge(const Volume& other, const MergeOptions& options)
   return out;
 }
 
+MergePoseCounts Volume::Merge(const Volume& other, const Transform& Tdst_src, const MergeOptions& options)
+{
+  const char* announced = "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first";
+  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, announced);
+  VULCAN_ASSERT_MSG(other.requests_ahead_.valid != 1, announced);
+  VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
+  vk_merge_pose_params p;
+  p.merge.flags = options.skip_unobserved ? VK_MERGE_SKIP_UNOBSERVED : 0;
+  p.merge.max_rounds = options.max_rounds;
+  p.merge.max_distance_weight = options.max_distance_weight;
+  p.merge.max_color_weight = options.max_color_weight;
+  p.pose = Tdst_src.ToVk();                       // the matrix and its inverse, from the one Transform
+  const size_t bytes = vk_volume_merge_posed_workspace_bytes(other.main_block_count_, other.excess_block_count_,
+      main_block_count_, excess_block_count_);
+  if (merge_pose_workspace_.GetSize() != bytes) merge_pose_workspace_.Resize(bytes);
+  if (merge_pose_counts_.GetSize() == 0) merge_pose_counts_.Resize(8);
+  // what was made ahead for the old table and visible list is void
+  view_bounds_.valid = 0;
+  light_prep_.valid = 0;
+  const vk_volume dst = ToVk(), src = other.ToVk();
+  int32_t counters[VK_CTR_PUBLIC];
+  GetCounters(counters);
+  const int32_t dropped = counters[VK_CTR_DROPPED];
+  MergePoseCounts out;
+  for (bool first = true;; first = false)
+  {
+    VK_ASSERT(vk_volume_merge_posed(&dst, &src, &p, merge_pose_counts_.GetData(), merge_pose_workspace_.GetData(), Device::GetStream()));
+    int32_t counts[8];
+    merge_pose_counts_.CopyToHost(counts);
+    if (first)
+    {
+      out.considered = counts[0];
+      out.candidates = counts[1];
+      out.skipped = counts[6];
+      out.fused = out.allocated = out.rounds = out.sampled = 0;
+    }
+    out.fused += counts[2];
+    out.allocated += counts[3];
+    out.left_out = counts[4];
+    out.rounds += counts[5];
+    out.sampled += counts[7];
+    // every candidate once: while a call posted in all its rounds, dropped nothing and still left candidates out, the
+    // next call goes on with those
+    GetCounters(counters);
+    if (!(counts[5] == p.merge.max_rounds && counts[4] > 0 && counters[VK_CTR_DROPPED] == dropped)) break;
+    p.merge.flags |= VK_MERGE_CONTINUE;
+  }
+  NotePoolExhaustion(counters[VK_CTR_DROPPED]);
+  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
+  visible_count_stale_ = false;
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");

@@ -210,6 +210,11 @@ class MergeParams(C.Structure):
     _fields_ = [("flags", C.c_int32), ("max_rounds", C.c_int32), ("max_distance_weight", C.c_float), ("max_color_weight", C.c_float)]
 
 
+class MergePoseParams(C.Structure):
+    """vk_merge_pose_params (vk.h): vk_merge_params, and the pose T_dst_src that vk_volume_merge_posed samples through"""
+    _fields_ = [("merge", MergeParams), ("pose", Transform)]
+
+
 class PyramidAhead(C.Structure):
     """vk_pyramid_ahead (vk.h): ABI 7's record of the retired pyramid ride; the library leaves it invalid"""
     _fields_ = [("key_depths", C.c_void_p), ("key_normals", C.c_void_p), ("frame_depths", C.c_void_p), ("frame_normals", C.c_void_p),
