@@ -1388,6 +1388,72 @@ VK_API size_t vk_volume_merge_posed_workspace_bytes(int32_t src_main, int32_t sr
 VK_API int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_merge_pose_params* p,
     int32_t* counts_dev /* [8] */, void* workspace, void* stream);
 
+/* ------------------------------------------------------- register volume to volume -- */
+
+typedef struct vk_register_params {
+  int32_t flags;             /* 0; reserved, anything else VK_ERR_ARGUMENT */
+  int32_t iterations;        /* 1 .. 64 */
+  float   max_abs_distance;  /* band, in truncation lengths: 0 < band <= 1 */
+  int32_t pad;
+} vk_register_params;
+
+#define VK_REGISTER_NO_OVERLAP 2   /* state_dev[1]: a step found no residual */
+
+/* Refine the rigid pose T_dst_src between two volumes — the pose vk_volume_merge_posed takes — by Gauss-Newton on the two
+ * TSDFs themselves: every source voxel near the surface is carried into dst, dst's field is sampled there, and the pose
+ * moves so that the sample equals the voxel's own distance. It REFINES a guess that already brings the two surfaces
+ * within roughly a truncation length of each other where they overlap; it searches nothing, and a periodic scene locks
+ * on to the nearest period. No upstream counterpart; ref: src/tracker.cpp:124-163 for the loop and its end,
+ * src/color_tracker.cpp:45-95 for the step. The definition is this comment; tests/register_reference.py states it on the
+ * CPU. All arithmetic is fp32, one rounding per operation, no contraction, IEEE division.
+ * ACCESS: both volumes are only read; dst == src is allowed; the table sizes may differ.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): a null argument or buffer (update_dev alone may be null), a volume
+ * that vk_volume_merge would refuse for its sizes or alignment, voxel_length or truncation_length not bitwise equal
+ * between the two, flags != 0, iterations outside 1 .. 64, the band not in (0, 1] (a NaN included).
+ * The pose is on the device (vk_transform_upload seeds it). m is used as given; the solve rewrites m and inv together.
+ * (coordinates) vk_volume_merge_posed's: voxel i = z*64 + y*8 + x of block B has centre c_a = (float)(8 B_a + i_a) + 0.5f;
+ * tm_a = m[12+a] / voxel_length; fwd(c)_a = ((m[a] c_0 + m[4+a] c_1) + m[8+a] c_2) + tm_a.
+ * (source voxels) the source blocks are vk_volume_merge's: reachable from a main bucket along `next`, data >= 0. A source
+ * voxel s is IN BAND iff s.distance_weight != 0 and fabsf(s.distance) < band.
+ * (sample) p = fwd(c), g_a = p_a - 0.5f, b_a = floorf(g_a), f_a = g_a - b_a. The eight lattice points b + k, k in {0,1}^3,
+ * are voxels of dst found by the chain walk; a point is absent when a block coordinate leaves the int16 range. The sample
+ * exists iff all eight are present with distance_weight != 0 (the gradient needs both ends of every axis: there is no
+ * "used points" rule here). v[k], k = kx + 2 ky + 4 kz, are their distances; lerp(t,a,b) = a + t*(b - a) (sub, mul, add).
+ *   x00 = lerp(fx,v0,v1), x10 = lerp(fx,v2,v3), x01 = lerp(fx,v4,v5), x11 = lerp(fx,v6,v7)
+ *   y0 = lerp(fy,x00,x10), y1 = lerp(fy,x01,x11), D = lerp(fz,y0,y1)
+ *   gz = y1 - y0, gy = lerp(fz, x10 - x00, x11 - x01),
+ *   gx = lerp(fz, lerp(fy, v1 - v0, v3 - v2), lerp(fy, v5 - v4, v7 - v6))       (truncation lengths per voxel)
+ * (residual) exists iff the voxel is in band, the sample exists and fabsf(D) < band. Then r = D - s.distance, weight 1,
+ *   J0 = p1*gz - p2*gy, J1 = p2*gx - p0*gz, J2 = p0*gy - p1*gx      (x cross gradient in metres: the voxel length cancels)
+ *   J3 = gx*iv, J4 = gy*iv, J5 = gz*iv, iv = 1.0f / voxel_length computed once
+ * — the depth tracker's form (X x n, n); the unknown is a twist applied on the left of T_dst_src, in dst's frame.
+ * (system) system[0..21) is the packed lower triangle of sum J J^T, row-major as vk_icp_compute_system's, system[36..42)
+ * is sum J r, system[42] is sum r^2, the rest 0. The reduction has one fixed order that depends on the source's table
+ * sizes alone: the same inputs give the same bits every call. counts = {source blocks considered, source voxels in band,
+ * residuals, 0}.
+ * (step) the colour trackers' step: update = -H^-1 g by the library's LDL^T (the zero update for a rank-deficient system),
+ * M = Tinc(update) * m with the proper skew matrix, pose <- rigid_from(M), m and inv together; an update of six zeros
+ * leaves the pose's bytes alone (no re-orthonormalisation, no change of a zero's sign).
+ * state_dev = {steps run, code}, zeroed by the caller. code 0: running; 1: converged, |update| < 1e-6 (tracker.cpp:162; that
+ * step's pose is written like any other's); VK_REGISTER_NO_OVERLAP: a step whose residual count is 0 — it counts as a step,
+ * leaves the pose's bytes alone and writes a zero update.
+ * vk_volume_register enqueues `iterations` steps on `stream`, launch per stage (a residual pass, the sum, a one-wave solve),
+ * with no host round trip and nothing read back; nothing in it waits inside a launch, so it cannot hang a device. The
+ * source blocks are listed once per call. A stage that finds state_dev[1] != 0 returns at once, so system_dev and
+ * counts_dev hold the last evaluated step's values, those of the pose BEFORE that step's update.
+ * vk_volume_register_system: one evaluation at the pose. vk_volume_register_terms: for source pool slot q and voxel i,
+ * valid[q*512+i], residuals[q*512+i] and jacobians[(q*512+i)*6 ..], zeros where no residual exists; the three buffers
+ * hold (src main + excess) * 512 voxels.
+ * workspace: device, vk_volume_register_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's). */
+VK_API size_t vk_volume_register_workspace_bytes(int32_t src_main, int32_t src_excess);
+VK_API int vk_volume_register_terms(const vk_volume* dst, const vk_volume* src, const vk_transform* pose_dev,
+    const vk_register_params* p, float* residuals, float* jacobians, uint8_t* valid, void* workspace, void* stream);
+VK_API int vk_volume_register_system(const vk_volume* dst, const vk_volume* src, const vk_transform* pose_dev,
+    const vk_register_params* p, float* system_dev, int32_t* counts_dev, void* workspace, void* stream);
+VK_API int vk_volume_register(const vk_volume* dst, const vk_volume* src, vk_transform* pose_dev /* in: start, out: result */,
+    const vk_register_params* p, float* system_dev /* [48] */, int32_t* state_dev /* [2] */, int32_t* counts_dev /* [4] */,
+    float* update_dev /* optional [6] */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

@@ -1,0 +1,208 @@
+"""vk_volume_register on the device against its CPU statement (tests/register_reference.py). Both volumes start from uploaded
+oracle states. The per-voxel terms are one defined sequence of float32 operations and equal the statement's bit for bit;
+the sums are added in float32 in the device's own fixed order and are held to the bound the depth tracker's system is held
+to (test_icp_system: 2e-5 of the sum of the absolute terms); a pose after the loop is held to 2e-5 per entry, the project's
+standing bound for a tracked pose against the oracle."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import merge_pose_reference as MP
+import merge_reference as M
+import register_reference as RR
+import release_reference as R
+from test_gpu_parity import api, sync  # noqa: F401
+from test_gpu_release import device_copy
+from vulcan_amd import vk_types as T
+
+pytestmark = pytest.mark.gpu
+
+SAME, OTHER = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
+_LOOP = {}
+
+
+def statement_loop(orc):
+    """the statement's 20 steps from the identity to generic(): once"""
+    if "loop" not in _LOOP:
+        dst, src = RR.pair(orc, MP.generic())
+        _LOOP["loop"] = RR.register(orc, dst, src, T.Transform.identity(), iterations=20)
+    return _LOOP["loop"]
+
+
+def volumes(api, orc, truth, sizes=SAME, frames=(2, 3)):
+    hd, hs = RR.pair(orc, truth, sizes, frames)
+    return hd, hs, device_copy(api, hd), device_copy(api, hs)
+
+
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def assert_system(got, want, absolute):
+    """test_icp_system's rule"""
+    error = np.abs(got.astype(np.float64) - want)
+    bound = 2e-5 * absolute + 1e-12
+    print("system: worst error / bound", float((error / bound).max()))
+    assert (error <= bound).all()
+    assert not got[21:36].any() and not got[43:48].any()
+
+
+@pytest.mark.parametrize("sizes", [SAME, OTHER], ids=["long-chains", "other-bucket-count"])
+@pytest.mark.parametrize("pose", ["generic", "identity"])
+def test_terms_bit_for_bit(api, orc, sizes, pose):
+    hd, hs, dd, ds = volumes(api, orc, MP.generic(), sizes)
+    pose = MP.generic() if pose == "generic" else T.Transform.identity()
+    want = RR.terms(RR.Pair(hd, hs), pose, 0.75)
+    valid, residuals, jacobians = dd._register_terms_call(ds, pose, 0.75)
+    print("counts", want.counts, "valid on the device", int(valid.sum()))
+    assert want.counts[2] > 1000
+    assert np.array_equal(valid, want.valid)
+    assert same_bits(residuals, want.r)
+    assert same_bits(jacobians, want.J)
+
+
+@pytest.mark.parametrize("sizes", [SAME, OTHER], ids=["long-chains", "other-bucket-count"])
+def test_system(api, orc, sizes):
+    hd, hs, dd, ds = volumes(api, orc, MP.generic(), sizes)
+    evaluated = RR.terms(RR.Pair(hd, hs), MP.generic(), 0.75)
+    want, absolute = RR.system(evaluated)
+    got, counts = dd._register_system_call(ds, MP.generic(), 0.75)
+    print("counts", counts, evaluated.counts)
+    assert counts == evaluated.counts
+    assert_system(got, want, absolute)
+    again, counts_again = dd._register_system_call(ds, MP.generic(), 0.75)
+    assert again.tobytes() == got.tobytes() and counts_again == counts
+
+
+def test_loop_from_the_identity(api, orc):
+    want = statement_loop(orc)
+    hd, hs, dd, ds = volumes(api, orc, MP.generic())
+    pose, state, counts, system, _ = dd._register_call(ds, T.Transform.identity(), 20, 0.75)
+    print("state", state, "statement", want.steps, want.code, "counts", counts, want.counts)
+    print("pose: worst entry", float(np.abs(pose.matrix() - want.pose.matrix()).max()),
+          "inverse", float(np.abs(pose.inverse_matrix() - want.pose.inverse_matrix()).max()), "error", RR.pose_error(pose, MP.generic()))
+    assert state[1] == 1 and state[0] <= want.steps + 1
+    assert np.abs(pose.matrix() - want.pose.matrix()).max() <= 2e-5
+    assert np.abs(pose.inverse_matrix() - want.pose.inverse_matrix()).max() <= 2e-5
+    # the volumes are only read
+    assert dd.host_voxels().tobytes() == hd.voxels.tobytes() and ds.host_voxels().tobytes() == hs.voxels.tobytes()
+    assert np.array_equal(dd.host_entries(), hd.hash_entries) and np.array_equal(ds.host_entries(), hs.hash_entries)
+
+    # through the class, from a 4x4 array: the same call
+    result = dd.register(ds, pose=np.eye(4))
+    print(result)
+    assert bytes(result.pose) == bytes(pose) and (result.steps, result.converged, result.overlap) == (state[0], True, True)
+    assert result.residuals == counts[2] and result.rms == pytest.approx(np.sqrt(system[42] / counts[2]))
+    assert dd.register(ds).steps == state[0]                                         # no pose: the identity
+
+
+def test_three_steps(api, orc):
+    want = statement_loop(orc)
+    _, _, dd, ds = volumes(api, orc, MP.generic())
+    pose, state, _, _, _ = dd._register_call(ds, T.Transform.identity(), 3, 0.75)
+    after = want.poses[3]
+    print("state", state, "worst entry", float(np.abs(pose.matrix() - after.matrix()).max()))
+    assert state == (3, 0)
+    assert np.abs(pose.matrix() - after.matrix()).max() <= 2e-5
+    assert np.abs(pose.inverse_matrix() - after.inverse_matrix()).max() <= 2e-5
+
+
+def test_a_clone_is_already_registered(api, orc):
+    hd, _, dd, _ = volumes(api, orc, MP.generic())
+    clone = device_copy(api, hd)
+    start = T.Transform.identity()
+    pose, state, counts, system, update = dd._register_call(clone, start, 5, 0.75)
+    print("state", state, "counts", counts)
+    assert state == (1, 1) and counts[2] > 100000
+    assert not system[36:43].any() and not update.any()                              # the gradient, exactly
+    assert bytes(pose) == bytes(start)
+    # a volume against itself
+    pose, state, again, _, _ = dd._register_call(dd, start, 5, 0.75)
+    assert state == (1, 1) and again == counts and bytes(pose) == bytes(start)
+
+
+def test_a_block_shift_has_no_residual(api, orc):
+    shift = MP.shift((8, -16, 0))
+    _, _, dd, ds = volumes(api, orc, shift, frames=(2, 2))
+    system, counts = dd._register_system_call(ds, shift, 0.75)
+    print("counts", counts, "sum of squares", float(system[42]))
+    assert counts[2] > 100000 and float(system[42]) == 0.0
+
+
+def test_the_band(api, orc):
+    hd, hs, dd, ds = volumes(api, orc, MP.generic())
+    counts = {}
+    for band in (0.5, 0.75):
+        _, counts[band] = dd._register_system_call(ds, MP.generic(), band)
+        assert counts[band] == RR.terms(RR.Pair(hd, hs), MP.generic(), band).counts
+    print(counts)
+    assert 0 < counts[0.5][2] < counts[0.75][2] and 0 < counts[0.5][1] < counts[0.75][1]
+
+
+@pytest.mark.parametrize("metres", [10.0, 3000.0], ids=["apart", "beyond-the-block-range"])
+def test_no_overlap(api, orc, metres):
+    _, _, dd, ds = volumes(api, orc, MP.generic())
+    start = T.Transform.translate(metres, 0.0, 0.0) * MP.generic()
+    pose, state, counts, _, update = dd._register_call(ds, start, 5, 0.75)
+    print("state", state, "counts", counts)
+    assert state == (1, T.VK_REGISTER_NO_OVERLAP) and counts[0] == 722 and counts[1] > 0 and counts[2:] == (0, 0)
+    assert bytes(pose) == bytes(start) and not update.any()
+    result = dd.register(ds, pose=start)
+    assert not result.overlap and not result.converged and result.residuals == 0 and bytes(result.pose) == bytes(start)
+
+
+def test_an_empty_source(api, orc):
+    hd, _, dd, _ = volumes(api, orc, MP.generic())
+    empty = device_copy(api, M.fresh(orc, 509, 4096))
+    pose, state, counts, _, _ = dd._register_call(empty, MP.generic(), 5, 0.75)
+    assert state == (1, T.VK_REGISTER_NO_OVERLAP) and counts == (0, 0, 0, 0) and bytes(pose) == bytes(MP.generic())
+
+
+def test_register_then_merge(api, orc):
+    """the registered pose merges as the true pose does: the voxels that take a distance sample differ by less than 2 % (a
+    cap that catches a wrong pose; the statement's pose gives 213 716 against 213 721 on the CPU)"""
+    hd, _, dd, ds = volumes(api, orc, MP.generic())
+    result = dd.register(ds)
+    assert result.converged
+    registered = dd.merge(ds, pose=result.pose)
+    truth = device_copy(api, hd).merge(ds, pose=MP.generic())
+    print(registered, truth, result)
+    assert registered[4] == 0 and abs(registered[7] - truth[7]) < 0.02 * truth[7]
+
+
+def test_arguments_are_checked_on_the_host(api, orc):
+    hd, hs, dd, ds = volumes(api, orc, MP.generic())
+    b, good = dd._register_setup(ds, T.Transform.identity(), 20, 0.75)
+    sync()
+    lib = api.lib()
+
+    def call(dst, src, params=good, pose="pose", system="system", state="state", counts="counts", workspace="workspace"):
+        at = lambda name: None if name is None else C.c_void_p(b[name].data_ptr())   # noqa: E731
+        return lib.vk_volume_register(C.byref(dst) if dst else None, C.byref(src) if src else None, at(pose), C.byref(params) if params else None,
+                                      at(system), at(state), at(counts), at("update"), at(workspace), api.stream())
+
+    def changed(volume, **fields):
+        desc = volume.desc()
+        for name, value in fields.items():
+            setattr(desc, name, value)
+        return desc
+
+    d, s = dd.desc(), ds.desc()
+    assert call(None, s) == -1 and call(d, None) == -1 and call(d, s, params=None) == -1
+    for name in ("pose", "system", "state", "counts", "workspace"):
+        assert call(d, s, **{name: None}) == -1
+    assert call(changed(dd, voxels=None), s) == -1 and call(d, changed(ds, hash_entries=None)) == -1
+    assert call(d, changed(ds, voxel_length=0.005)) == -1 and call(d, changed(ds, truncation_length=0.05)) == -1
+    for bad in (T.RegisterParams(1, 20, 0.75, 0), T.RegisterParams(0, 0, 0.75, 0), T.RegisterParams(0, 65, 0.75, 0),
+                T.RegisterParams(0, 20, 0.0, 0), T.RegisterParams(0, 20, 1.5, 0), T.RegisterParams(0, 20, float("nan"), 0)):
+        assert call(d, s, params=bad) == -1
+    one = C.c_void_p(b["system"].data_ptr())
+    assert lib.vk_volume_register_system(C.byref(d), C.byref(s), one, C.byref(good), None, one, one, api.stream()) == -1
+    assert lib.vk_volume_register_terms(C.byref(d), C.byref(s), one, C.byref(good), one, one, None, one, api.stream()) == -1
+    assert lib.vk_volume_register_workspace_bytes(0, 8) == 0 and lib.vk_volume_register_workspace_bytes(8, -1) == 0
+    sync()
+    assert dd.host_voxels().tobytes() == hd.voxels.tobytes() and ds.host_voxels().tobytes() == hs.voxels.tobytes()
+    assert np.array_equal(dd.host_entries(), hd.hash_entries) and np.array_equal(ds.host_entries(), hs.hash_entries)
+    assert call(d, s, params=T.RegisterParams(0, 64, 1.0, 0)) == 0                   # the ends of the ranges are inside
+    sync()

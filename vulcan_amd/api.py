@@ -123,6 +123,10 @@ _SIGNATURES = {
     "vk_volume_merge": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_volume_merge_posed_workspace_bytes": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32], _SZ),
     "vk_volume_merge_posed": ([_P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_register_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
+    "vk_volume_register_terms": ([_P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_register_system": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_register": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -330,6 +334,17 @@ class Frame:
                                      f32(k.cx) * f32(0.5), f32(k.cy) * f32(0.5))
         return Frame(depth, half(self.depth_projection), self.depth_to_world, color, normals,
                      half(self.color_projection), self.depth_to_color, self.device)
+
+
+class Registration:
+    """what Volume.register returns"""
+
+    def __init__(self, pose, steps, converged, overlap, residuals, rms):
+        self.pose, self.steps, self.converged, self.overlap, self.residuals, self.rms = pose, steps, converged, overlap, residuals, rms
+
+    def __repr__(self):
+        return (f"Registration(steps={self.steps}, converged={self.converged}, overlap={self.overlap}, "
+                f"residuals={self.residuals}, rms={self.rms:.3g})")
 
 
 class Volume:
@@ -593,6 +608,72 @@ class Volume:
             counts = self._merge_call(other, flags | T.VK_MERGE_CONTINUE, max_rounds, max_distance_weight, max_color_weight)
             fused, allocated, left_out, rounds = fused + counts[1], allocated + counts[2], counts[3], rounds + counts[4]
         return considered, fused, allocated, left_out, rounds, skipped
+
+    _register_buffers = None    # device buffers of vk_volume_register, per source size
+
+    def _register_setup(self, other, pose, iterations, band):
+        """the device buffers of a registration against `other`, the start pose uploaded: (buffers, vk_register_params)"""
+        import torch
+        size = (other.main, other.excess)
+        if self._register_buffers is None or self._register_buffers["size"] != size:
+            self._register_buffers = {
+                "size": size, "workspace": _dev_bytes(lib().vk_volume_register_workspace_bytes(*size), self.device),
+                "pose": _dev_bytes(C.sizeof(T.Transform), self.device), "system": torch.zeros(48, dtype=torch.float32, device=self.device),
+                "state": torch.zeros(2, dtype=torch.int32, device=self.device), "counts": torch.zeros(4, dtype=torch.int32, device=self.device),
+                "update": torch.zeros(6, dtype=torch.float32, device=self.device)}
+        b = self._register_buffers
+        check(lib().vk_transform_upload(_ptr(b["pose"]), _ref(pose), stream()), "vk_transform_upload")
+        return b, T.RegisterParams(0, int(iterations), float(band), 0)
+
+    def _register_terms_call(self, other, pose, band):
+        """vk_volume_register_terms at `pose` (a T.Transform): (valid, residuals, jacobians [.., 6]) per pool slot and voxel of `other`"""
+        import torch
+        b, params = self._register_setup(other, pose, 1, band)
+        voxels = (other.main + other.excess) * 512
+        valid = torch.empty(voxels, dtype=torch.uint8, device=self.device)
+        residuals = torch.empty(voxels, dtype=torch.float32, device=self.device)
+        jacobians = torch.empty((voxels, 6), dtype=torch.float32, device=self.device)
+        check(lib().vk_volume_register_terms(_ref(self.desc()), _ref(other.desc()), _ptr(b["pose"]), _ref(params), _ptr(residuals),
+                                             _ptr(jacobians), _ptr(valid), _ptr(b["workspace"]), stream()), "vk_volume_register_terms")
+        return valid.cpu().numpy(), residuals.cpu().numpy(), jacobians.cpu().numpy()
+
+    def _register_system_call(self, other, pose, band):
+        """vk_volume_register_system at `pose`: (system[48], the four counts) from one blocking read each"""
+        b, params = self._register_setup(other, pose, 1, band)
+        check(lib().vk_volume_register_system(_ref(self.desc()), _ref(other.desc()), _ptr(b["pose"]), _ref(params), _ptr(b["system"]),
+                                              _ptr(b["counts"]), _ptr(b["workspace"]), stream()), "vk_volume_register_system")
+        return b["system"].cpu().numpy(), tuple(int(c) for c in b["counts"].cpu().numpy())
+
+    def _register_call(self, other, pose, iterations, band):
+        """one vk_volume_register from `pose` (a T.Transform): (pose, (steps, code), counts, system[48], update[6])"""
+        b, params = self._register_setup(other, pose, iterations, band)
+        b["state"].zero_()
+        check(lib().vk_volume_register(_ref(self.desc()), _ref(other.desc()), _ptr(b["pose"]), _ref(params), _ptr(b["system"]),
+                                       _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]), _ptr(b["workspace"]), stream()),
+              "vk_volume_register")
+        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
+        return (out, tuple(int(c) for c in b["state"].cpu().numpy()), tuple(int(c) for c in b["counts"].cpu().numpy()),
+                b["system"].cpu().numpy(), b["update"].cpu().numpy())
+
+    def register(self, other, pose=None, iterations=20, max_abs_distance=0.75):
+        """vk_volume_register (not upstream): refine the rigid pose T_self_other between this volume and `other` — same
+        voxel and truncation length, on this device, any bucket and pool size — by Gauss-Newton on the two TSDFs: every
+        voxel of `other` whose distance is within `max_abs_distance` truncation lengths of the surface is carried into
+        this volume and compared with the trilinear sample there. `pose` (a 4x4 array or a Transform, what merge(pose=)
+        accepts; None: the identity) is the guess to start from: it has to bring the two surfaces within roughly a
+        truncation length of each other where they overlap — this call refines, it does not search. Both volumes are
+        only read. At most `iterations` steps (1 .. 64), all enqueued at once; one blocking read at the end. Returns a
+        Registration: `pose` (the result; merge(other, pose=result.pose) fuses through it), `steps`, `converged`,
+        `overlap` (False: a step found no voxel to compare and the pose is the one it had then), `residuals` and `rms`
+        (in truncation lengths) of the last evaluated step."""
+        if pose is None:
+            pose = T.Transform.identity()
+        elif not isinstance(pose, T.Transform):
+            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        out, state, counts, system, _ = self._register_call(other, pose, iterations, max_abs_distance)
+        return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
+                            float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0)
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

@@ -19,9 +19,7 @@
 //   finish    the eight counts, VK_CTR_VISIBLE and VK_CTR_BANDED
 //   fuse      one wave per marked destination entry: the source footprint's slots once into an LDS directory, then the
 //             eight-point gather per voxel through it: the only pass over the two voxel pools
-#include "vk_requests.hpp"
-
-#include <math.h>
+#include "vk_block_walk.hpp"
 
 using namespace vk;
 
@@ -30,19 +28,16 @@ namespace
 
 constexpr int kWaveThreads = 256;                                      // four waves = four entries per workgroup
 constexpr int kWavesPerGroup = kWaveThreads / kWave;
-constexpr int kVoxelWords = (int)sizeof(vk_voxel) / 4;                 // 5 dwords: distance, colour, the two weights
 constexpr int kBoxBlocks = 27;                                         // a rigid pose spans at most 3 blocks per axis
 constexpr int kLanesPerEntry = 32;                                     // request pass: one lane per box block, 27 of 32
 constexpr int kFootprint = 4;                                          // source blocks per axis under one dst block
 constexpr int kCoordinateClamp = 40000;                                // beyond the int16 range: see block_box
-static_assert(sizeof(vk_voxel) == 20 && kFootprint * kFootprint * kFootprint == kWave, "Voxel layout, one lane per directory cell");
+static_assert(kFootprint * kFootprint * kFootprint == kWave, "one lane per directory cell");
 
 enum : uint8_t { kNone = 0, kConsidered = 1, kSkipped = 2 };            // a source entry
 enum : int32_t { kNoCandidate = 0, kCandidate = 1, kFused = 2 };        // a destination entry
 // the words that steer the rounds and carry the sums
 enum { cStop = 0, cPosted, cRounds, cSavedRequests, cDroppedBefore, cConsidered, cSkipped, cPresentBefore, cMarked, cAbsent, cWords = 16 };
-
-typedef uint32_t vu4 __attribute__((ext_vector_type(4), aligned(4)));   // a voxel's first 16 bytes, 4-byte aligned
 
 struct PoseParams
 {
@@ -58,24 +53,6 @@ struct PoseParams
   int32_t* ctl;                 // [cWords]
   int32_t* counts;              // [8] output
 };
-
-// sum over the wave, then one atomic: integer sums commute
-__device__ __forceinline__ void wave_add(int32_t* word, int value)
-{
-  for (int d = 32; d > 0; d >>= 1) value += __shfl_down(value, d);
-  if (lane_id() == 0 && value) atomicAdd(word, value);
-}
-
-__device__ __forceinline__ f3 apply(const float* r, float c0, float c1, float c2)
-{
-  return f3{((r[0] * c0 + r[1] * c1) + r[2] * c2) + r[3], ((r[4] * c0 + r[5] * c1) + r[6] * c2) + r[7],
-            ((r[8] * c0 + r[9] * c1) + r[10] * c2) + r[11]};
-}
-
-__device__ __forceinline__ bool in_int16(int x, int y, int z)
-{
-  return x >= -32768 && x <= 32767 && y >= -32768 && y <= 32767 && z >= -32768 && z <= 32767;
-}
 
 __device__ __forceinline__ int block_coordinate(float v)
 {
@@ -98,29 +75,6 @@ __device__ __forceinline__ void block_box(const float* r, int bx, int by, int bz
   hi[0] = vmini(block_coordinate(most.x), lo[0] + 2);
   hi[1] = vmini(block_coordinate(most.y), lo[1] + 2);
   hi[2] = vmini(block_coordinate(most.z), lo[2] + 2);
-}
-
-// the entry of block (bx, by, bz) in `v` by the chain walk of its bucket: an entry with data >= 0 and that origin (the
-// empty main entry does not stand in for block (0,0,0)); -1 when absent. `main_entry`: the bucket's, for the request.
-__device__ __forceinline__ int find_block(const vk_volume& v, int total, int bx, int by, int bz, int& slot, Entry& main_entry)
-{
-  const uint32_t bucket = block_hash(bx, by, bz, (uint32_t)v.main_block_count);
-  main_entry = load_entry(v.hash_entries, bucket);
-  Entry entry = main_entry;
-  int at = (int)bucket;
-  for (int guard = 0; guard < total; ++guard)
-  {
-    if (entry.data >= 0 && entry.data < total && entry_is(entry, bx, by, bz))
-    {
-      slot = entry.data;
-      return at;
-    }
-    at = entry.next;
-    if (at < 0 || at >= total) break;
-    entry = load_entry(v.hash_entries, (uint32_t)at);
-  }
-  slot = -1;
-  return -1;
 }
 
 // (the control words are zero: a memset in front of this launch)
@@ -322,28 +276,6 @@ __global__ void pose_finish_kernel(PoseParams P)
   P.dst.counters[VK_CTR_BANDED] = -1;           // the banded lists list nothing any more
 }
 
-struct Lattice
-{
-  int bx, by, bz;               // floorf(g)
-  float fx, fy, fz;             // g - floorf(g)
-};
-
-// where voxel (x, y, z) of dst block (ox, oy, oz) samples src. (The clamp keeps b + 1 an int; a rigid pose never nears it.)
-__device__ __forceinline__ Lattice lattice_of(const float* back, int ox, int oy, int oz, int x, int y, int z)
-{
-  const f3 p = apply(back, (float)(8 * ox + x) + 0.5f, (float)(8 * oy + y) + 0.5f, (float)(8 * oz + z) + 0.5f);
-  const float gx = p.x - 0.5f, gy = p.y - 0.5f, gz = p.z - 0.5f;
-  const float qx = floorf(gx), qy = floorf(gy), qz = floorf(gz);
-  constexpr int kFar = 1 << 30;
-  return Lattice{vclampi(f2i(qx), -kFar, kFar), vclampi(f2i(qy), -kFar, kFar), vclampi(f2i(qz), -kFar, kFar), gx - qx, gy - qy, gz - qz};
-}
-
-__device__ __forceinline__ int wave_min(int v)
-{
-  for (int d = 32; d > 0; d >>= 1) v = vmini(v, __shfl_xor(v, d));
-  return v;
-}
-
 __device__ __forceinline__ float lerp_axis(float f, float a, float b) { return f == 0.0f ? a : a + f * (b - a); }
 
 // x, then y, then z over the eight values v[s], s = sx + 2 sy + 4 sz
@@ -470,19 +402,6 @@ __global__ __launch_bounds__(kWaveThreads) void pose_fuse_kernel(PoseParams P)
   }
   wave_add(&P.counts[7], sampled);
   if (lane == 0) P.mark[at] = kFused;            // a call that continues passes over it
-}
-
-inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
-bool volume_ok(const vk_volume* v)
-{
-  return v && v->voxels && v->hash_entries && v->free_voxel_blocks && v->allocation_types && v->allocation_blocks &&
-         v->block_visibility && v->visible_blocks && v->counters && v->main_block_count > 0 && v->excess_block_count >= 0 &&
-         v->excess_block_count <= INT32_MAX - v->main_block_count && v->voxel_length > 0 && v->truncation_length > 0 &&
-         // what the handle pass asks of a volume (check_volume, vk_volume.hip): refused here, before anything is enqueued
-         (reinterpret_cast<uintptr_t>(v->counters) & 7) == 0 && (reinterpret_cast<uintptr_t>(v->allocation_blocks) & 7) == 0 &&
-         (reinterpret_cast<uintptr_t>(v->hash_entries) & 15) == 0 && (reinterpret_cast<uintptr_t>(v->voxels) & 15) == 0 &&
-         (reinterpret_cast<uintptr_t>(v->block_visibility) & 3) == 0 && (reinterpret_cast<uintptr_t>(v->allocation_types) & 15) == 0;
 }
 
 // rows 0-2 of a column-major 4x4, the translation in voxels; false when one of the twelve is not finite

@@ -89,6 +89,17 @@ struct MergePoseCounts
   int sampled;          // voxels that took a distance sample
 };
 
+// Volume::Register (vk_volume_register)
+struct Registration
+{
+  Transform pose;       // Tdst_src after the last step: what Merge(other, pose) takes
+  int steps;            // Gauss-Newton steps run
+  bool converged;       // the last step was shorter than 1e-6
+  bool overlap;         // false: a step found no voxel to compare; the pose is the one it had then
+  int residuals;        // voxels compared in the last evaluated step
+  float rms;            // sqrt(sum r^2 / residuals) of that step, in truncation lengths
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -161,6 +172,12 @@ class Volume
     // blocks reach takes a trilinear sample of `other` at its own centre carried back; a reached block no sample falls into
     // stays allocated and empty (ReleaseBlocks with `unobserved` gives those back). Otherwise as Merge(other).
     MergePoseCounts Merge(const Volume& other, const Transform& Tdst_src, const MergeOptions& options = MergeOptions());
+    // Not upstream: refine that pose from the two volumes themselves (vk_volume_register) — Gauss-Newton on the TSDFs,
+    // every voxel of `other` within `max_abs_distance` truncation lengths of the surface against the trilinear sample of
+    // this volume where `start` (then the refined pose) carries it. `start` has to bring the two surfaces within roughly
+    // a truncation length of each other where they overlap: the call refines a guess, it does not search. Both volumes
+    // are only read; at most `iterations` steps (1 .. 64), enqueued at once; blocking readbacks at the end.
+    Registration Register(const Volume& other, const Transform& start, int iterations = 20, float max_abs_distance = 0.75f);
 
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
@@ -223,6 +240,9 @@ class Volume
     Buffer<int> merge_counts_;
     Buffer<unsigned char> merge_pose_workspace_;   // Merge through a pose: again for another pair of sizes
     Buffer<int> merge_pose_counts_;
+    Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
+    Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
+    Buffer<int> register_ints_;                    // the state (2), the counts (4)
 
     Vector2f depth_range_;
     int max_block_count_;

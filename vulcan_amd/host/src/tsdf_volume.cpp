@@ -1,7 +1,9 @@
 // tsdf_volume.cpp — Volume host class over vk_volume_* (ref: src/volume.cu:370-627).
 #include <vulcan/tsdf_volume.h>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 #include <vulcan/block.h>
 #include <vulcan/exception.h>
 #include <vulcan/observation.h>
@@ -454,6 +456,43 @@ MergePoseCounts Volume::Merge(const Volume& other, const Transform& Tdst_src, co
   NotePoolExhaustion(counters[VK_CTR_DROPPED]);
   visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
   visible_count_stale_ = false;
+  return out;
+}
+
+Registration Volume::Register(const Volume& other, const Transform& start, int iterations, float max_abs_distance)
+{
+  vk_register_params p;
+  p.flags = 0;
+  p.iterations = iterations;
+  p.max_abs_distance = max_abs_distance;
+  p.pad = 0;
+  const size_t bytes = vk_volume_register_workspace_bytes(other.main_block_count_, other.excess_block_count_);
+  if (register_workspace_.GetSize() != bytes) register_workspace_.Resize(bytes);
+  if (register_floats_.GetSize() == 0) register_floats_.Resize(32 + 48 + 8);
+  if (register_ints_.GetSize() == 0) register_ints_.Resize(2 + 4);
+  vk_transform* pose = reinterpret_cast<vk_transform*>(register_floats_.GetData());
+  float* system = register_floats_.GetData() + 32;
+  float* update = system + 48;
+  int* state = register_ints_.GetData();
+  int* counts = state + 2;
+  const vk_transform seed = start.ToVk();
+  const vk_volume dst = ToVk(), src = other.ToVk();
+  VK_ASSERT(vk_transform_upload(pose, &seed, Device::GetStream()));
+  VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
+  VK_ASSERT(vk_volume_register(&dst, &src, pose, &p, system, state, counts, update, register_workspace_.GetData(), Device::GetStream()));
+  std::vector<float> floats(register_floats_.GetSize());
+  std::vector<int> ints(register_ints_.GetSize());
+  register_floats_.CopyToHost(floats.data());
+  register_ints_.CopyToHost(ints.data());
+  vk_transform result;
+  std::memcpy(&result, floats.data(), sizeof(result));
+  Registration out;
+  out.pose = Transform::FromVk(result);
+  out.steps = ints[0];
+  out.converged = ints[1] == 1;
+  out.overlap = ints[1] != VK_REGISTER_NO_OVERLAP;
+  out.residuals = ints[4];
+  out.rms = ints[4] > 0 ? std::sqrt(floats[32 + 42] / float(ints[4])) : 0.0f;
   return out;
 }
 
