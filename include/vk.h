@@ -1454,6 +1454,51 @@ VK_API int vk_volume_register(const vk_volume* dst, const vk_volume* src, vk_tra
     const vk_register_params* p, float* system_dev /* [48] */, int32_t* state_dev /* [2] */, int32_t* counts_dev /* [4] */,
     float* update_dev /* optional [6] */, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ sample -- */
+
+enum { VK_SAMPLE_VOXEL_UNITS = 1, VK_SAMPLE_DISTANCE_ONLY = 2 };
+
+typedef struct vk_sample_params {
+  int32_t flags;             /* VK_SAMPLE_*; an unknown bit is VK_ERR_ARGUMENT */
+  int32_t pad;
+} vk_sample_params;
+
+/* The volume's field at arbitrary points: for each of `count` points the trilinear sample of the stored voxels — signed
+ * distance, colour and the two weights, as a vk_voxel — and the gradient of the distance. What a planner, a collision
+ * check or a tool that rates a reconstruction asks of a TSDF map. No upstream counterpart (the reference samples its
+ * volume only along camera rays); ref: src/tracer.cu:238-299 for the trilinear sample of a ray, src/volume.cu:168-191 for
+ * the chain walk. The definition is this comment; tests/sample_reference.py states it on the CPU and the device is held
+ * to it bit for bit. All arithmetic is fp32, one rounding per operation, no contraction, IEEE division.
+ * ACCESS: the volume is only read. One launch on `stream`, nothing read back, no atomic and no wait on another workgroup:
+ * it cannot hang a device.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): v or p null, a volume that vk_volume_merge would refuse for its sizes
+ * or alignment, a flag other than the two, count < 0, points null with count > 0, samples and gradients both null,
+ * gradients not 16-byte aligned. count == 0 returns 0 and launches nothing.
+ * (coordinates) point i is x = points[3i .. 3i+2], in metres, in the frame that pose_dev carries into the volume's.
+ * q_a = x_a / voxel_length; with VK_SAMPLE_VOXEL_UNITS q = x and nothing is divided. With pose_dev == NULL p = q, else
+ * p = fwd(q) as vk_volume_merge_posed defines fwd: fwd(q)_a = ((m[a] q_0 + m[4+a] q_1) + m[8+a] q_2) + tm_a with
+ * tm_a = m[12+a] / voxel_length; inv is not read. The pose is read on the device (vk_transform_upload seeds one; a
+ * tracker's pose that never left the device can be handed in). A point with a non-finite component of p has no sample of
+ * any kind.
+ * (lattice) g_a = p_a - 0.5f, b_a = floorf(g_a), f_a = g_a - b_a; b is converted to int (saturating) and clamped to
+ * +-2^30. The lattice point n = b + s, s in {0,1}^3, is voxel (n mod 8) — index z*64 + y*8 + x — of block floor(n / 8),
+ * found by the chain walk; a point is absent when a block coordinate leaves the int16 range.
+ * (the sample, a vk_voxel) vk_volume_merge_posed's, word for word: b + s is USED iff for every axis s_a == 0 or
+ * f_a != 0; a distance sample exists iff every USED point is present with distance_weight != 0; its value is the lerp
+ * a + f * (b - a) (sub, mul, add) along x, then y, then z, an axis with f == 0 taking its base value; its
+ * distance_weight is the smallest distance_weight over the USED points. The colour likewise, per channel, with
+ * color_weight. A field without a sample is Voxel::Empty()'s: distance 1.0f (never 0: a caller who ignores the weight
+ * reads "far from any surface"), colour 0, weight 0. Distances are in truncation lengths, as stored. With
+ * VK_SAMPLE_DISTANCE_ONLY the colour fields are 0 and no colour byte of the pool is read.
+ * (the gradient) gradients[4i .. 4i+3] = {gx, gy, gz, 1.0f} with vk_volume_register's gx, gy, gz over the eight
+ * distances v[k], k = kx + 2 ky + 4 kz, in truncation lengths per voxel, in the volume's frame. It exists iff all eight
+ * points are present with distance_weight != 0 (no USED rule: the gradient needs both ends of every axis); otherwise the
+ * four floats are 0. The fourth float is the validity: a zero gradient in free space is a real value.
+ * (writes) samples[i] and gradients[4i ..] for i < count only, each by its own lane; a null output is not written. */
+VK_API int vk_volume_sample(const vk_volume* v, const float* points /* device [3*count] */, int32_t count,
+    const vk_transform* pose_dev /* optional, device: T_volume_points */, const vk_sample_params* p,
+    vk_voxel* samples /* optional, device [count] */, float* gradients /* optional, device [4*count] */, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

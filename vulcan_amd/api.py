@@ -127,6 +127,7 @@ _SIGNATURES = {
     "vk_volume_register_terms": ([_P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_register_system": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_register": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_sample": ([_P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -345,6 +346,25 @@ class Registration:
     def __repr__(self):
         return (f"Registration(steps={self.steps}, converged={self.converged}, overlap={self.overlap}, "
                 f"residuals={self.residuals}, rms={self.rms:.3g})")
+
+
+class Samples:
+    """what Volume.sample returns: tensor views of the two device buffers vk_volume_sample wrote. `distance` [N] is in
+    truncation lengths and 1.0 where `distance_weight` [N] (int16) is 0; `color` [N, 3] with `color_weight` [N] (None when
+    the colour was not asked for); `gradient` [N, 3] in truncation lengths per voxel and `gradient_valid` [N] (1.0 or 0.0),
+    None when the gradient was not asked for."""
+
+    def __init__(self, samples, gradients, color, truncation_length):
+        self.samples, self.gradients, self.truncation_length = samples, gradients, truncation_length
+        import torch
+        floats, shorts = samples.view(torch.float32), samples.view(torch.int16)
+        self.distance, self.distance_weight = floats[:, 0], shorts[:, 8]
+        self.color, self.color_weight = (floats[:, 1:4], shorts[:, 9]) if color else (None, None)
+        self.gradient, self.gradient_valid = (None, None) if gradients is None else (gradients[:, :3], gradients[:, 3])
+
+    def metres(self):
+        """the distance in metres (a new tensor)"""
+        return self.distance * self.truncation_length
 
 
 class Volume:
@@ -674,6 +694,45 @@ class Volume:
         out, state, counts, system, _ = self._register_call(other, pose, iterations, max_abs_distance)
         return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
                             float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0)
+
+    _sample_pose = None         # the device vk_transform a host pose of sample() is uploaded to
+
+    def _sample_call(self, points, pose=None, flags=0, samples=True, gradients=True, count=None, out=None):
+        """one vk_volume_sample at `points` (a float32 device tensor of 3 * count floats or more): the raw output buffers
+        (uint8 [n, 20] or None, float32 [n, 4] or None), allocated here or `out`'s. `pose`: a T.Transform (uploaded), a device
+        buffer that holds a vk_transform, or None."""
+        import torch
+        count = points.numel() // 3 if count is None else int(count)
+        if isinstance(pose, T.Transform):
+            if self._sample_pose is None:
+                self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
+            check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
+            pose = self._sample_pose
+        if out is None:
+            out = (torch.empty((count, 20), dtype=torch.uint8, device=self.device) if samples else None,
+                   torch.empty((count, 4), dtype=torch.float32, device=self.device) if gradients else None)
+        params = T.SampleParams(int(flags), 0)
+        check(lib().vk_volume_sample(_ref(self.desc()), _ptr(points), count, _ptr(pose), _ref(params), _ptr(out[0]), _ptr(out[1]),
+                                     stream()), "vk_volume_sample")
+        return out
+
+    def sample(self, points, pose=None, color=True, gradient=False, voxel_units=False):
+        """vk_volume_sample (not upstream): the volume's field at `points`, a float32 [N, 3] device tensor — in metres, or in
+        voxels with `voxel_units` — in the frame that `pose` (a Transform, a 4x4 array, or a device buffer holding a
+        vk_transform, e.g. a tracker's; None: the volume's own frame) carries into the volume's. Every point takes the
+        trilinear sample of the stored voxels, as merge(pose=) takes it at a voxel's centre; `gradient`: and the gradient of
+        the distance. The volume is only read; one launch, nothing is read back. Returns a Samples: where a weight is 0
+        there is no sample of that field and the distance reads 1.0, "far from any surface"."""
+        import torch
+        if not (hasattr(points, "data_ptr") and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3):
+            raise VkError("sample: points is a float32 [N, 3] device tensor")
+        points = points.contiguous()
+        if pose is not None and not isinstance(pose, T.Transform) and not hasattr(pose, "data_ptr"):
+            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        flags = (T.VK_SAMPLE_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_SAMPLE_DISTANCE_ONLY)
+        samples, gradients = self._sample_call(points, pose, flags, True, bool(gradient), points.shape[0])
+        return Samples(samples, gradients, bool(color), self.truncation_length)
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

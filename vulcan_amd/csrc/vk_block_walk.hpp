@@ -1,7 +1,8 @@
-// vk_block_walk.hpp — what the passes that carry one volume's voxels into another volume's lattice share
-// (vk_merge_pose.hip, vk_register.hip): the pose as three rows in voxel units, the chain walk that finds a block, the
-// lattice cell a carried centre falls into, and the host's checks of a volume. The definitions are in include/vk.h at
-// vk_volume_merge_posed (coordinates, chain walk, absent beyond the int16 range).
+// vk_block_walk.hpp — what the passes that carry a point into a volume's lattice share (vk_merge_pose.hip,
+// vk_register.hip, vk_sample.hip): the pose as three rows in voxel units, the chain walk that finds a block, the lattice
+// cell a carried point falls into, the trilinear value and gradient over a cell's eight values, and the host's checks of
+// a volume. The definitions are in include/vk.h at vk_volume_merge_posed (coordinates, chain walk, absent beyond the int16
+// range, the value) and vk_volume_register (the gradient).
 #pragma once
 
 #include "vk_requests.hpp"
@@ -84,6 +85,31 @@ __device__ __forceinline__ Lattice lattice_at(f3 p)
 __device__ __forceinline__ Lattice lattice_of(const float* rows, int ox, int oy, int oz, int x, int y, int z)
 {
   return lattice_at(apply(rows, (float)(8 * ox + x) + 0.5f, (float)(8 * oy + y) + 0.5f, (float)(8 * oz + z) + 0.5f));
+}
+
+// the value, vk_volume_merge_posed's spelling: an axis with f == 0 takes its base value
+__device__ __forceinline__ float lerp_axis(float f, float a, float b) { return f == 0.0f ? a : a + f * (b - a); }
+
+// x, then y, then z over the eight values v[s], s = sx + 2 sy + 4 sz
+__device__ __forceinline__ float trilinear(const float v[8], float fx, float fy, float fz)
+{
+  const float x00 = lerp_axis(fx, v[0], v[1]), x10 = lerp_axis(fx, v[2], v[3]), x01 = lerp_axis(fx, v[4], v[5]), x11 = lerp_axis(fx, v[6], v[7]);
+  const float y0 = lerp_axis(fy, x00, x10), y1 = lerp_axis(fy, x01, x11);
+  return lerp_axis(fz, y0, y1);
+}
+
+// the value and its gradient per voxel, vk_volume_register's spelling: all eight values take part on every axis
+__device__ __forceinline__ float lerp(float t, float a, float b) { return a + t * (b - a); }
+
+__device__ __forceinline__ float trilinear_gradient(const float v[8], float fx, float fy, float fz, float& gx, float& gy, float& gz)
+{
+  const float x00 = lerp(fx, v[0], v[1]), x10 = lerp(fx, v[2], v[3]), x01 = lerp(fx, v[4], v[5]), x11 = lerp(fx, v[6], v[7]);
+  const float y0 = lerp(fy, x00, x10), y1 = lerp(fy, x01, x11);
+  const float D = lerp(fz, y0, y1);
+  gz = y1 - y0;
+  gy = lerp(fz, x10 - x00, x11 - x01);
+  gx = lerp(fz, lerp(fy, v[1] - v[0], v[3] - v[2]), lerp(fy, v[5] - v[4], v[7] - v[6]));
+  return D;
 }
 
 inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }

@@ -276,16 +276,6 @@ __global__ void pose_finish_kernel(PoseParams P)
   P.dst.counters[VK_CTR_BANDED] = -1;           // the banded lists list nothing any more
 }
 
-__device__ __forceinline__ float lerp_axis(float f, float a, float b) { return f == 0.0f ? a : a + f * (b - a); }
-
-// x, then y, then z over the eight values v[s], s = sx + 2 sy + 4 sz
-__device__ __forceinline__ float trilinear(const float v[8], float fx, float fy, float fz)
-{
-  const float x00 = lerp_axis(fx, v[0], v[1]), x10 = lerp_axis(fx, v[2], v[3]), x01 = lerp_axis(fx, v[4], v[5]), x11 = lerp_axis(fx, v[6], v[7]);
-  const float y0 = lerp_axis(fy, x00, x10), y1 = lerp_axis(fy, x01, x11);
-  return lerp_axis(fz, y0, y1);
-}
-
 // One wave per marked dst entry, eight voxels per lane (lane = 8 y + x, one z per trip). Under a rigid pose the lattice
 // points of a block's 512 samples lie in at most 4^3 source blocks from the least one: lane k walks the chain of cell k
 // once and leaves the slot in the wave's 64-word LDS directory, so a voxel's eight neighbours cost eight pool reads and

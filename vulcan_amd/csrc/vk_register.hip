@@ -70,8 +70,6 @@ __global__ __launch_bounds__(256) void register_mark_kernel(RegisterParams P)
   wave_add(&P.ctl[cConsidered], blocks);
 }
 
-__device__ __forceinline__ float lerp(float t, float a, float b) { return a + t * (b - a); }
-
 // the terms of the source block at entry `index`, summed over the lane's eight voxels
 template <bool TERMS>
 __device__ __forceinline__ void block_terms(const RegisterParams& P, int index, int* directory, float (&acc)[27], float& squares,
@@ -156,13 +154,9 @@ __device__ __forceinline__ void block_terms(const RegisterParams& P, int index, 
       present = present && (int16_t)(voxel[4] & 0xffffu) != 0;
     }
     if (!present) continue;
-    const float x00 = lerp(l.fx, v[0], v[1]), x10 = lerp(l.fx, v[2], v[3]), x01 = lerp(l.fx, v[4], v[5]), x11 = lerp(l.fx, v[6], v[7]);
-    const float y0 = lerp(l.fy, x00, x10), y1 = lerp(l.fy, x01, x11);
-    const float D = lerp(l.fz, y0, y1);
+    float gx, gy, gz;
+    const float D = trilinear_gradient(v, l.fx, l.fy, l.fz, gx, gy, gz);
     if (!(fabsf(D) < band)) continue;
-    const float gz = y1 - y0;
-    const float gy = lerp(l.fz, x10 - x00, x11 - x01);
-    const float gx = lerp(l.fz, lerp(l.fy, v[1] - v[0], v[3] - v[2]), lerp(l.fy, v[5] - v[4], v[7] - v[6]));
     const size_t at = (size_t)(z * 64 + lane);
     const float r = D - __uint_as_float(block[at * kVoxelWords]);
     const float iv = P.inverse_voxel;

@@ -100,6 +100,13 @@ struct Registration
   float rms;            // sqrt(sum r^2 / residuals) of that step, in truncation lengths
 };
 
+// Not upstream: how Volume::Sample reads its points and what it samples (vk_sample_params)
+struct SampleOptions
+{
+  bool voxel_units = false;     // the points are in voxels, not metres: a voxel's centre is then exactly representable
+  bool distance_only = false;   // the colour fields of a sample stay 0 and no colour is read
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -179,6 +186,16 @@ class Volume
     // are only read; at most `iterations` steps (1 .. 64), enqueued at once; blocking readbacks at the end.
     Registration Register(const Volume& other, const Transform& start, int iterations = 20, float max_abs_distance = 0.75f);
 
+    // Not upstream: the volume's field at `count` arbitrary points (vk_volume_sample) — per point the trilinear sample of
+    // the stored voxels as a Voxel, the way Merge(other, pose) samples at a voxel's centre, and the gradient of the
+    // distance (x, y, z in truncation lengths per voxel, then 1 where it exists, else four zeros). The points are in
+    // metres in the frame that `pose` (null: the volume's own) carries into the volume's. A field without a sample is
+    // Voxel::Empty()'s: distance 1, weight 0. All three buffers are device memory; one of samples_dev / gradients_dev may
+    // be null (gradients_dev is 16-byte aligned). The volume is only read: one launch on Device::GetStream(), nothing is
+    // read back.
+    void Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, Vector4f* gradients_dev, const Transform* pose = nullptr,
+        const SampleOptions& options = SampleOptions()) const;
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -243,6 +260,7 @@ class Volume
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
     Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
     Buffer<int> register_ints_;                    // the state (2), the counts (4)
+    mutable Buffer<float> sample_pose_;            // Sample: the pose on the device (32)
 
     Vector2f depth_range_;
     int max_block_count_;

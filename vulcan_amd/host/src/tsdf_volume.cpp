@@ -496,6 +496,25 @@ Registration Volume::Register(const Volume& other, const Transform& start, int i
   return out;
 }
 
+void Volume::Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, Vector4f* gradients_dev, const Transform* pose,
+    const SampleOptions& options) const
+{
+  vk_sample_params p;
+  p.flags = (options.voxel_units ? VK_SAMPLE_VOXEL_UNITS : 0) | (options.distance_only ? VK_SAMPLE_DISTANCE_ONLY : 0);
+  p.pad = 0;
+  const vk_transform* pose_dev = nullptr;
+  if (pose)
+  {
+    if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
+    const vk_transform seed = pose->ToVk();
+    VK_ASSERT(vk_transform_upload(reinterpret_cast<vk_transform*>(sample_pose_.GetData()), &seed, Device::GetStream()));
+    pose_dev = reinterpret_cast<const vk_transform*>(sample_pose_.GetData());
+  }
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_sample(&v, reinterpret_cast<const float*>(points_dev), count, pose_dev, &p, reinterpret_cast<vk_voxel*>(samples_dev),
+      reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
+}
+
 void Volume::ResetBlockVisibility()
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");

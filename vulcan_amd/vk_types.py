@@ -26,6 +26,7 @@ BLOCK_RESOLUTION, BLOCK_VOXELS, PATCH_MAX_SIZE = 8, 512, 16
 VK_RELEASE_UNOBSERVED, VK_RELEASE_NO_SURFACE, VK_RELEASE_OUTSIDE_BOX = 1, 2, 4   # vk_release_rule.flags
 VK_MERGE_SKIP_UNOBSERVED, VK_MERGE_CONTINUE = 1, 2                               # vk_merge_params.flags
 VK_REGISTER_NO_OVERLAP = 2                                                       # vk_volume_register: state_dev[1]
+VK_SAMPLE_VOXEL_UNITS, VK_SAMPLE_DISTANCE_ONLY = 1, 2                            # vk_sample_params.flags
 
 voxel_dtype = np.dtype([("distance", "<f4"), ("color", "<f4", (3,)),
                         ("distance_weight", "<i2"), ("color_weight", "<i2")])
@@ -219,6 +220,11 @@ class MergePoseParams(C.Structure):
 class RegisterParams(C.Structure):
     """vk_register_params (vk.h): how vk_volume_register aligns one volume to another; the band is in truncation lengths"""
     _fields_ = [("flags", C.c_int32), ("iterations", C.c_int32), ("max_abs_distance", C.c_float), ("pad", C.c_int32)]
+
+
+class SampleParams(C.Structure):
+    """vk_sample_params (vk.h): the units of vk_volume_sample's points, and whether the colour is sampled"""
+    _fields_ = [("flags", C.c_int32), ("pad", C.c_int32)]
 
 
 class PyramidAhead(C.Structure):
