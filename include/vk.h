@@ -1499,6 +1499,70 @@ VK_API int vk_volume_sample(const vk_volume* v, const float* points /* device [3
     const vk_transform* pose_dev /* optional, device: T_volume_points */, const vk_sample_params* p,
     vk_voxel* samples /* optional, device [count] */, float* gradients /* optional, device [4*count] */, void* stream);
 
+/* --------------------------------------------------------------- cast rays -- */
+
+enum { VK_CAST_VOXEL_UNITS = 1, VK_CAST_DISTANCE_ONLY = 2 };
+enum { VK_RAY_MISS = 0, VK_RAY_HIT = 1, VK_RAY_STEPS = 2, VK_RAY_INVALID = 3 };
+
+typedef struct vk_cast_params {
+  int32_t flags;             /* VK_CAST_*; an unknown bit is VK_ERR_ARGUMENT */
+  int32_t max_steps;         /* 1 .. 65536: the march of a ray takes at most this many steps */
+  float t_min;               /* 0 <= t_min < t_max, both finite: the stretch of the ray that is searched, in metres */
+  float t_max;               /*   along the normalised direction (in voxels with VK_CAST_VOXEL_UNITS) */
+} vk_cast_params;
+
+/* What each of `count` arbitrary rays through the volume hits first, and how far away: a line of sight or a collision
+ * check for a planner, a simulated LiDAR or fisheye sensor, picking in a viewer, a next-best-view score, a camera model
+ * vk_trace does not have. No upstream counterpart (the reference casts only the pixel rays of one pinhole camera, and
+ * vk_trace needs that camera's frame, visible-block list and patch bounds); ref: src/tracer.cu:317-451 for the march rule,
+ * which this is in voxel units, src/volume.cu:168-191 for the chain walk. The definition is this comment;
+ * tests/cast_reference.py states it on the CPU and the device is held to it bit for bit. All arithmetic is fp32, one
+ * rounding per operation, no contraction, IEEE division and a correctly rounded square root.
+ * ACCESS: the volume is only read. One launch on `stream`, nothing read back, no atomic and no wait on another
+ * workgroup; max_steps bounds the march and the table size bounds a chain walk: it cannot hang a device.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): v or p null, a volume that vk_volume_sample would refuse, a flag other
+ * than the two, count < 0, rays null with count > 0, t_out or status null, gradients not 16-byte aligned, max_steps
+ * outside 1 .. 65536, t_min or t_max not finite, not 0 <= t_min < t_max. count == 0 returns 0 and launches nothing.
+ * (units) L = voxel_length, tr = truncation_length / L, t0 = t_min / L, t1 = t_max / L; with VK_CAST_VOXEL_UNITS
+ * t0 = t_min, t1 = t_max and nothing is divided, in the origin or in t. The march runs in voxels.
+ * (the ray) ray i is origin x = rays[6i .. 6i+2] and direction d = rays[6i+3 .. 6i+5] (any length), in the frame that
+ * pose_dev carries into the volume's. q_a = x_a / L (q = x with VK_CAST_VOXEL_UNITS). With pose_dev == NULL o = q, else
+ * o = fwd(q) as vk_volume_sample defines fwd, and the direction goes through the rotation only:
+ * d'_a = (m[a] d_0 + m[4+a] d_1) + m[8+a] d_2. len = sqrtf((d_0 d_0 + d_1 d_1) + d_2 d_2), n_a = d_a / len. The ray is
+ * VK_RAY_INVALID unless |o_a| < 2^30 for every a (a NaN fails it; beyond the cell clamp below a cell is not the point's),
+ * len is finite and every n_a is finite: a zero direction is invalid (0 / 0), and so is one whose squares overflow (its
+ * n would be 0 or NaN).
+ * (the march) t = t0, armed = false, steps = 0; repeat:
+ *  1. !(t < t1): VK_RAY_MISS.
+ *  2. steps == max_steps: VK_RAY_STEPS; else ++steps.
+ *  3. p_a = o_a + t * n_a (mul, add); a non-finite p_a: VK_RAY_MISS.
+ *  4. the cell c_a = (int)floorf(p_a), saturating, clamped to +-2^30; the block B = c >> 3, found by the chain walk,
+ *     absent when a coordinate leaves the int16 range.
+ *  5. B absent: leave it through its exit face. For each axis with n_a != 0, face_a = (float)(8 B_a + (n_a > 0 ? 8 : 0))
+ *     and s_a = (face_a - p_a) / n_a; s = fminf over those axes in x, y, z order, starting from +infinity;
+ *     t = t + (fmaxf(s, 0.0f) + 0.5f). (The reference steps a whole block length, tracer.cu:435, and can jump a block's
+ *     corner; a query that must not miss geometry does not.)
+ *  6. B present: u = voxel (c & 7) of B, observed = (u.distance_weight != 0), sdf = observed ? u.distance : 1.0f
+ *     (Voxel::Empty()'s distance, as the reference reads an unobserved voxel). If observed and sdf <= 0.1f and
+ *     sdf >= -0.5f (the reference's window, tracer.cu:383) and vk_volume_sample's distance sample exists at p (voxel
+ *     units, no pose, the USED rule), sdf = that sample's distance. If observed and sdf > 0: armed = true. If observed
+ *     and armed and sdf <= 0: the refinement. Else t = t + (sdf > 0 ? fmaxf(1.0f, tr * sdf) : 1.0f).
+ *  A surface is reported only where the ray crosses it from its observed free side: a ray that starts behind a surface
+ *  walks out through it and goes on (the reference, whose rays start at the camera, reports the first sdf <= 0).
+ * (the refinement, tracer.cu:396-420) t = t + tr * sdf; p = o + t n; if the distance sample exists at p,
+ * t = t + tr * its distance. VK_RAY_HIT.
+ * (outputs) status[i] is the outcome. t_out[i] = t * L for a hit (t with VK_CAST_VOXEL_UNITS), 0.0f otherwise: the
+ * library's "no measurement", like a raycast depth of 0. For a hit, samples[i] and gradients[4i .. 4i+3] are exactly
+ * vk_volume_sample's at p_hit = o + t n with voxel units and no pose, in the volume's frame; for any other outcome
+ * Voxel::Empty() (distance 1.0f, the rest 0) and four zeros. With VK_CAST_DISTANCE_ONLY the colour fields are 0 and no
+ * colour byte of the pool is read.
+ * (writes) t_out[i], status[i], samples[i] and gradients[4i ..] for i < count only, each by its own lane; a null
+ * optional output is not written. */
+VK_API int vk_volume_cast_rays(const vk_volume* v, const float* rays /* device [6*count]: origin, direction */, int32_t count,
+    const vk_transform* pose_dev /* optional, device: T_volume_rays */, const vk_cast_params* p,
+    float* t_out /* device [count] */, int32_t* status /* device [count] */,
+    vk_voxel* samples /* optional, device [count] */, float* gradients /* optional, device [4*count], 16-byte aligned */, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

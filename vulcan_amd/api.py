@@ -128,6 +128,7 @@ _SIGNATURES = {
     "vk_volume_register_system": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_register": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_sample": ([_P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
+    "vk_volume_cast_rays": ([_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -365,6 +366,21 @@ class Samples:
     def metres(self):
         """the distance in metres (a new tensor)"""
         return self.distance * self.truncation_length
+
+
+class RayHits:
+    """what Volume.cast_rays returns: tensor views of the device buffers vk_volume_cast_rays wrote. `status` [N] int32 is
+    VK_RAY_MISS, _HIT, _STEPS (max_steps ran out) or _INVALID per ray; `t` [N] the distance along the normalised direction
+    in the unit the rays came in, 0.0 where there is no hit; the fields of the hit's sample are Samples' (`distance`,
+    `distance_weight`, `color`, `color_weight`, `gradient`, `gradient_valid`), Voxel::Empty() and zeros without a hit."""
+
+    def __init__(self, t, status, samples, gradients, color, truncation_length):
+        self.t, self.status = t, status
+        self.hit = status == T.VK_RAY_HIT
+        at = Samples(samples, gradients, color, truncation_length)
+        self.samples, self.gradients = at.samples, at.gradients
+        self.distance, self.distance_weight, self.color, self.color_weight = at.distance, at.distance_weight, at.color, at.color_weight
+        self.gradient, self.gradient_valid = at.gradient, at.gradient_valid
 
 
 class Volume:
@@ -733,6 +749,48 @@ class Volume:
         flags = (T.VK_SAMPLE_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_SAMPLE_DISTANCE_ONLY)
         samples, gradients = self._sample_call(points, pose, flags, True, bool(gradient), points.shape[0])
         return Samples(samples, gradients, bool(color), self.truncation_length)
+
+    def _cast_call(self, rays, pose=None, flags=0, t_min=0.0, t_max=5.0, max_steps=500, samples=True, gradients=True, count=None,
+                   out=None):
+        """one vk_volume_cast_rays of `rays` (a float32 device tensor of 6 * count floats or more): the raw output buffers
+        (float32 [n], int32 [n], uint8 [n, 20] or None, float32 [n, 4] or None), allocated here or `out`'s. `pose`: a
+        T.Transform (uploaded), a device buffer that holds a vk_transform, or None."""
+        import torch
+        count = rays.numel() // 6 if count is None else int(count)
+        if isinstance(pose, T.Transform):
+            if self._sample_pose is None:
+                self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
+            check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
+            pose = self._sample_pose
+        if out is None:
+            out = (torch.empty(count, dtype=torch.float32, device=self.device), torch.empty(count, dtype=torch.int32, device=self.device),
+                   torch.empty((count, 20), dtype=torch.uint8, device=self.device) if samples else None,
+                   torch.empty((count, 4), dtype=torch.float32, device=self.device) if gradients else None)
+        params = T.CastParams(int(flags), int(max_steps), float(t_min), float(t_max))
+        check(lib().vk_volume_cast_rays(_ref(self.desc()), _ptr(rays), count, _ptr(pose), _ref(params), _ptr(out[0]), _ptr(out[1]),
+                                        _ptr(out[2]), _ptr(out[3]), stream()), "vk_volume_cast_rays")
+        return out
+
+    def cast_rays(self, rays, pose=None, t_min=0.0, t_max=None, max_steps=500, color=True, gradient=False, voxel_units=False):
+        """vk_volume_cast_rays (not upstream): what each ray of `rays`, a float32 [N, 6] device tensor of origins and
+        directions (any length) — origins in metres, or in voxels with `voxel_units` — hits first in the volume, in the
+        frame that `pose` (a Transform, a 4x4 array, or a device buffer holding a vk_transform; None: the volume's own
+        frame) carries into the volume's. The raycast's march between `t_min` and `t_max` along the ray (in the origins'
+        unit; `t_max` None: the far end of the volume's depth range), at most `max_steps` steps: a surface is reported
+        where the ray crosses it from its observed free side. The volume is only read; one launch, nothing is read back.
+        Returns a RayHits: status, t and the sample (`gradient`: and the gradient) at every hit."""
+        import torch
+        if not (hasattr(rays, "data_ptr") and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6):
+            raise VkError("cast_rays: rays is a float32 [N, 6] device tensor")
+        rays = rays.contiguous()
+        if pose is not None and not isinstance(pose, T.Transform) and not hasattr(pose, "data_ptr"):
+            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        if t_max is None:
+            t_max = float(np.float32(self.depth_range[1]) / np.float32(self.voxel_length)) if voxel_units else self.depth_range[1]
+        flags = (T.VK_CAST_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_CAST_DISTANCE_ONLY)
+        t, status, samples, gradients = self._cast_call(rays, pose, flags, t_min, t_max, max_steps, True, bool(gradient), rays.shape[0])
+        return RayHits(t, status, samples, gradients, bool(color), self.truncation_length)
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

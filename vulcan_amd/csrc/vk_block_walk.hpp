@@ -1,8 +1,9 @@
 // vk_block_walk.hpp — what the passes that carry a point into a volume's lattice share (vk_merge_pose.hip,
-// vk_register.hip, vk_sample.hip): the pose as three rows in voxel units, the chain walk that finds a block, the lattice
-// cell a carried point falls into, the trilinear value and gradient over a cell's eight values, and the host's checks of
-// a volume. The definitions are in include/vk.h at vk_volume_merge_posed (coordinates, chain walk, absent beyond the int16
-// range, the value) and vk_volume_register (the gradient).
+// vk_register.hip, vk_sample.hip, vk_cast.hip): the pose as three rows in voxel units, the chain walk that finds a block,
+// the lattice cell a carried point falls into, the trilinear value and gradient over a cell's eight values, the cell of a
+// point read from the pool as vk_volume_sample defines it, and the host's checks of a volume. The definitions are in
+// include/vk.h at vk_volume_merge_posed (coordinates, chain walk, absent beyond the int16 range, the value),
+// vk_volume_register (the gradient) and vk_volume_sample (the sample of a point).
 #pragma once
 
 #include "vk_requests.hpp"
@@ -110,6 +111,142 @@ __device__ __forceinline__ float trilinear_gradient(const float v[8], float fx, 
   gy = lerp(fz, x10 - x00, x11 - x01);
   gx = lerp(fz, lerp(fy, v[1] - v[0], v[3] - v[2]), lerp(fy, v[5] - v[4], v[7] - v[6]));
   return D;
+}
+
+// a lane's block lookups are eight named registers, s[k] the slot of the block at offset k (bit a: one block further
+// along axis a) from the base block: an array indexed by the lane's own k would leave the register file
+__device__ __forceinline__ int pick(int k, int s0, int s1, int s2, int s3, int s4, int s5, int s6, int s7)
+{
+  int slot = s0;
+  slot = k == 1 ? s1 : slot;  slot = k == 2 ? s2 : slot;  slot = k == 3 ? s3 : slot;  slot = k == 4 ? s4 : slot;
+  slot = k == 5 ? s5 : slot;  slot = k == 6 ? s6 : slot;  slot = k == 7 ? s7 : slot;
+  return slot;
+}
+
+typedef float vf4 __attribute__((ext_vector_type(4)));
+
+// what a point reads of the pool, vk_volume_sample's definition: the eight values of its cell (0 where a lattice point is
+// not read or absent), whether the distance and the colour sample exist by the USED rule with their smallest weights, and
+// whether all eight points carry a distance (the gradient's condition)
+struct Cell
+{
+  Lattice l;
+  float distance[8], red[8], green[8], blue[8];
+  bool has_d, has_c, all_d;
+  int least_dw, least_cw;
+};
+
+// COLOR: the colour fields are read (else they are 0 and no colour byte is read). GRADIENT: all eight lattice points are
+// read, else the USED ones. A lane resolves its base block by one chain walk and walks a further chain only for a block of
+// the cell's 2x2x2 neighbourhood that a wanted lattice point lies in (an axis leaves the base block only where
+// b & 7 == 7); the slots are kept in registers, so the eight corners cost eight pool reads and no table read of their own.
+// `finite`: p has three finite components; a point without has no sample of any kind and reads nothing.
+template <bool COLOR, bool GRADIENT>
+__device__ __forceinline__ Cell read_cell(const vk_volume& v, int total, f3 p, bool finite)
+{
+  Cell c;
+  c.l = lattice_at(finite ? p : f3{0.0f, 0.0f, 0.0f});
+  const Lattice& l = c.l;
+  const bool far_x = l.fx != 0.0f, far_y = l.fy != 0.0f, far_z = l.fz != 0.0f;
+  // the lattice points that are read: all eight for the gradient, else the USED ones
+  const int wanted = GRADIENT ? 7 : (far_x ? 1 : 0) | (far_y ? 2 : 0) | (far_z ? 4 : 0);
+  // the axes along which b + 1 lies in the next block
+  const int leaves = ((l.bx & 7) == 7 ? 1 : 0) | ((l.by & 7) == 7 ? 2 : 0) | ((l.bz & 7) == 7 ? 4 : 0);
+  const int base_x = l.bx >> 3, base_y = l.by >> 3, base_z = l.bz >> 3;
+
+  // the blocks of the neighbourhood a wanted point lies in: offset k is one iff k is a subset of `leaves & wanted`
+  int s0 = -1, s1 = -1, s2 = -1, s3 = -1, s4 = -1, s5 = -1, s6 = -1, s7 = -1;
+  const int reach = leaves & wanted;
+  uint32_t pending = 0u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) pending |= (finite && (k & ~reach) == 0) ? 1u << k : 0u;
+  while (pending)
+  {
+    const int k = __ffs(pending) - 1;
+    pending &= pending - 1u;
+    const int bx = base_x + (k & 1), by = base_y + ((k >> 1) & 1), bz = base_z + (k >> 2);
+    int slot = -1;
+    Entry main_entry;
+    if (in_int16(bx, by, bz)) find_block(v, total, bx, by, bz, slot, main_entry);
+    s0 = k == 0 ? slot : s0;  s1 = k == 1 ? slot : s1;  s2 = k == 2 ? slot : s2;  s3 = k == 3 ? slot : s3;
+    s4 = k == 4 ? slot : s4;  s5 = k == 5 ? slot : s5;  s6 = k == 6 ? slot : s6;  s7 = k == 7 ? slot : s7;
+  }
+
+  const uint32_t* pool = reinterpret_cast<const uint32_t*>(v.voxels);
+  c.has_d = c.has_c = c.all_d = finite;
+  c.least_dw = c.least_cw = 32767;
+#pragma unroll
+  for (int s = 0; s < 8; ++s)
+  {
+    c.distance[s] = c.red[s] = c.green[s] = c.blue[s] = 0.0f;
+    const bool used = (!(s & 1) || far_x) && (!(s & 2) || far_y) && (!(s & 4) || far_z);
+    if (!(GRADIENT || used)) continue;
+    const int nx = l.bx + (s & 1), ny = l.by + ((s >> 1) & 1), nz = l.bz + (s >> 2);
+    const int slot = pick(s & leaves, s0, s1, s2, s3, s4, s5, s6, s7);
+    if (slot < 0)
+    {
+      c.all_d = false;
+      if (used) c.has_d = c.has_c = false;
+      continue;
+    }
+    const uint32_t* voxel = pool + ((size_t)slot * VK_BLOCK_VOXELS + (size_t)((nz & 7) * 64 + (ny & 7) * 8 + (nx & 7))) * kVoxelWords;
+    const uint32_t weights = voxel[4];
+    const int dw = (int16_t)(weights & 0xffffu), cw = (int16_t)(weights >> 16);
+    if (COLOR)
+    {
+      const vu4 head = *reinterpret_cast<const vu4*>(voxel);
+      c.distance[s] = __uint_as_float(head.x);
+      c.red[s] = __uint_as_float(head.y);
+      c.green[s] = __uint_as_float(head.z);
+      c.blue[s] = __uint_as_float(head.w);
+    }
+    else c.distance[s] = __uint_as_float(voxel[0]);
+    c.all_d = c.all_d && dw != 0;
+    if (used)
+    {
+      c.has_d = c.has_d && dw != 0;
+      c.has_c = c.has_c && cw != 0;
+      c.least_dw = vmini(c.least_dw, dw);
+      c.least_cw = vmini(c.least_cw, cw);
+    }
+  }
+  return c;
+}
+
+// the cell's sample as a vk_voxel at `sample`: a field without a sample is Voxel::Empty()'s
+template <bool COLOR>
+__device__ __forceinline__ void store_sample(const Cell& c, uint32_t* sample)
+{
+  uint32_t out[5] = {__float_as_uint(1.0f), 0u, 0u, 0u, 0u};
+  if (c.has_d)
+  {
+    out[0] = __float_as_uint(trilinear(c.distance, c.l.fx, c.l.fy, c.l.fz));
+    out[4] = (uint32_t)(uint16_t)c.least_dw;
+  }
+  if (COLOR && c.has_c)
+  {
+    out[1] = __float_as_uint(trilinear(c.red, c.l.fx, c.l.fy, c.l.fz));
+    out[2] = __float_as_uint(trilinear(c.green, c.l.fx, c.l.fy, c.l.fz));
+    out[3] = __float_as_uint(trilinear(c.blue, c.l.fx, c.l.fy, c.l.fz));
+    out[4] |= (uint32_t)(uint16_t)c.least_cw << 16;
+  }
+  vu4 head;
+  head.x = out[0];  head.y = out[1];  head.z = out[2];  head.w = out[3];
+  *reinterpret_cast<vu4*>(sample) = head;
+  sample[4] = out[4];
+}
+
+// {gx, gy, gz, 1} of a cell read with GRADIENT, or four zeros where one of the eight is missing: one 16-byte store
+__device__ __forceinline__ void store_gradient(const Cell& c, float* gradient)
+{
+  vf4 g = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (c.all_d)
+  {
+    float gx, gy, gz;
+    trilinear_gradient(c.distance, c.l.fx, c.l.fy, c.l.fz, gx, gy, gz);
+    g.x = gx;  g.y = gy;  g.z = gz;  g.w = 1.0f;
+  }
+  *reinterpret_cast<vf4*>(gradient) = g;
 }
 
 inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }

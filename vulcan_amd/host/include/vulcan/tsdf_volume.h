@@ -107,6 +107,23 @@ struct SampleOptions
   bool distance_only = false;   // the colour fields of a sample stay 0 and no colour is read
 };
 
+// Not upstream: how Volume::CastRays reads its rays, how far it marches and what it samples at a hit (vk_cast_params)
+struct CastOptions
+{
+  bool voxel_units = false;     // the origins, t_min, t_max and the returned t are in voxels, not metres
+  bool distance_only = false;   // the colour fields of a hit's sample stay 0 and no colour is read
+  float t_min = 0.0f;           // the stretch of each ray that is searched, along its normalised direction
+  float t_max = 5.0f;
+  int max_steps = 500;          // 1 .. 65536: a ray that needs more ends as VK_RAY_STEPS
+};
+
+// Not upstream: a ray of Volume::CastRays, in the layout vk_volume_cast_rays reads
+struct Ray
+{
+  Vector3f origin;
+  Vector3f direction;           // any length; a zero or non-finite direction is VK_RAY_INVALID
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -196,6 +213,17 @@ class Volume
     void Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, Vector4f* gradients_dev, const Transform* pose = nullptr,
         const SampleOptions& options = SampleOptions()) const;
 
+    // Not upstream: what each of `count` arbitrary rays hits first in the volume (vk_volume_cast_rays) — the raycast's
+    // march along rays that are no pixels of a camera: a line of sight, a simulated range sensor, picking. Per ray the
+    // outcome (VK_RAY_MISS, _HIT, _STEPS, _INVALID) in status_dev, the distance along the normalised direction in t_dev
+    // (0 without a hit) and, where asked for, Sample's voxel and gradient at the hit (Voxel::Empty() and four zeros
+    // without one). A surface is reported only where the ray crosses it from its observed free side. The rays are in the
+    // frame that `pose` (null: the volume's own) carries into the volume's. All buffers are device memory; samples_dev
+    // and gradients_dev may be null (gradients_dev is 16-byte aligned). The volume is only read: one launch on
+    // Device::GetStream(), nothing is read back.
+    void CastRays(const Ray* rays_dev, int count, float* t_dev, int* status_dev, Voxel* samples_dev = nullptr,
+        Vector4f* gradients_dev = nullptr, const Transform* pose = nullptr, const CastOptions& options = CastOptions()) const;
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -260,7 +288,7 @@ class Volume
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
     Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
     Buffer<int> register_ints_;                    // the state (2), the counts (4)
-    mutable Buffer<float> sample_pose_;            // Sample: the pose on the device (32)
+    mutable Buffer<float> sample_pose_;            // Sample, CastRays: the pose on the device (32)
 
     Vector2f depth_range_;
     int max_block_count_;

@@ -515,6 +515,28 @@ void Volume::Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, V
       reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
 }
 
+void Volume::CastRays(const Ray* rays_dev, int count, float* t_dev, int* status_dev, Voxel* samples_dev, Vector4f* gradients_dev,
+    const Transform* pose, const CastOptions& options) const
+{
+  static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
+  vk_cast_params p;
+  p.flags = (options.voxel_units ? VK_CAST_VOXEL_UNITS : 0) | (options.distance_only ? VK_CAST_DISTANCE_ONLY : 0);
+  p.max_steps = options.max_steps;
+  p.t_min = options.t_min;
+  p.t_max = options.t_max;
+  const vk_transform* pose_dev = nullptr;
+  if (pose)
+  {
+    if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
+    const vk_transform seed = pose->ToVk();
+    VK_ASSERT(vk_transform_upload(reinterpret_cast<vk_transform*>(sample_pose_.GetData()), &seed, Device::GetStream()));
+    pose_dev = reinterpret_cast<const vk_transform*>(sample_pose_.GetData());
+  }
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_cast_rays(&v, reinterpret_cast<const float*>(rays_dev), count, pose_dev, &p, t_dev, status_dev,
+      reinterpret_cast<vk_voxel*>(samples_dev), reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
+}
+
 void Volume::ResetBlockVisibility()
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");

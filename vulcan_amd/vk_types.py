@@ -27,6 +27,8 @@ VK_RELEASE_UNOBSERVED, VK_RELEASE_NO_SURFACE, VK_RELEASE_OUTSIDE_BOX = 1, 2, 4  
 VK_MERGE_SKIP_UNOBSERVED, VK_MERGE_CONTINUE = 1, 2                               # vk_merge_params.flags
 VK_REGISTER_NO_OVERLAP = 2                                                       # vk_volume_register: state_dev[1]
 VK_SAMPLE_VOXEL_UNITS, VK_SAMPLE_DISTANCE_ONLY = 1, 2                            # vk_sample_params.flags
+VK_CAST_VOXEL_UNITS, VK_CAST_DISTANCE_ONLY = 1, 2                                # vk_cast_params.flags
+VK_RAY_MISS, VK_RAY_HIT, VK_RAY_STEPS, VK_RAY_INVALID = 0, 1, 2, 3               # vk_volume_cast_rays: status[i]
 
 voxel_dtype = np.dtype([("distance", "<f4"), ("color", "<f4", (3,)),
                         ("distance_weight", "<i2"), ("color_weight", "<i2")])
@@ -225,6 +227,12 @@ class RegisterParams(C.Structure):
 class SampleParams(C.Structure):
     """vk_sample_params (vk.h): the units of vk_volume_sample's points, and whether the colour is sampled"""
     _fields_ = [("flags", C.c_int32), ("pad", C.c_int32)]
+
+
+class CastParams(C.Structure):
+    """vk_cast_params (vk.h): the units of vk_volume_cast_rays' origins and bounds, whether the colour is sampled, and the
+    bounds of the march"""
+    _fields_ = [("flags", C.c_int32), ("max_steps", C.c_int32), ("t_min", C.c_float), ("t_max", C.c_float)]
 
 
 class PyramidAhead(C.Structure):
