@@ -1563,6 +1563,78 @@ VK_API int vk_volume_cast_rays(const vk_volume* v, const float* rays /* device [
     float* t_out /* device [count] */, int32_t* status /* device [count] */,
     vk_voxel* samples /* optional, device [count] */, float* gradients /* optional, device [4*count], 16-byte aligned */, void* stream);
 
+/* ---------------------------------------------------------- integrate rays -- */
+
+enum { VK_RAYS_VOXEL_UNITS = 1, VK_RAYS_ONE_OBSERVATION = 2 };
+
+typedef struct vk_integrate_rays_params {
+  int32_t flags;               /* VK_RAYS_*; an unknown bit is VK_ERR_ARGUMENT */
+  int32_t max_rounds;          /* 0 .. 64 allocation rounds; 0 allocates nothing (update a fixed map) */
+  float   r_min, r_max;        /* a ray has a measurement iff r_min <= range <= r_max (false for a NaN); 0 <= r_min < r_max, finite */
+  float   max_distance_weight; /* 1 .. 32767 */
+  int32_t pad;
+} vk_integrate_rays_params;
+
+/* Fuse `count` range measurements along arbitrary rays into the volume: a spinning LiDAR, a fisheye or otherwise distorted
+ * depth camera, a sparse or unorganised point cloud, or what vk_volume_cast_rays returned for another volume — (rays, t)
+ * feeds in unchanged, t == 0 being "no measurement". No upstream counterpart (the reference fuses only the pixels of one
+ * pinhole depth image, which every voxel finds by projecting into it); ref: src/depth_integrator.cu:54-74 for the band test,
+ * the min(1, d / truncation) and the running average, src/volume.cu:87-301 for requesting the blocks within one truncation
+ * length either side of the measurement, src/volume.cu:304-368 for the handle pass. The definition is this comment;
+ * tests/integrate_rays_reference.py states it on the CPU and the device is held to it bit for bit. All arithmetic is fp32,
+ * one rounding per operation, no contraction, IEEE division and a correctly rounded square root.
+ * PRECONDITIONS: vk_volume_merge's for dst — between SetView calls, no frame announced (the class layers enforce it).
+ * ACCESS: rays, ranges and the pose are only read. Everything is enqueued on `stream`, nothing is read back, no workgroup
+ * waits on another; the walk is bounded by G below and a chain walk by the table size: it cannot hang a device. `workspace`:
+ * vk_volume_integrate_rays_workspace_bytes(main, excess) bytes, 16-byte aligned, need not be initialised.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): v, p, counts_dev or workspace null, a volume that vk_volume_merge would
+ * refuse, a flag other than the two, max_rounds outside 0 .. 64, a cap outside 1 .. 32767, r_min or r_max not finite or not
+ * 0 <= r_min < r_max, count < 0 or count > 1 << 22, rays or ranges null with count > 0, a workspace not 16-byte aligned,
+ * truncation_length / voxel_length > 64. count == 0 returns 0, launches nothing and leaves the counters' bytes alone.
+ * (units) L = voxel_length, tr = truncation_length / L. The walk runs in voxels.
+ * (the ray) ray i is vk_volume_cast_rays' ray word for word: q = x / L (q = x with VK_RAYS_VOXEL_UNITS), o = q or fwd(q)
+ * through pose_dev, the direction through the rotation alone, n = d / sqrtf((d_0 d_0 + d_1 d_1) + d_2 d_2), and INVALID by
+ * the same rule (|o_a| not < 2^30, a non-finite length or n_a). range_i = ranges[i] is the distance along n in the origin's
+ * unit, like r_min and r_max; r = range_i / L (r = range_i with VK_RAYS_VOXEL_UNITS). A valid ray has a measurement iff
+ * r_min <= range_i <= r_max; one without is skipped.
+ * (the walk) the exact traversal of the cells the ray crosses inside the band: ta = fmaxf(r - tr, 0), tb = r + tr,
+ * p_a = o_a + ta * n_a (mul, add), c_a = (int)floorf(p_a), saturating, clamped to +-2^30. Per axis: n_a > 0: step_a = 1,
+ * tmax_a = ta + ((float)(c_a + 1) - p_a) / n_a, tdelta_a = 1.0f / n_a; n_a < 0: step_a = -1, tmax_a = ta + ((float)c_a - p_a)
+ * / n_a, tdelta_a = 1.0f / fabsf(n_a); n_a == 0: step_a = 0, both +infinity. At most G = 3 * (min((int)ceilf(tb - ta), 1024)
+ * + 2) times (the conversion saturates, a NaN gives 0; tb - ta <= 4 tr, so the 1024 is never reached): visit c; a = the axis
+ * of the smallest tmax, x before y before z on a tie (tmax_y < tmax_x, then tmax_z < the smaller: a NaN is never smaller);
+ * !(tmax_a <= tb): end; c_a += step_a, tmax_a = tmax_a + tdelta_a. A visited cell whose block B = c >> 3 has a coordinate
+ * outside the int16 range is passed over: it is requested nowhere, counted nowhere and takes no update.
+ * (allocation) vk_volume_merge's rounds with the blocks of the visited cells of the rays that have a measurement in the place
+ * of the source blocks: presence by the chain walk, one request per bucket and round, MAIN or EXCESS, the largest key wins, a
+ * MAIN request sets visibility TRUE, one vk_volume_handle_allocation_requests per round, the same two ends of the rounds
+ * (a round that posts nothing, a round that drops), exhaustion included. max_rounds == 0: no round.
+ * (accumulation) for every visited cell whose block is present after the rounds: e_a = (float)c_a + 0.5f,
+ * raw = r - (((e_0 - o_0) n_0 + (e_1 - o_1) n_1) + (e_2 - o_2) n_2); if raw > -tr: u = fminf(1.0f, raw / tr),
+ * q = (int)rintf(u * 1048576.0f) (ties to even), and the voxel's S += q (a 64-bit integer), N += 1. Integer sums commute:
+ * S and N do not depend on the order of the rays or on timing. No float atomic touches a voxel or an accumulator.
+ * (the fold) for every voxel with N > 0: m = ((float)S / (float)N) * 0x1p-20f (both conversions round to nearest even),
+ * ws = VK_RAYS_ONE_OBSERVATION ? 1.0f : (float)N, and the voxel's running average goes on as vk_volume_merge continues it with
+ * a source voxel of distance m and weight ws: wd = (float)distance_weight, distance = wd == 0 ? m : (wd * distance + ws * m)
+ * / (wd + ws), distance_weight = (int16)fminf(max_distance_weight, wd + ws). The colour fields and the colour weight keep
+ * their bytes; a voxel with N == 0 keeps all its bytes; an allocated block that took no update stays Voxel::Empty().
+ * (afterwards) as after vk_volume_merge: VK_CTR_VISIBLE = 0, VK_CTR_BANDED = -1, anything prepared ahead is void.
+ * counts_dev int32[8]: rays integrated (valid, with a measurement); valid rays without a measurement; invalid rays; blocks
+ * allocated by the call (visited blocks present after the rounds and not before); rounds that posted; blocks that took an
+ * update; voxels updated; cell visits lost to a block still absent (counted before the band test; the sum wraps at 2^32). */
+VK_API size_t vk_volume_integrate_rays_workspace_bytes(int32_t main, int32_t excess);
+VK_API int vk_volume_integrate_rays(const vk_volume* v, const float* rays /* device [6*count]: origin, direction */,
+    const float* ranges /* device [count] */, int32_t count, const vk_transform* pose_dev /* optional: T_volume_rays */,
+    const vk_integrate_rays_params* p, int32_t* counts_dev /* [8] */, void* workspace, void* stream);
+
+/* Measurement only: the next vk_volume_integrate_rays of this host thread records events[0 .. 5] (vk_event_create) on its
+ * stream in front of its first pass, behind the allocation rounds, the mark pass, the zero pass, the add pass and the fold,
+ * so that tools/integrate_rays_bench.py can say what each pass costs; no upstream counterpart (ref: the reference times its
+ * integrator from outside, src/depth_integrator.cu:89-115). One CALL only, as with vk_integrate_time_next: the events are used
+ * up by the next call even when it returns an error before its launches, and a call with count == 0 records none;
+ * (NULL, 0) cancels. `count` must be 6. Not a stream operation: nothing is enqueued by this call. */
+VK_API int vk_volume_integrate_rays_time_next(void* const* events, int32_t count);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

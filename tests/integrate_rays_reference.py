@@ -1,0 +1,318 @@
+"""The CPU statement of vk_volume_integrate_rays (include/vk.h): which blocks a batch of range rays allocates in a volume and
+what every voxel in the band of a measurement holds afterwards — in numpy, on an oracle.HostVolume. The band test, the
+min(1, d / truncation) and the running average are the reference integrator's (src/depth_integrator.cu:54-74), the blocks
+requested are those within one truncation length either side of the measurement (src/volume.cu:87-301), allocated through the
+oracle's handle pass (src/volume.cu:304-368) in vk_volume_merge's rounds. There is no upstream call for a measurement that is
+no pixel of a pinhole depth image, so this file is the definition.
+
+Everything is float32 with one rounding per operation, in the order vk.h gives (numpy's float32 arithmetic is exactly that),
+and what rays that share a voxel add up is an integer: no result depends on the order of the rays, no tolerance exists and
+the device is held to it bit for bit (tests/test_gpu_integrate_rays.py).
+
+It is vectorised over rays with a per-ray active mask, and it holds the ray sets the CPU and the GPU tests share."""
+import numpy as np
+
+import cast_reference as CR
+import merge_pose_reference as MP
+import merge_reference as M
+import register_reference as RR
+import release_reference as R
+from vulcan_amd import vk_types as T
+
+f32 = np.float32
+FAR = 1 << 30
+VOXEL_UNITS, ONE_OBSERVATION = T.VK_RAYS_VOXEL_UNITS, T.VK_RAYS_ONE_OBSERVATION
+MAX_COUNT = 1 << 22
+SCALE = f32(1048576.0)                                                # 2^20: a visit adds rintf(u * 2^20)
+INTEGRATED, NO_MEASUREMENT, INVALID = 0, 1, 2
+# what the tests integrate with: r_min below the truncation length, so a band may begin at the ray's origin
+R_MIN, R_MAX = 0.01, 5.0
+
+
+def carried(hv, rays, ranges, pose, r_min, r_max, voxel_units):
+    """(o [N, 3], n [N, 3], r [N], kind [N]): cast_rays' ray word for word, the range in voxels, and what the ray is"""
+    x = np.ascontiguousarray(rays, dtype=f32).reshape(-1, 6)
+    ranges = np.ascontiguousarray(ranges, dtype=f32).reshape(-1)
+    assert len(ranges) == len(x)
+    with np.errstate(all="ignore"):
+        L = f32(hv.voxel_length)
+        q, d = (x[:, :3] if voxel_units else x[:, :3] / L), x[:, 3:]
+        o = q
+        if pose is not None:
+            rows = MP.rows(pose.m, hv.voxel_length)
+            o = MP.apply(rows, q)
+            d = np.stack([(rows[a, 0] * d[:, 0] + rows[a, 1] * d[:, 1]) + rows[a, 2] * d[:, 2] for a in range(3)], -1)
+        length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        n = d / length[:, None]
+        valid = (np.abs(o) < f32(FAR)).all(-1) & np.isfinite(length) & np.isfinite(n).all(-1)
+        measured = (f32(r_min) <= ranges) & (ranges <= f32(r_max))                    # false for a NaN
+        r = ranges if voxel_units else ranges / L
+    assert o.dtype == f32 and n.dtype == f32 and r.dtype == f32
+    kind = np.where(valid, np.where(measured, INTEGRATED, NO_MEASUREMENT), INVALID)
+    return o, n, r, kind
+
+
+def walk(o, n, r, tr, branches=None):
+    """the exact traversal of the cells the rays cross inside their bands: (ray [M], cell [M, 3] int64), every visit of every
+    ray, in the order of the walk"""
+    count = len(o)
+    with np.errstate(all="ignore"):
+        ta, tb = np.fmax(r - tr, f32(0)), r + tr
+        p = o + ta[:, None] * n
+        c = np.clip(MP.to_int(np.floor(p)), -FAR, FAR)
+        pos, neg = n > 0, n < 0
+        face = np.where(pos, c + 1, c).astype(f32)
+        tmax = np.where(pos | neg, ta[:, None] + (face - p) / n, f32(np.inf)).astype(f32)
+        tdelta = np.where(pos | neg, f32(1) / np.abs(n), f32(np.inf)).astype(f32)
+        step = pos.astype(np.int64) - neg.astype(np.int64)
+        guard = 3 * (np.clip(MP.to_int(np.ceil(tb - ta)), 0, 1024) + 2)
+        assert tmax.dtype == f32 and tdelta.dtype == f32 and p.dtype == f32
+        if branches is not None:
+            branches["ta_clamped"] += int((r - tr < 0).sum())
+            branches["zero_component"] += int((n == 0).sum())
+            branches["negative_step"] += int(neg.sum())
+        who, cells = [], []
+        active = np.arange(count)
+        for turn in range(int(guard.max()) if count else 0):
+            active = active[turn < guard[active]]
+            if not len(active):
+                break
+            who.append(active)
+            cells.append(c[active].copy())
+            # the axis of the smallest tmax, x before y before z on a tie (a NaN is never the smaller)
+            t = tmax[active]
+            axis = np.zeros(len(active), dtype=np.int64)
+            least = t[:, 0]
+            for a in (1, 2):
+                smaller = t[:, a] < least
+                axis[smaller] = a
+                least = np.where(smaller, t[:, a], least)
+            if branches is not None:
+                branches["ties"] += int((np.isfinite(least) & ((t == least[:, None]).sum(-1) > 1)).sum())
+            go = least <= tb[active]
+            active, axis = active[go], axis[go]
+            c[active, axis] += step[active, axis]
+            tmax[active, axis] = tmax[active, axis] + tdelta[active, axis]
+    if not who:
+        return np.zeros(0, dtype=np.int64), np.zeros((0, 3), dtype=np.int64)
+    return np.concatenate(who), np.concatenate(cells)
+
+
+def in_int16(blocks):
+    return ((blocks >= -32768) & (blocks <= 32767)).all(-1)
+
+
+class Result:
+    """counts (the eight of vk.h), branches (how often each branch of the definition was taken), S and N (the sums per
+    pool voxel)"""
+
+
+def integrate(hv, rays, ranges, pose=None, r_min=R_MIN, r_max=R_MAX, cap=16.0, flags=0, max_rounds=8):
+    """Mutates `hv` as the call is defined. `flags`: VOXEL_UNITS | ONE_OBSERVATION. Returns a Result."""
+    voxel_units, one = bool(flags & VOXEL_UNITS), bool(flags & ONE_OBSERVATION)
+    assert 0 <= max_rounds <= 64 and 1 <= cap <= 32767 and 0 <= r_min < r_max and np.isfinite(r_max)
+    out = Result()
+    out.branches = b = dict(ta_clamped=0, zero_component=0, negative_step=0, ties=0, refused=0, u_clamped=0, outside_int16=0,
+                            lost=0, visits=0, shared_voxels=0, most_on_a_voxel=0)
+    count = len(np.asarray(ranges).reshape(-1))
+    assert count <= MAX_COUNT
+    if count == 0:
+        out.counts = None                                               # the counters' bytes are left alone
+        return out
+    L = f32(hv.voxel_length)
+    tr = f32(hv.truncation_length) / L
+    assert tr <= 64
+    o, n, r, kind = carried(hv, rays, ranges, pose, r_min, r_max, voxel_units)
+    fused = kind == INTEGRATED
+    o, n, r = o[fused], n[fused], r[fused]
+    who, cells = walk(o, n, r, tr, b)
+    blocks = cells >> 3
+    inside = in_int16(blocks)
+    b["visits"], b["outside_int16"] = len(who), int((~inside).sum())
+    who, cells, blocks = who[inside], cells[inside], blocks[inside]
+    wanted = [tuple(int(v) for v in origin) for origin in np.unique(blocks, axis=0)] if len(blocks) else []
+
+    # vk_volume_merge's rounds, the visited blocks in the place of the source blocks
+    present_before = sum(1 for origin in wanted if R.find(hv, origin) >= 0)
+    rounds = 0
+    for _ in range(max_rounds):
+        winners = {}
+        for origin in wanted:
+            if R.find(hv, origin) >= 0:
+                continue
+            bucket = M.bucket_of(origin, hv.main)
+            alloc = T.ALLOC_MAIN if hv.hash_entries["data"][bucket] == -1 else T.ALLOC_EXCESS
+            key = M.request_key(alloc, origin)
+            if bucket not in winners or key > winners[bucket][0]:
+                winners[bucket] = (key, alloc, origin)
+        if not winners:
+            break
+        rounds += 1
+        for bucket, (_, alloc, origin) in winners.items():
+            hv.allocation_types[bucket] = alloc
+            hv.allocation_blocks["origin"][bucket] = origin
+            hv.allocation_blocks["pad"][bucket] = alloc
+            if alloc == T.ALLOC_MAIN:
+                hv.block_visibility[bucket] = T.VISIBILITY_TRUE
+        dropped = int(hv.counters[T.VK_CTR_DROPPED])
+        hv.handle_allocation_requests()
+        if int(hv.counters[T.VK_CTR_DROPPED]) != dropped:
+            break
+    table = RR.block_table(hv)
+    present_after = sum(1 for origin in wanted if origin in table)
+
+    # the sums: integers, so their order does not matter
+    slot = CR.Lookup(table).slots(blocks) if len(blocks) else np.zeros(0, dtype=np.int64)
+    held = slot >= 0
+    b["lost"] = int((~held).sum())
+    who, cells, slot = who[held], cells[held], slot[held]
+    with np.errstate(all="ignore"):
+        e = cells.astype(f32) + f32(0.5)
+        oo, nn = o[who], n[who]
+        raw = r[who] - (((e[:, 0] - oo[:, 0]) * nn[:, 0] + (e[:, 1] - oo[:, 1]) * nn[:, 1]) + (e[:, 2] - oo[:, 2]) * nn[:, 2])
+        take = raw > -tr
+        u = np.fmin(f32(1), raw / tr)
+        assert raw.dtype == f32 and u.dtype == f32
+        q = np.rint(u * SCALE)
+    b["refused"], b["u_clamped"] = int((~take).sum()), int((take & (raw / tr > 1)).sum())
+    index = (slot * 512 + (cells[:, 2] & 7) * 64 + (cells[:, 1] & 7) * 8 + (cells[:, 0] & 7))[take]
+    S, N = np.zeros(hv.max * 512, dtype=np.int64), np.zeros(hv.max * 512, dtype=np.int64)
+    np.add.at(S, index, q[take].astype(np.int64))
+    np.add.at(N, index, 1)
+    out.S, out.N = S, N
+    b["shared_voxels"], b["most_on_a_voxel"] = int((N >= 2).sum()), int(N.max()) if len(N) else 0
+
+    # the fold: vk_volume_merge's running average with a source voxel of distance m and weight ws
+    at = np.flatnonzero(N > 0)
+    with np.errstate(all="ignore"):
+        m = (S[at].astype(f32) / N[at].astype(f32)) * f32(2.0 ** -20)
+        ws = np.ones(len(at), dtype=f32) if one else N[at].astype(f32)
+        wd = hv.voxels["distance_weight"][at].astype(f32)
+        total = wd + ws
+        mean = (wd * hv.voxels["distance"][at] + ws * m) / total
+        assert m.dtype == f32 and mean.dtype == f32
+        hv.voxels["distance"][at] = np.where(wd == 0, m, mean)
+        hv.voxels["distance_weight"][at] = np.minimum(f32(cap), total).astype(np.int16)
+    hv.counters[T.VK_CTR_VISIBLE] = 0
+    hv.counters[T.VK_CTR_BANDED] = -1
+    out.counts = (int(fused.sum()), int((kind == NO_MEASUREMENT).sum()), int((kind == INVALID).sum()),
+                  present_after - present_before, rounds, len(np.unique(at // 512)), len(at), b["lost"])
+    return out
+
+
+# ---- the ray sets the CPU and the GPU tests share ----------------------------------------------------------------------
+
+W, H = RR.W, RR.H
+_SETS, _HITS = {}, {}
+
+
+def pixel_rays(k=1):
+    """the fusing camera's pixel rays (the identity pose: the origin is 0), k x k per pixel of the 160 x 120 view, as
+    cast_reference.pixel_rays builds them: [H * W * k * k, 6], and the pixel of each"""
+    p = R.projection()
+    ys, xs = np.mgrid[0:H * k, 0:W * k]
+    ifx, ify = f32(1) / f32(p.fx), f32(1) / f32(p.fy)
+    u = (xs.reshape(-1).astype(f32) + f32(0.5)) / f32(k)
+    v = (ys.reshape(-1).astype(f32) + f32(0.5)) / f32(k)
+    rays = np.zeros((len(u), 6), dtype=f32)
+    rays[:, 3], rays[:, 4], rays[:, 5] = ifx * u - f32(p.cx) * ifx, ify * v - f32(p.cy) * ify, 1
+    return rays, xs.reshape(-1) // k, ys.reshape(-1) // k
+
+
+def pixel_hits(orc, k=1):
+    """(rays, t) of pixel_rays(k) cast through the scene volume by the statement of cast_rays: t == 0 where nothing is hit"""
+    if k not in _HITS:
+        rays = pixel_rays(k)[0]
+        _HITS[k] = (rays, CR.cast(CR.volume(orc), rays).t)
+    return _HITS[k]
+
+
+def ray_sets(orc, voxel_units):
+    """{name: (rays float32 [n, 6], ranges float32 [n])}, origins and ranges in the unit asked for (metres, or voxels), on
+    cast_reference.volume(orc): computed once. A set born in the other unit is converted in float32: whatever the conversion
+    rounds to is a ray like any other to the statement."""
+    if voxel_units in _SETS:
+        return _SETS[voxel_units]
+    hv = CR.volume(orc)
+    L = f32(hv.voxel_length)
+    rng = np.random.default_rng(47)
+    metres, voxels = {}, {}
+    # (a) the 160 x 120 pixel rays of the fusing camera with the ranges cast_rays gives them: 0 where nothing is hit
+    metres["a"] = pixel_hits(orc)
+    hit = np.flatnonzero(metres["a"][1] > 0)
+    # (b) 4 096 copies of one ray that hits
+    one = hit[len(hit) // 2]
+    metres["b"] = (np.repeat(metres["a"][0][one:one + 1], 4096, axis=0), np.repeat(metres["a"][1][one:one + 1], 4096))
+    # (c) along an axis, in both directions, from lattice points near held blocks; and along face and space diagonals from
+    # lattice points, where two or three tmax tie at every step
+    origins = np.array(list(RR.block_table(hv)), dtype=np.int64)
+    along = np.zeros((1200, 6), dtype=f32)
+    start = 8 * origins[rng.integers(0, len(origins), 1200)] + rng.integers(0, 8, (1200, 3))
+    along[:, :3] = start
+    axis, sign = rng.integers(0, 3, 800), rng.choice([-1.0, 1.0], 800)
+    along[np.arange(800), 3 + axis] = sign * rng.uniform(0.5, 2.0, 800)
+    along[800:, 3:] = rng.choice([-1.0, 0.0, 1.0], (400, 3))
+    along[800:][(along[800:, 3:] == 0).all(-1), 3] = 1
+    voxels["c"] = (along, rng.uniform(0.0, 30.0, 1200).astype(f32))               # ranges below tr: ta clamps at 0
+    # (d) random rays around the surface with random ranges
+    vertices = orc.extract_mesh(hv, all_allocated=True, interpolate=True)[0]
+    around = np.zeros((3000, 6), dtype=f32)
+    around[:, :3] = vertices[rng.integers(0, len(vertices), 3000)] + rng.uniform(-0.3, 0.3, (3000, 3))
+    around[:, 3:] = rng.normal(size=(3000, 3))
+    metres["d"] = (around, rng.uniform(R_MIN, 0.6, 3000).astype(f32))
+    # (e) valid rays without a measurement: 0, NaN, +-inf, below r_min, above r_max
+    nothing = np.repeat(metres["a"][0][one:one + 1], 12, axis=0)
+    metres["e"] = (nothing, np.array([0, -0.0, np.nan, np.inf, -np.inf, 0.005, 0.00999, -1.0, 5.001, 7.0, 1e30, 1e-30], dtype=f32))
+    # (f) cast_rays' 25 invalid rays, with a range that would count
+    bad = CR.ray_sets(orc, False)["f"]
+    metres["f"] = (bad, np.full(len(bad), 1.0, dtype=f32))
+    # (g) far away: bands that cross the end of the int16 range of block coordinates, and bands wholly beyond it
+    far = np.zeros((64, 6), dtype=f32)
+    far[:, :3] = rng.integers(-40, 40, (64, 3))
+    edge = rng.integers(0, 3, 64)
+    side = rng.choice([-1.0, 1.0], 64)
+    far[np.arange(64), edge] = side * (8 * 32768 - rng.integers(0, 60, 64))
+    far[:, 3:] = rng.normal(size=(64, 3)) * 0.2
+    far[np.arange(64), 3 + edge] = side
+    voxels["g"] = (far, rng.uniform(20.0, 80.0, 64).astype(f32))
+    with np.errstate(all="ignore"):
+        for name in "abcdefg":
+            if name in metres:
+                rays, ranges = metres[name]
+                there = rays.copy()
+                there[:, :3] = rays[:, :3] / L
+                voxels[name] = (there, ranges / L)
+            else:
+                rays, ranges = voxels[name]
+                there = rays.copy()
+                there[:, :3] = rays[:, :3] * L
+                metres[name] = (there, ranges * L)
+    _SETS[False], _SETS[True] = metres, voxels
+    return _SETS[voxel_units]
+
+
+def spans(orc):
+    sets, at, out = ray_sets(orc, False), 0, {}
+    for name in "abcdefg":
+        out[name] = slice(at, at + len(sets[name][1]))
+        at += len(sets[name][1])
+    return out
+
+
+def all_rays(orc, voxel_units):
+    """(rays [N, 6], ranges [N]): every set, one after the other"""
+    sets = ray_sets(orc, voxel_units)
+    return (np.ascontiguousarray(np.concatenate([sets[name][0] for name in "abcdefg"]), dtype=f32),
+            np.ascontiguousarray(np.concatenate([sets[name][1] for name in "abcdefg"]), dtype=f32))
+
+
+def bounds(voxel_units, voxel_length=R.VOXEL):
+    """(r_min, r_max) in the unit the form takes them in"""
+    if not voxel_units:
+        return float(f32(R_MIN)), float(f32(R_MAX))
+    return float(f32(R_MIN) / f32(voxel_length)), float(f32(R_MAX) / f32(voxel_length))
+
+
+def permuted(rays, ranges, seed=5):
+    order = np.random.default_rng(seed).permutation(len(ranges))
+    return np.ascontiguousarray(rays[order]), np.ascontiguousarray(ranges[order])

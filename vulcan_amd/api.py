@@ -129,6 +129,9 @@ _SIGNATURES = {
     "vk_volume_register": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_sample": ([_P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
     "vk_volume_cast_rays": ([_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_integrate_rays_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
+    "vk_volume_integrate_rays": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
+    "vk_volume_integrate_rays_time_next": ([_P, C.c_int32], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -791,6 +794,67 @@ class Volume:
         flags = (T.VK_CAST_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_CAST_DISTANCE_ONLY)
         t, status, samples, gradients = self._cast_call(rays, pose, flags, t_min, t_max, max_steps, True, bool(gradient), rays.shape[0])
         return RayHits(t, status, samples, gradients, bool(color), self.truncation_length)
+
+    _rays_workspace = None      # device bytes of vk_volume_integrate_rays, allocated by the first call
+    _rays_counts = None
+
+    def _integrate_rays_call(self, rays, ranges, pose=None, flags=0, max_rounds=8, r_min=0.1, r_max=5.0, max_distance_weight=16.0,
+                             count=None):
+        """one vk_volume_integrate_rays of `rays` and `ranges` (float32 device tensors of 6 * count and count floats or more):
+        the eight counts from one blocking read. `pose`: a T.Transform (uploaded), a device buffer that holds a vk_transform,
+        or None."""
+        import torch
+        self._no_requests_pending("integrate_rays")
+        count = ranges.numel() if count is None else int(count)
+        if isinstance(pose, T.Transform):
+            if self._sample_pose is None:
+                self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
+            check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
+            pose = self._sample_pose
+        if self._rays_workspace is None:
+            self._rays_workspace = _dev_bytes(lib().vk_volume_integrate_rays_workspace_bytes(self.main, self.excess), self.device)
+            self._rays_counts = torch.zeros(8, dtype=torch.int32, device=self.device)
+        params = T.IntegrateRaysParams(int(flags), int(max_rounds), float(r_min), float(r_max), float(max_distance_weight), 0)
+        self._view_changed()
+        if self.light_prep is not None:
+            self.light_prep.valid = 0
+        check(lib().vk_volume_integrate_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(pose), _ref(params),
+                                             _ptr(self._rays_counts), _ptr(self._rays_workspace), stream()), "vk_volume_integrate_rays")
+        return tuple(int(c) for c in self._rays_counts.cpu().numpy())
+
+    def integrate_rays(self, rays, ranges, pose=None, r_min=None, r_max=None, max_distance_weight=16, one_observation=False,
+                       voxel_units=False, max_rounds=8):
+        """vk_volume_integrate_rays (not upstream): fuse range measurements along arbitrary rays — a LiDAR sweep, a fisheye
+        depth camera, a point cloud seen from known origins, or what cast_rays returned for another volume. `rays` is a
+        float32 [N, 6] device tensor of origins and directions (any length), `ranges` a float32 [N] device tensor of
+        distances along the normalised directions — origins and ranges in metres, or in voxels with `voxel_units` — in the
+        frame that `pose` (a Transform, a 4x4 array, or a device buffer holding a vk_transform; None: the volume's own frame)
+        carries into the volume's. A ray whose range lies outside [`r_min`, `r_max`] (None: the volume's depth range), a NaN
+        included, carries no measurement and is skipped: cast_rays' t == 0 feeds in unchanged. The blocks within one
+        truncation length either side of a measurement are allocated (`max_rounds` rounds of requests and handle pass; 0:
+        only blocks that exist are updated), then every voxel whose cell a ray crosses inside that band continues its running
+        average with the mean of what the rays through it measured, weighted with their number (`one_observation`: with 1),
+        the weight capped at `max_distance_weight`. Colours are left alone. The result does not depend on the order of the
+        rays. Between SetView calls only: raises while a frame is announced. The visible list is empty afterwards (the next
+        set_view rebuilds it) and what was prepared ahead for this volume is void. Returns (rays integrated, valid rays
+        without a measurement, invalid rays, blocks allocated, rounds that posted a request, blocks updated, voxels updated,
+        cell visits lost to a block that could not be allocated)."""
+        import torch
+        if not (hasattr(rays, "data_ptr") and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6):
+            raise VkError("integrate_rays: rays is a float32 [N, 6] device tensor")
+        if not (hasattr(ranges, "data_ptr") and ranges.dtype == torch.float32 and ranges.dim() == 1 and ranges.shape[0] == rays.shape[0]):
+            raise VkError("integrate_rays: ranges is a float32 [N] device tensor, one range per ray")
+        rays, ranges = rays.contiguous(), ranges.contiguous()
+        if pose is not None and not isinstance(pose, T.Transform) and not hasattr(pose, "data_ptr"):
+            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
+        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
+        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
+        flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
+        if rays.shape[0] == 0:
+            return (0,) * 8
+        return self._integrate_rays_call(rays, ranges, pose, flags, max_rounds, r_min, r_max, max_distance_weight, rays.shape[0])
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

@@ -124,6 +124,30 @@ struct Ray
   Vector3f direction;           // any length; a zero or non-finite direction is VK_RAY_INVALID
 };
 
+// Not upstream: how Volume::IntegrateRays reads its rays and ranges and what it fuses (vk_integrate_rays_params)
+struct IntegrateRaysOptions
+{
+  bool voxel_units = false;           // the origins, the ranges, r_min and r_max are in voxels, not metres
+  bool one_observation = false;       // a voxel's mean counts as one observation, not as one per ray through it
+  float r_min = 0.1f;                 // a ray whose range lies outside [r_min, r_max] (a NaN included) carries no
+  float r_max = 5.0f;                 //   measurement and is skipped: CastRays' t == 0 feeds in unchanged
+  float max_distance_weight = 16.0f;  // the cap an integrator would apply (integrator.cu:7-13)
+  int max_rounds = 8;                 // allocation rounds; 0: only blocks that exist are updated
+};
+
+// Volume::IntegrateRays (vk_volume_integrate_rays' eight counts)
+struct IntegrateRaysCounts
+{
+  int integrated;       // valid rays with a measurement
+  int unmeasured;       // valid rays without one
+  int invalid;          // rays CastRays would call VK_RAY_INVALID
+  int allocated;        // blocks this volume did not have before
+  int rounds;           // allocation rounds that posted a request
+  int blocks;           // blocks that took an update
+  int voxels;           // voxels updated
+  int lost;             // cell visits lost to a block that found no room
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -224,6 +248,19 @@ class Volume
     void CastRays(const Ray* rays_dev, int count, float* t_dev, int* status_dev, Voxel* samples_dev = nullptr,
         Vector4f* gradients_dev = nullptr, const Transform* pose = nullptr, const CastOptions& options = CastOptions()) const;
 
+    // Not upstream: fuse `count` range measurements along arbitrary rays (vk_volume_integrate_rays) — a LiDAR sweep, a
+    // fisheye depth camera, a point cloud seen from known origins, or what CastRays returned for another volume.
+    // ranges_dev[i] is the distance along the normalised direction of rays_dev[i], both in the frame that `pose` (null:
+    // the volume's own) carries into the volume's. The blocks within one truncation length either side of a measurement
+    // are allocated, then every voxel whose cell a ray crosses inside that band continues its running average with the
+    // mean of what the rays through it measured; colours are left alone, and the order of the rays does not matter.
+    // Between SetView calls only: throws while a frame announced by Tracer::Trace(keyframe, next_frame) is outstanding.
+    // The visible list is empty afterwards (the next SetView rebuilds it); the raycast bounds and the light preparation
+    // made ahead are void. Both buffers are device memory and only read. Blocking readbacks (the eight counts,
+    // VK_CTR_DROPPED); count == 0 does nothing.
+    IntegrateRaysCounts IntegrateRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform* pose = nullptr,
+        const IntegrateRaysOptions& options = IntegrateRaysOptions());
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -288,7 +325,9 @@ class Volume
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
     Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
     Buffer<int> register_ints_;                    // the state (2), the counts (4)
-    mutable Buffer<float> sample_pose_;            // Sample, CastRays: the pose on the device (32)
+    mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays: the pose on the device (32)
+    Buffer<unsigned char> rays_workspace_;         // IntegrateRays: allocated by the first call
+    Buffer<int> rays_counts_;
 
     Vector2f depth_range_;
     int max_block_count_;

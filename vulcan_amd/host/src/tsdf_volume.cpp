@@ -537,6 +537,55 @@ void Volume::CastRays(const Ray* rays_dev, int count, float* t_dev, int* status_
       reinterpret_cast<vk_voxel*>(samples_dev), reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
 }
 
+IntegrateRaysCounts Volume::IntegrateRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform* pose,
+    const IntegrateRaysOptions& options)
+{
+  static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
+  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+  IntegrateRaysCounts out = {};
+  vk_integrate_rays_params p;
+  p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+  p.max_rounds = options.max_rounds;
+  p.r_min = options.r_min;
+  p.r_max = options.r_max;
+  p.max_distance_weight = options.max_distance_weight;
+  p.pad = 0;
+  const size_t bytes = vk_volume_integrate_rays_workspace_bytes(main_block_count_, excess_block_count_);
+  if (rays_workspace_.GetSize() != bytes) rays_workspace_.Resize(bytes);
+  if (rays_counts_.GetSize() == 0) rays_counts_.Resize(8);
+  const vk_transform* pose_dev = nullptr;
+  if (pose && count > 0)
+  {
+    if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
+    const vk_transform seed = pose->ToVk();
+    VK_ASSERT(vk_transform_upload(reinterpret_cast<vk_transform*>(sample_pose_.GetData()), &seed, Device::GetStream()));
+    pose_dev = reinterpret_cast<const vk_transform*>(sample_pose_.GetData());
+  }
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_integrate_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose_dev, &p, rays_counts_.GetData(),
+      rays_workspace_.GetData(), Device::GetStream()));
+  if (count == 0) return out;                      // nothing was launched and the counts were not written
+  // what was made ahead for the old table and visible list is void
+  view_bounds_.valid = 0;
+  light_prep_.valid = 0;
+  int32_t counts[8];
+  rays_counts_.CopyToHost(counts);
+  out.integrated = counts[0];
+  out.unmeasured = counts[1];
+  out.invalid = counts[2];
+  out.allocated = counts[3];
+  out.rounds = counts[4];
+  out.blocks = counts[5];
+  out.voxels = counts[6];
+  out.lost = counts[7];
+  int32_t counters[VK_CTR_PUBLIC];
+  GetCounters(counters);
+  NotePoolExhaustion(counters[VK_CTR_DROPPED]);
+  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
+  visible_count_stale_ = false;
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");

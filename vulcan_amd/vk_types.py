@@ -29,6 +29,7 @@ VK_REGISTER_NO_OVERLAP = 2                                                      
 VK_SAMPLE_VOXEL_UNITS, VK_SAMPLE_DISTANCE_ONLY = 1, 2                            # vk_sample_params.flags
 VK_CAST_VOXEL_UNITS, VK_CAST_DISTANCE_ONLY = 1, 2                                # vk_cast_params.flags
 VK_RAY_MISS, VK_RAY_HIT, VK_RAY_STEPS, VK_RAY_INVALID = 0, 1, 2, 3               # vk_volume_cast_rays: status[i]
+VK_RAYS_VOXEL_UNITS, VK_RAYS_ONE_OBSERVATION = 1, 2                              # vk_integrate_rays_params.flags
 
 voxel_dtype = np.dtype([("distance", "<f4"), ("color", "<f4", (3,)),
                         ("distance_weight", "<i2"), ("color_weight", "<i2")])
@@ -233,6 +234,13 @@ class CastParams(C.Structure):
     """vk_cast_params (vk.h): the units of vk_volume_cast_rays' origins and bounds, whether the colour is sampled, and the
     bounds of the march"""
     _fields_ = [("flags", C.c_int32), ("max_steps", C.c_int32), ("t_min", C.c_float), ("t_max", C.c_float)]
+
+
+class IntegrateRaysParams(C.Structure):
+    """vk_integrate_rays_params (vk.h): the units of vk_volume_integrate_rays' origins and ranges, the weight of a voxel's
+    mean, the allocation rounds, which ranges are measurements and the cap of the distance weight"""
+    _fields_ = [("flags", C.c_int32), ("max_rounds", C.c_int32), ("r_min", C.c_float), ("r_max", C.c_float),
+                ("max_distance_weight", C.c_float), ("pad", C.c_int32)]
 
 
 class PyramidAhead(C.Structure):
