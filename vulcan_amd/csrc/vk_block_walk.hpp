@@ -1,9 +1,16 @@
-// vk_block_walk.hpp — what the passes that carry a point into a volume's lattice share (vk_merge_pose.hip,
-// vk_register.hip, vk_sample.hip, vk_cast.hip): the pose as three rows in voxel units, the chain walk that finds a block,
-// the lattice cell a carried point falls into, the trilinear value and gradient over a cell's eight values, the cell of a
-// point read from the pool as vk_volume_sample defines it, and the host's checks of a volume. The definitions are in
-// include/vk.h at vk_volume_merge_posed (coordinates, chain walk, absent beyond the int16 range, the value),
-// vk_volume_register (the gradient) and vk_volume_sample (the sample of a point).
+// vk_block_walk.hpp — what the operations on a voxel-hashed volume share (vk_merge.hip, vk_merge_pose.hip, vk_register.hip,
+// vk_sample.hip, vk_cast.hip, vk_integrate_rays.hip; the allocation rounds are in vk_alloc_rounds.hpp beside it):
+//   wave_add, wave_min                      sums and minima over a wave
+//   voxel_rows, carry_rows, apply           the pose as three rows in voxel units, and a point through them
+//   find_block, mark_chain                  the chain walk that finds a block; the one that lists a bucket's blocks
+//   Ray, load_ray, finite3, cell_of, kFar   a ray in the volume's frame, and the cell of a point
+//   Lattice, lattice_at, lattice_of         the lattice cell a carried point falls into
+//   fill_directory                          the 4x4x4 blocks under one carried block, as slots in LDS
+//   trilinear, trilinear_gradient           the value and gradient over a cell's eight values
+//   Cell, read_cell, store_sample, store_gradient   the cell of a point read from the pool as vk_volume_sample defines it
+//   volume_ok, volumes_match                the host's checks of a volume and of a pair
+// The definitions are in include/vk.h at vk_volume_merge_posed (coordinates, chain walk, absent beyond the int16 range,
+// the value), vk_volume_register (the gradient), vk_volume_sample (the sample of a point) and vk_volume_cast_rays (the ray).
 #pragma once
 
 #include "vk_requests.hpp"
@@ -29,6 +36,29 @@ __device__ __forceinline__ int wave_min(int v)
 {
   for (int d = 32; d > 0; d >>= 1) v = vmini(v, __shfl_xor(v, d));
   return v;
+}
+
+// rows 0-2 of a column-major 4x4, the translation in voxels
+__host__ __device__ __forceinline__ void carry_rows(const float* m, float voxel_length, float rows[12])
+{
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+  {
+    rows[4 * a + 0] = m[a];
+    rows[4 * a + 1] = m[4 + a];
+    rows[4 * a + 2] = m[8 + a];
+    rows[4 * a + 3] = m[12 + a] / voxel_length;
+  }
+}
+__device__ __forceinline__ void carry_rows(const vk_transform* t, float voxel_length, float rows[12]) { carry_rows(t->m, voxel_length, rows); }
+
+// the host's: false when one of the twelve is not finite
+inline bool voxel_rows(const float* m, float voxel_length, float* rows)
+{
+  for (int i = 0; i < 16; ++i)
+    if ((i & 3) != 3 && !isfinite(m[i])) return false;
+  carry_rows(m, voxel_length, rows);
+  return true;
 }
 
 // row a of `r`: m[a], m[4+a], m[8+a], the translation in voxels
@@ -66,6 +96,72 @@ __device__ __forceinline__ int find_block(const vk_volume& v, int total, int bx,
   return -1;
 }
 
+// The source blocks of one main bucket: an entry with data >= 0 that is reachable from the bucket along `next`. A link that
+// leaves the table ends the chain and no chain is longer than the table (as in vk_release.hip). mark(index) per such entry;
+// how many there were (0 for a thread beyond the last bucket).
+template <class Mark>
+__device__ __forceinline__ int mark_chain(const vk_volume& v, int total, int bucket, Mark&& mark)
+{
+  int blocks = 0;
+  if (bucket >= v.main_block_count) return blocks;
+  int index = bucket;
+  for (int guard = 0; index >= 0 && index < total && guard < total; ++guard)
+  {
+    const Entry entry = load_entry(v.hash_entries, (uint32_t)index);
+    if (entry.data >= 0 && entry.data < total)
+    {
+      mark(index);
+      ++blocks;
+    }
+    index = entry.next;
+  }
+  return blocks;
+}
+
+constexpr int kFar = 1 << 30;                  // a coordinate is clamped here, so that the next cell is still an int
+
+__device__ __forceinline__ bool finite3(f3 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+
+// the cell a coordinate lies in
+__device__ __forceinline__ int cell_of(float p) { return vclampi(f2i(floorf(p)), -kFar, kFar); }
+
+// Ray i of a [6 * count] array as vk_volume_cast_rays defines it: origin and unit direction in voxels, in the volume's frame.
+// The origin is divided by the voxel length unless `voxel_units` and goes through the pose, the direction through its
+// rotation only. `valid`: the origin within 2^30 and a finite unit direction.
+struct Ray
+{
+  f3 o, n;
+  bool valid;
+};
+
+__device__ __forceinline__ Ray load_ray(const float* rays, size_t i, const vk_transform* pose, float voxel_length, bool voxel_units)
+{
+  const float* x = rays + i * 6;
+  float q0 = x[0], q1 = x[1], q2 = x[2];
+  float d0 = x[3], d1 = x[4], d2 = x[5];
+  if (!voxel_units)
+  {
+    q0 = q0 / voxel_length;
+    q1 = q1 / voxel_length;
+    q2 = q2 / voxel_length;
+  }
+  Ray ray;
+  ray.o = f3{q0, q1, q2};
+  if (pose)
+  {
+    float fwd[12];
+    carry_rows(pose, voxel_length, fwd);
+    ray.o = apply(fwd, q0, q1, q2);
+    const float r0 = (fwd[0] * d0 + fwd[1] * d1) + fwd[2] * d2, r1 = (fwd[4] * d0 + fwd[5] * d1) + fwd[6] * d2,
+                r2 = (fwd[8] * d0 + fwd[9] * d1) + fwd[10] * d2;
+    d0 = r0;  d1 = r1;  d2 = r2;
+  }
+  const float len = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+  ray.n = f3{d0 / len, d1 / len, d2 / len};
+  ray.valid = fabsf(ray.o.x) < (float)kFar && fabsf(ray.o.y) < (float)kFar && fabsf(ray.o.z) < (float)kFar && isfinite(len) && finite3(ray.n);
+  return ray;
+}
+
 struct Lattice
 {
   int bx, by, bz;               // floorf(g)
@@ -78,7 +174,6 @@ __device__ __forceinline__ Lattice lattice_at(f3 p)
 {
   const float gx = p.x - 0.5f, gy = p.y - 0.5f, gz = p.z - 0.5f;
   const float qx = floorf(gx), qy = floorf(gy), qz = floorf(gz);
-  constexpr int kFar = 1 << 30;
   return Lattice{vclampi(f2i(qx), -kFar, kFar), vclampi(f2i(qy), -kFar, kFar), vclampi(f2i(qz), -kFar, kFar), gx - qx, gy - qy, gz - qz};
 }
 
@@ -86,6 +181,36 @@ __device__ __forceinline__ Lattice lattice_at(f3 p)
 __device__ __forceinline__ Lattice lattice_of(const float* rows, int ox, int oy, int oz, int x, int y, int z)
 {
   return lattice_at(apply(rows, (float)(8 * ox + x) + 0.5f, (float)(8 * oy + y) + 0.5f, (float)(8 * oz + z) + 0.5f));
+}
+
+constexpr int kFootprint = 4;                  // blocks per axis under one block carried through a rigid pose
+static_assert(kFootprint * kFootprint * kFootprint == kWave, "one lane per directory cell");
+
+// One wave, eight voxels per lane (lane = 8 y + x). Under a rigid pose the lattice points of the 512 samples of block `mine`
+// carried through `rows` lie in at most 4^3 blocks of `v` from the least one: lane k walks the chain of cell k once and
+// leaves the slot (-1: absent) in the wave's 64-word LDS `directory`, cell (rx, ry, rz) at rx + 4 ry + 16 rz.
+__device__ __forceinline__ void fill_directory(const vk_volume& v, int total, const float* rows, const Entry& mine, int* directory,
+    int& least_x, int& least_y, int& least_z)
+{
+  const int lane = lane_id();
+  least_x = least_y = least_z = INT32_MAX;
+#pragma unroll
+  for (int z = 0; z < 8; ++z)
+  {
+    const Lattice l = lattice_of(rows, mine.ox, mine.oy, mine.oz, lane & 7, lane >> 3, z);
+    least_x = vmini(least_x, l.bx >> 3);
+    least_y = vmini(least_y, l.by >> 3);
+    least_z = vmini(least_z, l.bz >> 3);
+  }
+  least_x = wave_min(least_x);
+  least_y = wave_min(least_y);
+  least_z = wave_min(least_z);
+  const int sx = least_x + (lane & 3), sy = least_y + ((lane >> 2) & 3), sz = least_z + (lane >> 4);
+  int slot = -1;
+  Entry main_entry;
+  if (in_int16(sx, sy, sz)) find_block(v, total, sx, sy, sz, slot, main_entry);
+  directory[lane] = slot;
+  wave_lds_fence();
 }
 
 // the value, vk_volume_merge_posed's spelling: an axis with f == 0 takes its base value
@@ -249,8 +374,6 @@ __device__ __forceinline__ void store_gradient(const Cell& c, float* gradient)
   *reinterpret_cast<vf4*>(gradient) = g;
 }
 
-inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 inline bool volume_ok(const vk_volume* v)
 {
   return v && v->voxels && v->hash_entries && v->free_voxel_blocks && v->allocation_types && v->allocation_blocks &&
@@ -260,6 +383,13 @@ inline bool volume_ok(const vk_volume* v)
          (reinterpret_cast<uintptr_t>(v->counters) & 7) == 0 && (reinterpret_cast<uintptr_t>(v->allocation_blocks) & 7) == 0 &&
          (reinterpret_cast<uintptr_t>(v->hash_entries) & 15) == 0 && (reinterpret_cast<uintptr_t>(v->voxels) & 15) == 0 &&
          (reinterpret_cast<uintptr_t>(v->block_visibility) & 3) == 0 && (reinterpret_cast<uintptr_t>(v->allocation_types) & 15) == 0;
+}
+
+// two volumes one lattice can be carried between: the same voxel and truncation length, bit for bit
+inline bool volumes_match(const vk_volume* dst, const vk_volume* src)
+{
+  return volume_ok(dst) && volume_ok(src) && memcmp(&dst->voxel_length, &src->voxel_length, sizeof(float)) == 0 &&
+         memcmp(&dst->truncation_length, &src->truncation_length, sizeof(float)) == 0;
 }
 
 }  // namespace vk

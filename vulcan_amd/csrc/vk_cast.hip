@@ -35,8 +35,6 @@ struct CastParams
   float* gradients;             // [4 * count], or null
 };
 
-__device__ __forceinline__ bool finite3(f3 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
-
 __device__ __forceinline__ f3 along(f3 o, float t, f3 n) { return f3{o.x + t * n.x, o.y + t * n.y, o.z + t * n.z}; }
 
 // vk_volume_sample's distance sample at p (the USED rule): does it exist, and its value
@@ -63,46 +61,19 @@ __global__ __launch_bounds__(kThreads) void cast_kernel(CastParams P)
 {
   const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= (size_t)P.count) return;
-  const float* x = P.rays + i * 6;
-  float q0 = x[0], q1 = x[1], q2 = x[2];
-  float d0 = x[3], d1 = x[4], d2 = x[5];
   const float voxel_length = P.v.voxel_length;
   const float tr = P.v.truncation_length / voxel_length;
   float t = P.t_min, t1 = P.t_max;
   if (!P.voxel_units)
   {
-    q0 = q0 / voxel_length;
-    q1 = q1 / voxel_length;
-    q2 = q2 / voxel_length;
     t = t / voxel_length;
     t1 = t1 / voxel_length;
   }
-  f3 o = f3{q0, q1, q2};
-  if (P.pose)
-  {
-    const float* m = P.pose->m;
-    float fwd[12];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-    {
-      fwd[4 * a + 0] = m[a];
-      fwd[4 * a + 1] = m[4 + a];
-      fwd[4 * a + 2] = m[8 + a];
-      fwd[4 * a + 3] = m[12 + a] / voxel_length;
-    }
-    o = apply(fwd, q0, q1, q2);
-    // the direction goes through the rotation only
-    const float r0 = (fwd[0] * d0 + fwd[1] * d1) + fwd[2] * d2, r1 = (fwd[4] * d0 + fwd[5] * d1) + fwd[6] * d2,
-                r2 = (fwd[8] * d0 + fwd[9] * d1) + fwd[10] * d2;
-    d0 = r0;  d1 = r1;  d2 = r2;
-  }
-  const float len = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-  const f3 n = f3{d0 / len, d1 / len, d2 / len};
-  constexpr int kFar = 1 << 30;
-  const bool valid = fabsf(o.x) < (float)kFar && fabsf(o.y) < (float)kFar && fabsf(o.z) < (float)kFar && isfinite(len) && finite3(n);
+  const Ray ray = load_ray(P.rays, i, P.pose, voxel_length, P.voxel_units != 0);
+  const f3 o = ray.o, n = ray.n;
 
   int status = VK_RAY_INVALID;
-  if (valid)
+  if (ray.valid)
   {
     const uint32_t* pool = reinterpret_cast<const uint32_t*>(P.v.voxels);
     bool armed = false, held = false;
@@ -113,8 +84,7 @@ __global__ __launch_bounds__(kThreads) void cast_kernel(CastParams P)
       if (steps == P.max_steps) { status = VK_RAY_STEPS; break; }
       const f3 p = along(o, t, n);
       if (!finite3(p)) { status = VK_RAY_MISS; break; }
-      const int cx = vclampi(f2i(floorf(p.x)), -kFar, kFar), cy = vclampi(f2i(floorf(p.y)), -kFar, kFar),
-                cz = vclampi(f2i(floorf(p.z)), -kFar, kFar);
+      const int cx = cell_of(p.x), cy = cell_of(p.y), cz = cell_of(p.z);
       const int bx = cx >> 3, by = cy >> 3, bz = cz >> 3;
       if (!held || bx != held_x || by != held_y || bz != held_z)
       {

@@ -46,6 +46,9 @@
 
 static inline hipStream_t vk_s(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
 
+// every part of a workspace starts on a 256-byte boundary
+inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
+
 // a field of vk_test_hooks (vk.h), by position; defined in vk_runtime.hip
 enum { VK_HOOK_POSTED_CAPACITY = 0, VK_HOOK_RETRY_CAPACITY, VK_HOOK_SET_VIEW_UNFUSED, VK_HOOK_FORCE_LOOP_ABORT,
        VK_HOOK_LOOP_GRID_CAP, VK_HOOK_LOOP_COOPERATIVE, VK_HOOK_FORCE_NORMALS_EXPIRY };

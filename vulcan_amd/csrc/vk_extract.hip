@@ -571,8 +571,6 @@ __global__ __launch_bounds__(kExtractThreads) void attributes_kernel(ExtractPara
   }
 }
 
-inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {

@@ -14,14 +14,14 @@
 // of the previous cell and its slot kept in registers, so a chain is walked once per block (about eight cells), not per cell.
 //   snapshot  per table entry: which pool slots hold a block before the call (the count of blocks allocated needs it)
 //   rounds    max_rounds times: rays walk and post a request for every absent block (the largest key wins the bucket),
-//             the existing handle pass, round end — vk_merge.hip's rounds with the visited blocks for the source blocks
+//             the existing handle pass, round end (run_rounds, vk_alloc_rounds.hpp)
 //   mark      rays walk and set a byte per pool slot they visit: a plain store of a value every writer agrees on
 //   zero      one wave per marked slot zeroes its 512 accumulators
 //   add       rays walk and add, one atomic per update (two from 2^21 rays on); the three ray counts and the visits lost
 //   fold      one wave per marked slot: the voxels with a count continue their running average with the mean
 //   finish    the eight counts, VK_CTR_VISIBLE and VK_CTR_BANDED
 // Every loop is bounded: the walk by its guard G, a chain walk by the table size. No workgroup waits on another.
-#include "vk_block_walk.hpp"
+#include "vk_alloc_rounds.hpp"
 
 using namespace vk;
 
@@ -29,7 +29,6 @@ namespace
 {
 
 constexpr int kThreads = 256;
-constexpr int kFar = 1 << 30;
 constexpr int kMaxCount = 1 << 22;
 constexpr int kPackedCount = 1 << 21;       // below this many rays a voxel's N and biased sum share one 64-bit word
 constexpr int kCountShift = 43;
@@ -37,9 +36,8 @@ constexpr int kBias = 1 << 20;
 constexpr int kMaxGuardCells = 1024;         // ceilf(tb - ta) saturates here; tb - ta <= 4 tr <= 256, so it never does
 
 enum : uint8_t { kHeldBefore = 1, kVisited = 2 };
-// the words that steer the rounds and carry the sums
-enum { cStop = 0, cPosted, cRounds, cSavedRequests, cDroppedBefore, cIntegrated, cNoMeasurement, cInvalid, cAllocated, cBlocks,
-       cVoxels, cLost, cWords = 16 };
+// the words that carry the sums, behind the ones that steer the rounds
+enum { cIntegrated = cRoundWords, cNoMeasurement, cInvalid, cAllocated, cBlocks, cVoxels, cLost, cWords = 16 };
 struct RaysParams
 {
   vk_volume v;
@@ -60,57 +58,21 @@ struct RaysParams
 
 enum { kIntegrated = 0, kNoMeasurement = 1, kInvalid = 2 };
 
-struct Ray
+// vk_volume_cast_rays' ray (load_ray), and its range
+struct RangeRay : Ray
 {
-  f3 o, n;                      // origin and unit direction, in voxels, in the volume's frame
   float r;                      // the range in voxels
   int kind;
 };
 
-__device__ __forceinline__ bool finite3(f3 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
-
-// vk_volume_cast_rays' ray word for word (vk_cast.hip), and its range
-__device__ __forceinline__ Ray load_ray(const RaysParams& P, size_t i)
+__device__ __forceinline__ RangeRay load_range_ray(const RaysParams& P, size_t i)
 {
-  const float* x = P.rays + i * 6;
-  float q0 = x[0], q1 = x[1], q2 = x[2];
-  float d0 = x[3], d1 = x[4], d2 = x[5];
+  RangeRay ray;
+  static_cast<Ray&>(ray) = load_ray(P.rays, i, P.pose, P.v.voxel_length, P.voxel_units != 0);
   const float range = P.ranges[i];
-  const float voxel_length = P.v.voxel_length;
-  Ray ray;
-  ray.r = range;
-  if (!P.voxel_units)
-  {
-    q0 = q0 / voxel_length;
-    q1 = q1 / voxel_length;
-    q2 = q2 / voxel_length;
-    ray.r = range / voxel_length;
-  }
-  ray.o = f3{q0, q1, q2};
-  if (P.pose)
-  {
-    const float* m = P.pose->m;
-    float fwd[12];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-    {
-      fwd[4 * a + 0] = m[a];
-      fwd[4 * a + 1] = m[4 + a];
-      fwd[4 * a + 2] = m[8 + a];
-      fwd[4 * a + 3] = m[12 + a] / voxel_length;
-    }
-    ray.o = apply(fwd, q0, q1, q2);
-    // the direction goes through the rotation only
-    const float r0 = (fwd[0] * d0 + fwd[1] * d1) + fwd[2] * d2, r1 = (fwd[4] * d0 + fwd[5] * d1) + fwd[6] * d2,
-                r2 = (fwd[8] * d0 + fwd[9] * d1) + fwd[10] * d2;
-    d0 = r0;  d1 = r1;  d2 = r2;
-  }
-  const float len = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-  ray.n = f3{d0 / len, d1 / len, d2 / len};
-  const bool valid = fabsf(ray.o.x) < (float)kFar && fabsf(ray.o.y) < (float)kFar && fabsf(ray.o.z) < (float)kFar && isfinite(len) &&
-                     finite3(ray.n);
+  ray.r = P.voxel_units ? range : range / P.v.voxel_length;
   const bool measured = P.r_min <= range && range <= P.r_max;         // false for a NaN
-  ray.kind = valid ? (measured ? kIntegrated : kNoMeasurement) : kInvalid;
+  ray.kind = ray.valid ? (measured ? kIntegrated : kNoMeasurement) : kInvalid;
   return ray;
 }
 
@@ -134,11 +96,11 @@ __device__ __forceinline__ void axis_setup(float ta, float p, float n, int c, in
 // The exact traversal of the cells the ray crosses between ta = max(r - tr, 0) and tb = r + tr: visit(cx, cy, cz) per cell,
 // at most G of them.
 template <class Visit>
-__device__ __forceinline__ void walk(const Ray& ray, float tr, Visit&& visit)
+__device__ __forceinline__ void walk(const RangeRay& ray, float tr, Visit&& visit)
 {
   const float ta = fmaxf(ray.r - tr, 0.0f), tb = ray.r + tr;
   const float px = ray.o.x + ta * ray.n.x, py = ray.o.y + ta * ray.n.y, pz = ray.o.z + ta * ray.n.z;
-  int cx = vclampi(f2i(floorf(px)), -kFar, kFar), cy = vclampi(f2i(floorf(py)), -kFar, kFar), cz = vclampi(f2i(floorf(pz)), -kFar, kFar);
+  int cx = cell_of(px), cy = cell_of(py), cz = cell_of(pz);
   int sx, sy, sz;
   float mx, my, mz, dx, dy, dz;
   axis_setup(ta, px, ray.n.x, cx, sx, mx, dx);
@@ -188,16 +150,10 @@ __global__ __launch_bounds__(kThreads) void rays_snapshot_kernel(RaysParams P)
     const int data = P.v.hash_entries[index].data;
     if (data >= 0 && data < P.total) P.marks[data] = kHeldBefore;
   }
-  if (index == 0)
-  {
-    P.ctl[cSavedRequests] = P.v.counters[VK_CTR_REQUESTS];
-    P.ctl[cDroppedBefore] = P.v.counters[VK_CTR_DROPPED];
-  }
+  if (index == 0) rounds_begin(P.ctl, P.v.counters);
 }
 
-// One lane per ray. An absent block of a visited cell asks for a slot the way SetView's request pass does (post_request,
-// the largest 64-bit key wins the bucket; a MAIN request marks the bucket visible, volume.cu:193-200), as vk_merge.hip's
-// request pass does for a source block.
+// One lane per ray. An absent block of a visited cell asks for a slot (request_block).
 __global__ __launch_bounds__(kThreads) void rays_request_kernel(RaysParams P)
 {
   if (P.ctl[cStop]) return;                           // the rounds are over: this one changes nothing
@@ -205,42 +161,19 @@ __global__ __launch_bounds__(kThreads) void rays_request_kernel(RaysParams P)
   int posted = 0;
   if (i < (size_t)P.count)
   {
-    const Ray ray = load_ray(P, i);
+    const RangeRay ray = load_range_ray(P, i);
     if (ray.kind == kIntegrated)
     {
       const float tr = P.v.truncation_length / P.v.voxel_length;
       Held held;
       walk(ray, tr, [&](int cx, int cy, int cz) {
         if (!held.move_to(P, cx >> 3, cy >> 3, cz >> 3) || !held.inside || held.slot >= 0) return;
-        const Retry none = {};                        // nothing is recorded for later rounds: every round looks again
-        const uint32_t bucket = block_hash(held.x, held.y, held.z, (uint32_t)P.v.main_block_count);
-        const int type = held.main_entry.data == -1 ? VK_ALLOC_MAIN : VK_ALLOC_EXCESS;
-        if (type == VK_ALLOC_MAIN && P.v.block_visibility[bucket] != VK_VISIBILITY_TRUE)
-          P.v.block_visibility[bucket] = VK_VISIBILITY_TRUE;
-        post_request(P.v, bucket, type, held.x, held.y, held.z, none, bucket);
+        request_block(P.v, held.x, held.y, held.z, held.main_entry);
         posted = 1;
       });
     }
   }
   wave_add(&P.ctl[cPosted], posted);
-}
-
-// One thread, behind a round's handle pass (vk_merge.hip's round end). A handle pass that found no request has only
-// written VK_CTR_REQUESTS = 0: put back what the last round that did something left there.
-__global__ void rays_round_end_kernel(RaysParams P)
-{
-  int32_t* ctl = P.ctl;
-  int32_t* counters = P.v.counters;
-  if (ctl[cStop] || ctl[cPosted] == 0)
-  {
-    ctl[cStop] = 1;
-    counters[VK_CTR_REQUESTS] = ctl[cSavedRequests];
-    return;
-  }
-  ctl[cRounds] += 1;
-  ctl[cPosted] = 0;
-  ctl[cSavedRequests] = counters[VK_CTR_REQUESTS];
-  if (counters[VK_CTR_DROPPED] != ctl[cDroppedBefore]) ctl[cStop] = 1;      // a round that drops ends the rounds
 }
 
 // One lane per ray: the slots of the blocks it visits. Every writer of a byte writes the same value (kHeldBefore does not
@@ -249,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void rays_mark_kernel(RaysParams P)
 {
   const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= (size_t)P.count) return;
-  const Ray ray = load_ray(P, i);
+  const RangeRay ray = load_range_ray(P, i);
   if (ray.kind != kIntegrated) return;
   const float tr = P.v.truncation_length / P.v.voxel_length;
   Held held;
@@ -287,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void rays_add_kernel(RaysParams P)
   int kind = -1, lost = 0;
   if (i < (size_t)P.count)
   {
-    const Ray ray = load_ray(P, i);
+    const RangeRay ray = load_range_ray(P, i);
     kind = ray.kind;
     if (kind == kIntegrated)
     {
@@ -383,8 +316,7 @@ __global__ void rays_finish_kernel(RaysParams P)
   P.counts[5] = ctl[cBlocks];
   P.counts[6] = ctl[cVoxels];
   P.counts[7] = ctl[cLost];
-  P.v.counters[VK_CTR_VISIBLE] = 0;
-  P.v.counters[VK_CTR_BANDED] = -1;             // the banded lists list nothing any more
+  lists_stale(P.v.counters);
 }
 
 // vk_volume_integrate_rays_time_next: the events the next call of this host thread records between its passes
@@ -463,15 +395,9 @@ int vk_volume_integrate_rays(const vk_volume* v, const float* rays, const float*
   VK_CHECK(hipMemsetAsync(P.marks, 0, align_up(total) + cWords * sizeof(int32_t), s));   // the marks, and the control words behind them
   hipLaunchKernelGGL(rays_snapshot_kernel, dim3(entry_groups), dim3(kThreads), 0, s, P);
   VK_LAUNCH_CHECK();
-  for (int round = 0; round < p->max_rounds; ++round)
-  {
-    hipLaunchKernelGGL(rays_request_kernel, dim3(ray_groups), dim3(kThreads), 0, s, P);
-    VK_LAUNCH_CHECK();
-    const int code = vk_volume_handle_allocation_requests(v, stream);
-    if (code != VK_OK) return code;
-    hipLaunchKernelGGL(rays_round_end_kernel, dim3(1), dim3(1), 0, s, P);
-    VK_LAUNCH_CHECK();
-  }
+  const int code = run_rounds(v, p->max_rounds, P.ctl, stream,
+      [&] { hipLaunchKernelGGL(rays_request_kernel, dim3(ray_groups), dim3(kThreads), 0, s, P); });
+  if (code != VK_OK) return code;
   VK_CHECK(pass_done());
   hipLaunchKernelGGL(rays_mark_kernel, dim3(ray_groups), dim3(kThreads), 0, s, P);
   VK_LAUNCH_CHECK();

@@ -17,7 +17,7 @@
 //   resolve   the request pass once more, without posting: the slots of the blocks the last round allocated
 //   finish    the six counts, VK_CTR_VISIBLE and VK_CTR_BANDED
 //   fuse      one wave per source block with a destination slot: the only pass over the two voxel pools
-#include "vk_requests.hpp"
+#include "vk_alloc_rounds.hpp"
 
 using namespace vk;
 
@@ -31,8 +31,8 @@ constexpr int kWaveThreads = 256;                                      // four w
 static_assert(sizeof(vk_voxel) == 20 && kBlockVectors % kWave == 0, "Voxel layout");
 
 enum : uint8_t { kNone = 0, kConsidered = 1, kSkipped = 2, kFusedEarlier = 3 };
-// the words that steer the rounds and carry the sums
-enum { cStop = 0, cPosted, cRounds, cSavedRequests, cDroppedBefore, cConsidered, cSkipped, cPresentBefore, cPresent, cWords = 16 };
+// the words that carry the sums, behind the ones that steer the rounds
+enum { cConsidered = cRoundWords, cSkipped, cPresentBefore, cPresent, cWords = 16 };
 
 struct MergeParams
 {
@@ -46,13 +46,6 @@ struct MergeParams
   int32_t* ctl;                 // [cWords]
   int32_t* counts;              // [6] output
 };
-
-// sum over the wave, then one atomic: integer sums commute
-__device__ __forceinline__ void wave_add(int32_t* word, int value)
-{
-  for (int d = 32; d > 0; d >>= 1) value += __shfl_down(value, d);
-  if (lane_id() == 0 && value) atomicAdd(word, value);
-}
 
 // (the control words are zero: a memset in front of this launch)
 __global__ __launch_bounds__(256) void merge_init_kernel(MergeParams P)
@@ -75,33 +68,14 @@ __global__ __launch_bounds__(256) void merge_init_kernel(MergeParams P)
     }
   }
   if (P.flags & VK_MERGE_CONTINUE) wave_add(&P.ctl[cConsidered], still);
-  if (index == 0)
-  {
-    P.ctl[cSavedRequests] = P.dst.counters[VK_CTR_REQUESTS];
-    P.ctl[cDroppedBefore] = P.dst.counters[VK_CTR_DROPPED];
-  }
+  if (index == 0) rounds_begin(P.ctl, P.dst.counters);
 }
 
-// a source block: an entry with data >= 0 that is reachable from a main bucket along `next` (a link that leaves the
-// table ends the chain and no chain is longer than the table, as in vk_release.hip)
+// one thread per source bucket: its source blocks (mark_chain)
 __global__ __launch_bounds__(256) void merge_mark_kernel(MergeParams P)
 {
   const int bucket = blockIdx.x * blockDim.x + threadIdx.x;
-  int blocks = 0;
-  if (bucket < P.src.main_block_count)
-  {
-    int index = bucket;
-    for (int guard = 0; index >= 0 && index < P.src_total && guard < P.src_total; ++guard)
-    {
-      const Entry entry = load_entry(P.src.hash_entries, (uint32_t)index);
-      if (entry.data >= 0 && entry.data < P.src_total)
-      {
-        P.state[index] = kConsidered;
-        ++blocks;
-      }
-      index = entry.next;
-    }
-  }
+  const int blocks = mark_chain(P.src, P.src_total, bucket, [&](int index) { P.state[index] = kConsidered; });
   if (!(P.flags & VK_MERGE_SKIP_UNOBSERVED)) wave_add(&P.ctl[cConsidered], blocks);   // (classify counts otherwise)
 }
 
@@ -136,10 +110,8 @@ __global__ __launch_bounds__(kWaveThreads) void merge_classify_kernel(MergeParam
   }
 }
 
-// One lane per source entry. The lane walks the chain of the block's bucket in dst: an entry with data >= 0 and the
-// block's origin is the block (the empty main entry does not stand in for block (0,0,0)); its slot is kept for the fuse
-// pass. POST: a block that is absent asks for a slot the way SetView's request pass does (post_request, the largest
-// 64-bit key wins the bucket; a MAIN request marks the bucket visible, volume.cu:193-200).
+// One lane per source entry. The lane looks for the block in dst (find_block); its slot is kept for the fuse pass. POST: a
+// block that is absent asks for a slot (request_block).
 template <bool POST>
 __global__ __launch_bounds__(256) void merge_request_kernel(MergeParams P)
 {
@@ -152,29 +124,12 @@ __global__ __launch_bounds__(256) void merge_request_kernel(MergeParams P)
     if (slot < 0)
     {
       const Entry mine = load_entry(P.src.hash_entries, (uint32_t)index);
-      const uint32_t bucket = block_hash(mine.ox, mine.oy, mine.oz, (uint32_t)P.dst.main_block_count);
-      const Entry main_entry = load_entry(P.dst.hash_entries, bucket);
-      Entry entry = main_entry;
-      int at = (int)bucket;
-      for (int guard = 0; guard < P.dst_total; ++guard)
-      {
-        if (entry.data >= 0 && entry.data < P.dst_total && entry_is(entry, mine.ox, mine.oy, mine.oz))
-        {
-          slot = entry.data;
-          break;
-        }
-        at = entry.next;
-        if (at < 0 || at >= P.dst_total) break;
-        entry = load_entry(P.dst.hash_entries, (uint32_t)at);
-      }
+      Entry main_entry;
+      find_block(P.dst, P.dst_total, mine.ox, mine.oy, mine.oz, slot, main_entry);
       if (slot >= 0) P.found[index] = slot;
       else if (POST)
       {
-        const Retry none = {};                      // nothing is recorded for later rounds: every round looks again
-        const int type = main_entry.data == -1 ? VK_ALLOC_MAIN : VK_ALLOC_EXCESS;
-        if (type == VK_ALLOC_MAIN && P.dst.block_visibility[bucket] != VK_VISIBILITY_TRUE)
-          P.dst.block_visibility[bucket] = VK_VISIBILITY_TRUE;
-        post_request(P.dst, bucket, type, mine.ox, mine.oy, mine.oz, none, bucket);
+        request_block(P.dst, mine.ox, mine.oy, mine.oz, main_entry);
         posted = 1;
       }
     }
@@ -189,24 +144,6 @@ __global__ __launch_bounds__(256) void merge_request_kernel(MergeParams P)
   else wave_add(&P.ctl[cPresent], present);
 }
 
-// One thread, behind a round's handle pass. A handle pass that found no request has only written VK_CTR_REQUESTS = 0:
-// put back what the last round that did something left there.
-__global__ void merge_round_end_kernel(MergeParams P)
-{
-  int32_t* ctl = P.ctl;
-  int32_t* counters = P.dst.counters;
-  if (ctl[cStop] || ctl[cPosted] == 0)
-  {
-    ctl[cStop] = 1;
-    counters[VK_CTR_REQUESTS] = ctl[cSavedRequests];
-    return;
-  }
-  ctl[cRounds] += 1;
-  ctl[cPosted] = 0;
-  ctl[cSavedRequests] = counters[VK_CTR_REQUESTS];
-  if (counters[VK_CTR_DROPPED] != ctl[cDroppedBefore]) ctl[cStop] = 1;      // divergence 14: a round that drops ends the rounds
-}
-
 __global__ void merge_finish_kernel(MergeParams P)
 {
   const int32_t* ctl = P.ctl;
@@ -216,8 +153,7 @@ __global__ void merge_finish_kernel(MergeParams P)
   P.counts[3] = ctl[cConsidered] - ctl[cPresent];
   P.counts[4] = ctl[cRounds];
   P.counts[5] = ctl[cSkipped];
-  P.dst.counters[VK_CTR_VISIBLE] = 0;
-  P.dst.counters[VK_CTR_BANDED] = -1;           // the banded lists list nothing any more
+  lists_stale(P.dst.counters);
 }
 
 // a[i] of eight values for a lane-dependent i, as selects: an array indexed at run time would leave the registers
@@ -310,19 +246,6 @@ __global__ __launch_bounds__(kWaveThreads) void merge_fuse_kernel(MergeParams P)
   }
 }
 
-inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
-bool volume_ok(const vk_volume* v)
-{
-  return v && v->voxels && v->hash_entries && v->free_voxel_blocks && v->allocation_types && v->allocation_blocks &&
-         v->block_visibility && v->visible_blocks && v->counters && v->main_block_count > 0 && v->excess_block_count >= 0 &&
-         v->excess_block_count <= INT32_MAX - v->main_block_count && v->voxel_length > 0 && v->truncation_length > 0 &&
-         // what the handle pass asks of a volume (check_volume, vk_volume.hip): refused here, before anything is enqueued
-         (reinterpret_cast<uintptr_t>(v->counters) & 7) == 0 && (reinterpret_cast<uintptr_t>(v->allocation_blocks) & 7) == 0 &&
-         (reinterpret_cast<uintptr_t>(v->hash_entries) & 15) == 0 && (reinterpret_cast<uintptr_t>(v->voxels) & 15) == 0 &&
-         (reinterpret_cast<uintptr_t>(v->block_visibility) & 3) == 0 && (reinterpret_cast<uintptr_t>(v->allocation_types) & 15) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -339,14 +262,7 @@ int vk_volume_merge(const vk_volume* dst, const vk_volume* src, const vk_merge_p
     void* stream)
 {
   VK_REQUIRE(dst && src && p && counts_dev && workspace);
-  VK_REQUIRE(volume_ok(dst) && volume_ok(src));
-  VK_REQUIRE(dst->voxels != src->voxels);
-  VK_REQUIRE(memcmp(&dst->voxel_length, &src->voxel_length, sizeof(float)) == 0);
-  VK_REQUIRE(memcmp(&dst->truncation_length, &src->truncation_length, sizeof(float)) == 0);
-  VK_REQUIRE((p->flags & ~(VK_MERGE_SKIP_UNOBSERVED | VK_MERGE_CONTINUE)) == 0);
-  VK_REQUIRE(p->max_rounds >= 1);
-  VK_REQUIRE(p->max_distance_weight >= 1.0f && p->max_distance_weight <= 32767.0f);      // (false for a NaN)
-  VK_REQUIRE(p->max_color_weight >= 1.0f && p->max_color_weight <= 32767.0f);
+  VK_REQUIRE(merge_ok(dst, src, *p));
   hipStream_t s = vk_s(stream);
   MergeParams P;
   P.dst = *dst;
@@ -378,15 +294,9 @@ int vk_volume_merge(const vk_volume* dst, const vk_volume* src, const vk_merge_p
       VK_LAUNCH_CHECK();
     }
   }
-  for (int round = 0; round < p->max_rounds; ++round)
-  {
-    hipLaunchKernelGGL(merge_request_kernel<true>, dim3(entry_groups), dim3(256), 0, s, P);
-    VK_LAUNCH_CHECK();
-    const int code = vk_volume_handle_allocation_requests(dst, stream);
-    if (code != VK_OK) return code;
-    hipLaunchKernelGGL(merge_round_end_kernel, dim3(1), dim3(1), 0, s, P);
-    VK_LAUNCH_CHECK();
-  }
+  const int code = run_rounds(dst, p->max_rounds, P.ctl, stream,
+      [&] { hipLaunchKernelGGL(merge_request_kernel<true>, dim3(entry_groups), dim3(256), 0, s, P); });
+  if (code != VK_OK) return code;
   hipLaunchKernelGGL(merge_request_kernel<false>, dim3(entry_groups), dim3(256), 0, s, P);
   VK_LAUNCH_CHECK();
   hipLaunchKernelGGL(merge_finish_kernel, dim3(1), dim3(1), 0, s, P);

@@ -19,7 +19,7 @@
 //   finish    the eight counts, VK_CTR_VISIBLE and VK_CTR_BANDED
 //   fuse      one wave per marked destination entry: the source footprint's slots once into an LDS directory, then the
 //             eight-point gather per voxel through it: the only pass over the two voxel pools
-#include "vk_block_walk.hpp"
+#include "vk_alloc_rounds.hpp"
 
 using namespace vk;
 
@@ -30,14 +30,12 @@ constexpr int kWaveThreads = 256;                                      // four w
 constexpr int kWavesPerGroup = kWaveThreads / kWave;
 constexpr int kBoxBlocks = 27;                                         // a rigid pose spans at most 3 blocks per axis
 constexpr int kLanesPerEntry = 32;                                     // request pass: one lane per box block, 27 of 32
-constexpr int kFootprint = 4;                                          // source blocks per axis under one dst block
 constexpr int kCoordinateClamp = 40000;                                // beyond the int16 range: see block_box
-static_assert(kFootprint * kFootprint * kFootprint == kWave, "one lane per directory cell");
 
 enum : uint8_t { kNone = 0, kConsidered = 1, kSkipped = 2 };            // a source entry
 enum : int32_t { kNoCandidate = 0, kCandidate = 1, kFused = 2 };        // a destination entry
-// the words that steer the rounds and carry the sums
-enum { cStop = 0, cPosted, cRounds, cSavedRequests, cDroppedBefore, cConsidered, cSkipped, cPresentBefore, cMarked, cAbsent, cWords = 16 };
+// the words that carry the sums, behind the ones that steer the rounds
+enum { cConsidered = cRoundWords, cSkipped, cPresentBefore, cMarked, cAbsent, cWords = 16 };
 
 struct PoseParams
 {
@@ -93,32 +91,14 @@ __global__ __launch_bounds__(256) void pose_init_kernel(PoseParams P)
     if (index < P.src_total) P.state[index] = kNone;
     if (index < P.dst_total) P.mark[index] = kNoCandidate;
   }
-  if (index == 0)
-  {
-    P.ctl[cSavedRequests] = P.dst.counters[VK_CTR_REQUESTS];
-    P.ctl[cDroppedBefore] = P.dst.counters[VK_CTR_DROPPED];
-  }
+  if (index == 0) rounds_begin(P.ctl, P.dst.counters);
 }
 
-// a source block: as in vk_merge.hip
+// one thread per source bucket: its source blocks (mark_chain)
 __global__ __launch_bounds__(256) void pose_mark_kernel(PoseParams P)
 {
   const int bucket = blockIdx.x * blockDim.x + threadIdx.x;
-  int blocks = 0;
-  if (bucket < P.src.main_block_count)
-  {
-    int index = bucket;
-    for (int guard = 0; index >= 0 && index < P.src_total && guard < P.src_total; ++guard)
-    {
-      const Entry entry = load_entry(P.src.hash_entries, (uint32_t)index);
-      if (entry.data >= 0 && entry.data < P.src_total)
-      {
-        P.state[index] = kConsidered;
-        ++blocks;
-      }
-      index = entry.next;
-    }
-  }
+  const int blocks = mark_chain(P.src, P.src_total, bucket, [&](int index) { P.state[index] = kConsidered; });
   if (!(P.flags & VK_MERGE_SKIP_UNOBSERVED)) wave_add(&P.ctl[cConsidered], blocks);   // (classify counts otherwise)
 }
 
@@ -199,8 +179,7 @@ __device__ __forceinline__ bool first_owner(const PoseParams& P, int index, int 
 
 // One lane per source entry and block of its box. The lane walks the chain of the candidate's bucket in dst. A candidate
 // that is there is marked at its entry, once (the compare-and-swap decides who counts it; a mark of an earlier call
-// stays). POST: one that is absent asks for a slot the way SetView's request pass does (post_request, the largest 64-bit
-// key wins the bucket; a MAIN request marks the bucket visible, volume.cu:193-200).
+// stays). POST: one that is absent asks for a slot (request_block).
 template <bool POST>
 __global__ __launch_bounds__(256) void pose_request_kernel(PoseParams P)
 {
@@ -223,12 +202,7 @@ __global__ __launch_bounds__(256) void pose_request_kernel(PoseParams P)
       }
       else if (POST)
       {
-        const Retry none = {};                      // nothing is recorded for later rounds: every round looks again
-        const uint32_t bucket = block_hash(bx, by, bz, (uint32_t)P.dst.main_block_count);
-        const int type = main_entry.data == -1 ? VK_ALLOC_MAIN : VK_ALLOC_EXCESS;
-        if (type == VK_ALLOC_MAIN && P.dst.block_visibility[bucket] != VK_VISIBILITY_TRUE)
-          P.dst.block_visibility[bucket] = VK_VISIBILITY_TRUE;
-        post_request(P.dst, bucket, type, bx, by, bz, none, bucket);
+        request_block(P.dst, bx, by, bz, main_entry);
         posted = 1;
       }
       else absent = first_owner(P, index, bx, by, bz) ? 1 : 0;
@@ -244,23 +218,6 @@ __global__ __launch_bounds__(256) void pose_request_kernel(PoseParams P)
   else wave_add(&P.ctl[cAbsent], absent);
 }
 
-// One thread, behind a round's handle pass: as in vk_merge.hip
-__global__ void pose_round_end_kernel(PoseParams P)
-{
-  int32_t* ctl = P.ctl;
-  int32_t* counters = P.dst.counters;
-  if (ctl[cStop] || ctl[cPosted] == 0)
-  {
-    ctl[cStop] = 1;
-    counters[VK_CTR_REQUESTS] = ctl[cSavedRequests];
-    return;
-  }
-  ctl[cRounds] += 1;
-  ctl[cPosted] = 0;
-  ctl[cSavedRequests] = counters[VK_CTR_REQUESTS];
-  if (counters[VK_CTR_DROPPED] != ctl[cDroppedBefore]) ctl[cStop] = 1;      // divergence 14: a round that drops ends the rounds
-}
-
 __global__ void pose_finish_kernel(PoseParams P)
 {
   const int32_t* ctl = P.ctl;
@@ -272,14 +229,12 @@ __global__ void pose_finish_kernel(PoseParams P)
   P.counts[5] = ctl[cRounds];
   P.counts[6] = ctl[cSkipped];
   P.counts[7] = 0;                              // the fuse pass adds to it
-  P.dst.counters[VK_CTR_VISIBLE] = 0;
-  P.dst.counters[VK_CTR_BANDED] = -1;           // the banded lists list nothing any more
+  lists_stale(P.dst.counters);
 }
 
-// One wave per marked dst entry, eight voxels per lane (lane = 8 y + x, one z per trip). Under a rigid pose the lattice
-// points of a block's 512 samples lie in at most 4^3 source blocks from the least one: lane k walks the chain of cell k
-// once and leaves the slot in the wave's 64-word LDS directory, so a voxel's eight neighbours cost eight pool reads and
-// no table read. A lattice point outside the directory (no rigid pose gets there) counts as absent.
+// One wave per marked dst entry, eight voxels per lane (lane = 8 y + x, one z per trip). The source footprint's slots go
+// into the wave's LDS directory once (fill_directory), so a voxel's eight neighbours cost eight pool reads and no table
+// read. A lattice point outside the directory (no rigid pose gets there) counts as absent.
 __global__ __launch_bounds__(kWaveThreads) void pose_fuse_kernel(PoseParams P)
 {
   __shared__ int directory[kWavesPerGroup][kWave];
@@ -292,26 +247,8 @@ __global__ __launch_bounds__(kWaveThreads) void pose_fuse_kernel(PoseParams P)
   const int lane = lane_id();
   const int x = lane & 7, y = lane >> 3;
 
-  int least_x = INT32_MAX, least_y = INT32_MAX, least_z = INT32_MAX;
-#pragma unroll
-  for (int z = 0; z < 8; ++z)
-  {
-    const Lattice l = lattice_of(P.back, mine.ox, mine.oy, mine.oz, x, y, z);
-    least_x = vmini(least_x, l.bx >> 3);
-    least_y = vmini(least_y, l.by >> 3);
-    least_z = vmini(least_z, l.bz >> 3);
-  }
-  least_x = wave_min(least_x);
-  least_y = wave_min(least_y);
-  least_z = wave_min(least_z);
-  {
-    const int sx = least_x + (lane & 3), sy = least_y + ((lane >> 2) & 3), sz = least_z + (lane >> 4);
-    int slot = -1;
-    Entry main_entry;
-    if (in_int16(sx, sy, sz)) find_block(P.src, P.src_total, sx, sy, sz, slot, main_entry);
-    directory[wave][lane] = slot;
-  }
-  wave_lds_fence();
+  int least_x, least_y, least_z;
+  fill_directory(P.src, P.src_total, P.back, mine, directory[wave], least_x, least_y, least_z);
 
   const uint32_t* src_pool = reinterpret_cast<const uint32_t*>(P.src.voxels);
   uint32_t* mine_voxels = reinterpret_cast<uint32_t*>(P.dst.voxels) + (size_t)mine.data * VK_BLOCK_VOXELS * kVoxelWords;
@@ -394,21 +331,6 @@ __global__ __launch_bounds__(kWaveThreads) void pose_fuse_kernel(PoseParams P)
   if (lane == 0) P.mark[at] = kFused;            // a call that continues passes over it
 }
 
-// rows 0-2 of a column-major 4x4, the translation in voxels; false when one of the twelve is not finite
-bool voxel_rows(const float* m, float voxel_length, float* rows)
-{
-  for (int a = 0; a < 3; ++a)
-  {
-    for (int c = 0; c < 4; ++c)
-      if (!isfinite(m[4 * c + a])) return false;
-    rows[4 * a + 0] = m[a];
-    rows[4 * a + 1] = m[4 + a];
-    rows[4 * a + 2] = m[8 + a];
-    rows[4 * a + 3] = m[12 + a] / voxel_length;
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -425,15 +347,8 @@ int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_m
     void* workspace, void* stream)
 {
   VK_REQUIRE(dst && src && p && counts_dev && workspace);
-  VK_REQUIRE(volume_ok(dst) && volume_ok(src));
-  VK_REQUIRE(dst->voxels != src->voxels);
-  VK_REQUIRE(memcmp(&dst->voxel_length, &src->voxel_length, sizeof(float)) == 0);
-  VK_REQUIRE(memcmp(&dst->truncation_length, &src->truncation_length, sizeof(float)) == 0);
   const vk_merge_params& m = p->merge;
-  VK_REQUIRE((m.flags & ~(VK_MERGE_SKIP_UNOBSERVED | VK_MERGE_CONTINUE)) == 0);
-  VK_REQUIRE(m.max_rounds >= 1);
-  VK_REQUIRE(m.max_distance_weight >= 1.0f && m.max_distance_weight <= 32767.0f);      // (false for a NaN)
-  VK_REQUIRE(m.max_color_weight >= 1.0f && m.max_color_weight <= 32767.0f);
+  VK_REQUIRE(merge_ok(dst, src, m));
   PoseParams P;
   VK_REQUIRE(voxel_rows(p->pose.m, dst->voxel_length, P.fwd) && voxel_rows(p->pose.inv, dst->voxel_length, P.back));
   hipStream_t s = vk_s(stream);
@@ -473,15 +388,9 @@ int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_m
     hipLaunchKernelGGL(pose_geometry_kernel, dim3(src_wave_groups), dim3(kWaveThreads), 0, s, P);
     VK_LAUNCH_CHECK();
   }
-  for (int round = 0; round < m.max_rounds; ++round)
-  {
-    hipLaunchKernelGGL(pose_request_kernel<true>, dim3((unsigned)request_groups), dim3(256), 0, s, P);
-    VK_LAUNCH_CHECK();
-    const int code = vk_volume_handle_allocation_requests(dst, stream);
-    if (code != VK_OK) return code;
-    hipLaunchKernelGGL(pose_round_end_kernel, dim3(1), dim3(1), 0, s, P);
-    VK_LAUNCH_CHECK();
-  }
+  const int code = run_rounds(dst, m.max_rounds, P.ctl, stream,
+      [&] { hipLaunchKernelGGL(pose_request_kernel<true>, dim3((unsigned)request_groups), dim3(256), 0, s, P); });
+  if (code != VK_OK) return code;
   hipLaunchKernelGGL(pose_request_kernel<false>, dim3((unsigned)request_groups), dim3(256), 0, s, P);
   VK_LAUNCH_CHECK();
   hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(1), 0, s, P);

@@ -24,8 +24,6 @@ namespace
 
 constexpr int kWaveThreads = 256;                                      // four waves = four source entries per workgroup
 constexpr int kWavesPerGroup = kWaveThreads / kWave;
-constexpr int kFootprint = 4;                                          // dst blocks per axis under one source block
-static_assert(kFootprint * kFootprint * kFootprint == kWave, "one lane per directory cell");
 
 enum { cConsidered = 0, cWords = 16 };                                 // the control words
 enum { kSumSquares = 27, kBanded = 28, kResiduals = 29 };              // a partial row behind the 27 sums (two are ints)
@@ -48,26 +46,11 @@ struct RegisterParams
   uint8_t* valid;
 };
 
-// a source block: as in vk_merge.hip
+// one thread per source bucket: its source blocks (mark_chain)
 __global__ __launch_bounds__(256) void register_mark_kernel(RegisterParams P)
 {
   const int bucket = blockIdx.x * blockDim.x + threadIdx.x;
-  int blocks = 0;
-  if (bucket < P.src.main_block_count)
-  {
-    int index = bucket;
-    for (int guard = 0; index >= 0 && index < P.src_total && guard < P.src_total; ++guard)
-    {
-      const Entry entry = load_entry(P.src.hash_entries, (uint32_t)index);
-      if (entry.data >= 0 && entry.data < P.src_total)
-      {
-        P.considered[index] = 1;
-        ++blocks;
-      }
-      index = entry.next;
-    }
-  }
-  wave_add(&P.ctl[cConsidered], blocks);
+  wave_add(&P.ctl[cConsidered], mark_chain(P.src, P.src_total, bucket, [&](int index) { P.considered[index] = 1; }));
 }
 
 // the terms of the source block at entry `index`, summed over the lane's eight voxels
@@ -93,38 +76,9 @@ __device__ __forceinline__ void block_terms(const RegisterParams& P, int index, 
   if (banded == 0) return;                        // (the same for the whole wave) dst is not touched
 
   float fwd[12];
-  {
-    const float* m = P.pose->m;
-    const float voxel_length = P.dst.voxel_length;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-    {
-      fwd[4 * a + 0] = m[a];
-      fwd[4 * a + 1] = m[4 + a];
-      fwd[4 * a + 2] = m[8 + a];
-      fwd[4 * a + 3] = m[12 + a] / voxel_length;
-    }
-  }
-  int least_x = INT32_MAX, least_y = INT32_MAX, least_z = INT32_MAX;
-#pragma unroll
-  for (int z = 0; z < 8; ++z)
-  {
-    const Lattice l = lattice_of(fwd, mine.ox, mine.oy, mine.oz, x, y, z);
-    least_x = vmini(least_x, l.bx >> 3);
-    least_y = vmini(least_y, l.by >> 3);
-    least_z = vmini(least_z, l.bz >> 3);
-  }
-  least_x = wave_min(least_x);
-  least_y = wave_min(least_y);
-  least_z = wave_min(least_z);
-  {
-    const int sx = least_x + (lane & 3), sy = least_y + ((lane >> 2) & 3), sz = least_z + (lane >> 4);
-    int slot = -1;
-    Entry main_entry;
-    if (in_int16(sx, sy, sz)) find_block(P.dst, P.dst_total, sx, sy, sz, slot, main_entry);
-    directory[lane] = slot;
-  }
-  wave_lds_fence();
+  carry_rows(P.pose, P.dst.voxel_length, fwd);
+  int least_x, least_y, least_z;
+  fill_directory(P.dst, P.dst_total, fwd, mine, directory, least_x, least_y, least_z);
 
   const uint32_t* dst_pool = reinterpret_cast<const uint32_t*>(P.dst.voxels);
 #pragma unroll 1
@@ -290,9 +244,7 @@ int prepare(const vk_volume* dst, const vk_volume* src, const vk_transform* pose
     RegisterParams& P)
 {
   VK_REQUIRE(dst && src && pose_dev && p && workspace);
-  VK_REQUIRE(volume_ok(dst) && volume_ok(src));
-  VK_REQUIRE(memcmp(&dst->voxel_length, &src->voxel_length, sizeof(float)) == 0);
-  VK_REQUIRE(memcmp(&dst->truncation_length, &src->truncation_length, sizeof(float)) == 0);
+  VK_REQUIRE(volumes_match(dst, src));
   VK_REQUIRE(p->flags == 0);
   VK_REQUIRE(p->iterations >= 1 && p->iterations <= 64);
   VK_REQUIRE(p->max_abs_distance > 0.0f && p->max_abs_distance <= 1.0f);        // (false for a NaN)

@@ -247,8 +247,6 @@ __global__ __launch_bounds__(256) void free_list_kernel(ReleaseParams P)
   }
 }
 
-inline size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {

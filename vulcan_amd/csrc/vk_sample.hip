@@ -46,20 +46,11 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(SampleParams P)
   f3 p = f3{q0, q1, q2};
   if (P.pose)
   {
-    const float* m = P.pose->m;
     float fwd[12];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-    {
-      fwd[4 * a + 0] = m[a];
-      fwd[4 * a + 1] = m[4 + a];
-      fwd[4 * a + 2] = m[8 + a];
-      fwd[4 * a + 3] = m[12 + a] / voxel_length;
-    }
+    carry_rows(P.pose, voxel_length, fwd);
     p = apply(fwd, q0, q1, q2);
   }
-  const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-  const Cell cell = read_cell<COLOR, GRADIENT>(P.v, P.total, p, finite);
+  const Cell cell = read_cell<COLOR, GRADIENT>(P.v, P.total, p, finite3(p));
   if (P.samples) store_sample<COLOR>(cell, reinterpret_cast<uint32_t*>(P.samples) + i * kVoxelWords);
   if (GRADIENT) store_gradient(cell, P.gradients + i * 4);
 }

@@ -2,98 +2,16 @@
 // kernel (no upstream case: the reference casts only the pixel rays of one pinhole camera). The call is held against the CPU
 // statement bit for bit by tests/test_gpu_cast.py; these cases are what a user of the class sees: rays built from the Tracer's
 // camera hit where the raycast depth says, a ray from behind a surface reports no back face, and after Merge(other, pose) the
-// rays see both sessions' surfaces. Harness as in sample_tests.cpp.
+// rays see both sessions' surfaces. Harness: volume_test_support.h.
 //
 //   ./cast_tests            run everything (needs a GPU)
 //   ./cast_tests <filter>   run the cases whose name contains <filter>
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <functional>
-#include <memory>
-#include <string>
-#include <vector>
+#include "volume_test_support.h"
 
-#include <vulcan/vulcan.h>
-
-using namespace vulcan;
-
-struct Failure { std::string text; };
-
-#define STR2(x) #x
-#define STR(x) STR2(x)
-#define FAIL_HERE(msg) throw Failure{std::string(__FILE__ ":" STR(__LINE__) ": ") + (msg)}
-#define ASSERT_TRUE(c) do { if (!(c)) FAIL_HERE("expected true: " #c); } while (0)
-#define ASSERT_EQ(a, b) do { if (!((a) == (b))) FAIL_HERE("expected equal: " #a " vs " #b + \
-    (" (" + std::to_string((double)(a)) + " vs " + std::to_string((double)(b)) + ")")); } while (0)
-#define ASSERT_THROW(stmt) do { bool t__ = false; try { stmt; } catch (const Exception&) { t__ = true; } \
-    if (!t__) FAIL_HERE("expected vulcan::Exception: " #stmt); } while (0)
-
-struct TestCase { const char* name; std::function<void()> body; };
-static std::vector<TestCase>& Registry() { static std::vector<TestCase> r; return r; }
-struct Registrar { Registrar(const char* n, std::function<void()> f) { Registry().push_back({n, f}); } };
-#define TEST(suite, name) static void suite##_##name(); \
-    static Registrar reg_##suite##_##name(#suite "." #name, suite##_##name); static void suite##_##name()
-
-static const int kWidth = 160, kHeight = 120;
-static const float kVoxel = 0.008f;
 // |t (n . optical axis) - raycast depth| in metres, tests/test_cast_reference.py: twice what the statement measures against
 // the reference's raycast. The maximum is reached where the observed region ends (the rim of the image, a block the table
 // could not hold): there the reference's trilinear sample blends the unobserved voxels in and the cast's does not
 static const float kDepthBound = 2 * 0.0232f;
-
-static std::shared_ptr<Image> MakeDepth(const std::function<float(int, int)>& f)
-{
-  std::vector<float> host(size_t(kWidth) * kHeight);
-  for (int y = 0; y < kHeight; ++y) for (int x = 0; x < kWidth; ++x) host[size_t(y) * kWidth + x] = f(x, y);
-  auto image = std::make_shared<Image>(kWidth, kHeight);
-  image->CopyFromHost(host.data());
-  return image;
-}
-
-// the scene of tests/register_reference.py: a wall at 1 m with a bump, a dent and a slope
-static float Bumps(int x, int y)
-{
-  const double w = kWidth, h = kHeight;
-  const double bump = std::exp(-((x - 0.375 * w) * (x - 0.375 * w) + (y - 0.42 * h) * (y - 0.42 * h)) / (2 * (0.16 * w) * (0.16 * w)));
-  const double dent = std::exp(-((x - 0.69 * w) * (x - 0.69 * w) + (y - 0.67 * h) * (y - 0.67 * h)) / (2 * (0.11 * w) * (0.11 * w)));
-  return float(1.0 + 0.06 * bump - 0.04 * dent + 0.03 * x / w);
-}
-
-static Frame BumpsFrame(const Transform& pose)
-{
-  Frame frame;
-  frame.depth_projection.SetFocalLength(136, 136);
-  frame.depth_projection.SetCenterPoint(80, 60);
-  frame.depth_image = MakeDepth(Bumps);
-  frame.depth_to_world_transform = pose;
-  return frame;
-}
-
-static std::shared_ptr<Volume> Fused(int main_blocks, int excess_blocks, const Frame& frame, int integrations)
-{
-  auto volume = std::make_shared<Volume>(main_blocks, excess_blocks);
-  volume->SetVoxelLength(kVoxel);
-  for (int i = 0; i < 6; ++i) volume->SetView(frame);
-  DepthIntegrator integrator(volume);
-  for (int i = 0; i < integrations; ++i) integrator.Integrate(frame);
-  return volume;
-}
-
-// the pixel rays of the frame's camera, in the camera's frame: from its centre through every pixel's centre
-static std::vector<Ray> PixelRays(const Frame& frame)
-{
-  std::vector<Ray> rays(size_t(kWidth) * kHeight);
-  for (int y = 0; y < kHeight; ++y)
-    for (int x = 0; x < kWidth; ++x)
-    {
-      Ray& ray = rays[size_t(y) * kWidth + x];
-      ray.origin = Vector3f(0.0f, 0.0f, 0.0f);
-      ray.direction = frame.depth_projection.Unproject(x + 0.5f, y + 0.5f);
-    }
-  return rays;
-}
 
 struct Hits
 {
@@ -125,8 +43,6 @@ static Hits Cast(const Volume& volume, const std::vector<Ray>& rays, const Trans
   gradients_dev.CopyToHost(hits.gradients.data());
   return hits;
 }
-
-static float Length(const Vector3f& v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
 // the raycast of the fusing view and the same pixels as rays: where both hit, t along the optical axis is the raycast's depth
 TEST(Cast, CameraRaysHitWhereTheRaycastSays)
@@ -251,22 +167,4 @@ TEST(Cast, AfterAMergeBothSessionsSurfacesAreSeen)
   ASSERT_TRUE(moved / found < 0.004);
 }
 
-int main(int argc, char** argv)
-{
-  int count = 0;
-  VK_ASSERT(vk_device_count(&count));
-  if (count == 0) { std::printf("cast_tests: no HIP device\n"); return 2; }
-  const std::string filter = argc > 1 ? argv[1] : "";
-  int failed = 0, ran = 0;
-  for (const TestCase& t : Registry())
-  {
-    if (!filter.empty() && std::string(t.name).find(filter) == std::string::npos) continue;
-    ++ran;
-    try { t.body(); Device::Synchronize(); std::printf("[  OK  ] %s\n", t.name); }
-    catch (const Failure& f) { ++failed; std::printf("[FAILED] %s\n         %s\n", t.name, f.text.c_str()); }
-    catch (const std::exception& e) { ++failed; std::printf("[FAILED] %s\n         exception: %s\n", t.name, e.what()); }
-    std::fflush(stdout);
-  }
-  std::printf("%d test(s), %d failed\n", ran, failed);
-  return failed ? 1 : 0;
-}
+int main(int argc, char** argv) { return RunTests("cast_tests", argc, argv); }

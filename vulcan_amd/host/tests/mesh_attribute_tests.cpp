@@ -2,41 +2,14 @@
 // case: ref include/vulcan/mesh.h holds points and faces only). The values are held against their CPU statement bit for
 // bit by tests/test_gpu_extract_attributes.py; these cases are what a user of the classes sees: Extractor::SetColors /
 // SetNormals fill Mesh::colors / Mesh::normals, Exporter writes them, and with both switches off nothing changes.
-// Harness as in host_tests.cpp.
+// Harness: volume_test_support.h.
 //
 //   ./mesh_attribute_tests            run everything (needs a GPU)
 //   ./mesh_attribute_tests <filter>   run the cases whose name contains <filter>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <fstream>
 #include <sstream>
-#include <functional>
-#include <string>
-#include <vector>
 
-#include <vulcan/vulcan.h>
-
-using namespace vulcan;
-
-struct Failure { std::string text; };
-
-#define STR2(x) #x
-#define STR(x) STR2(x)
-#define FAIL_HERE(msg) throw Failure{std::string(__FILE__ ":" STR(__LINE__) ": ") + (msg)}
-#define ASSERT_TRUE(c) do { if (!(c)) FAIL_HERE("expected true: " #c); } while (0)
-#define ASSERT_EQ(a, b) do { if (!((a) == (b))) FAIL_HERE("expected equal: " #a " vs " #b + \
-    (" (" + std::to_string((double)(a)) + " vs " + std::to_string((double)(b)) + ")")); } while (0)
-#define ASSERT_THROW(stmt) do { bool t__ = false; try { stmt; } catch (const Exception&) { t__ = true; } \
-    if (!t__) FAIL_HERE("expected vulcan::Exception: " #stmt); } while (0)
-
-struct TestCase { const char* name; std::function<void()> body; };
-static std::vector<TestCase>& Registry() { static std::vector<TestCase> r; return r; }
-struct Registrar { Registrar(const char* n, std::function<void()> f) { Registry().push_back({n, f}); } };
-#define TEST(suite, name) static void suite##_##name(); \
-    static Registrar reg_##suite##_##name(#suite "." #name, suite##_##name); static void suite##_##name()
-
-static const int kWidth = 160, kHeight = 120;
+#include "volume_test_support.h"
 
 // a plane 1.5 m in front of the camera, facing it, in one constant colour, fused once (so every voxel's stored colour is
 // the frame's, exactly)
@@ -177,22 +150,4 @@ TEST(MeshAttributes, ExtractedMeshExportsWithProperties)
   ASSERT_TRUE(ReadFile(file) == before);
 }
 
-int main(int argc, char** argv)
-{
-  int count = 0;
-  VK_ASSERT(vk_device_count(&count));
-  if (count == 0) { std::printf("mesh_attribute_tests: no HIP device\n"); return 2; }
-  const std::string filter = argc > 1 ? argv[1] : "";
-  int failed = 0, ran = 0;
-  for (const TestCase& t : Registry())
-  {
-    if (!filter.empty() && std::string(t.name).find(filter) == std::string::npos) continue;
-    ++ran;
-    try { t.body(); Device::Synchronize(); std::printf("[  OK  ] %s\n", t.name); }
-    catch (const Failure& f) { ++failed; std::printf("[FAILED] %s\n         %s\n", t.name, f.text.c_str()); }
-    catch (const std::exception& e) { ++failed; std::printf("[FAILED] %s\n         exception: %s\n", t.name, e.what()); }
-    std::fflush(stdout);
-  }
-  std::printf("%d test(s), %d failed\n", ran, failed);
-  return failed ? 1 : 0;
-}
+int main(int argc, char** argv) { return RunTests("mesh_attribute_tests", argc, argv); }

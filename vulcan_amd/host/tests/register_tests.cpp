@@ -2,87 +2,11 @@
 // the reference's Volume is a process-wide singleton, src/volume.cu:17-21). The call's terms, sums and loop are held against
 // the CPU statement by tests/test_gpu_register.py; these cases are what a user of the class sees: a copy is registered as
 // it stands, a source carried by whole blocks has no residual at that shift, and a source displaced by a generic pose is
-// brought back from the identity and then merges as the surface it came from. Harness as in merge_pose_tests.cpp.
+// brought back from the identity and then merges as the surface it came from. Harness: volume_test_support.h.
 //
 //   ./register_tests            run everything (needs a GPU)
 //   ./register_tests <filter>   run the cases whose name contains <filter>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <array>
-#include <functional>
-#include <map>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include <vulcan/vulcan.h>
-
-using namespace vulcan;
-
-struct Failure { std::string text; };
-
-#define STR2(x) #x
-#define STR(x) STR2(x)
-#define FAIL_HERE(msg) throw Failure{std::string(__FILE__ ":" STR(__LINE__) ": ") + (msg)}
-#define ASSERT_TRUE(c) do { if (!(c)) FAIL_HERE("expected true: " #c); } while (0)
-#define ASSERT_EQ(a, b) do { if (!((a) == (b))) FAIL_HERE("expected equal: " #a " vs " #b + \
-    (" (" + std::to_string((double)(a)) + " vs " + std::to_string((double)(b)) + ")")); } while (0)
-#define ASSERT_THROW(stmt) do { bool t__ = false; try { stmt; } catch (const Exception&) { t__ = true; } \
-    if (!t__) FAIL_HERE("expected vulcan::Exception: " #stmt); } while (0)
-
-struct TestCase { const char* name; std::function<void()> body; };
-static std::vector<TestCase>& Registry() { static std::vector<TestCase> r; return r; }
-struct Registrar { Registrar(const char* n, std::function<void()> f) { Registry().push_back({n, f}); } };
-#define TEST(suite, name) static void suite##_##name(); \
-    static Registrar reg_##suite##_##name(#suite "." #name, suite##_##name); static void suite##_##name()
-
-static const int kWidth = 160, kHeight = 120;
-
-static std::shared_ptr<Image> MakeDepth(const std::function<float(int, int)>& f)
-{
-  std::vector<float> host(size_t(kWidth) * kHeight);
-  for (int y = 0; y < kHeight; ++y) for (int x = 0; x < kWidth; ++x) host[size_t(y) * kWidth + x] = f(x, y);
-  auto image = std::make_shared<Image>(kWidth, kHeight);
-  image->CopyFromHost(host.data());
-  return image;
-}
-
-// the scene of tests/register_reference.py: a wall at 1 m with a bump, a dent and a slope — nothing repeats and no direction
-// is free, so the alignment has one answer
-static float Bumps(int x, int y)
-{
-  const double w = kWidth, h = kHeight;
-  const double bump = std::exp(-((x - 0.375 * w) * (x - 0.375 * w) + (y - 0.42 * h) * (y - 0.42 * h)) / (2 * (0.16 * w) * (0.16 * w)));
-  const double dent = std::exp(-((x - 0.69 * w) * (x - 0.69 * w) + (y - 0.67 * h) * (y - 0.67 * h)) / (2 * (0.11 * w) * (0.11 * w)));
-  return float(1.0 + 0.06 * bump - 0.04 * dent + 0.03 * x / w);
-}
-
-static Frame BumpsFrame(const Transform& pose)
-{
-  Frame frame;
-  frame.depth_projection.SetFocalLength(136, 136);
-  frame.depth_projection.SetCenterPoint(80, 60);
-  frame.depth_image = MakeDepth(Bumps);
-  frame.depth_to_world_transform = pose;
-  return frame;
-}
-
-static std::shared_ptr<Volume> Fresh(int main_blocks, int excess_blocks)
-{
-  auto volume = std::make_shared<Volume>(main_blocks, excess_blocks);
-  volume->SetVoxelLength(0.008f);
-  return volume;
-}
-
-static std::shared_ptr<Volume> Fused(int main_blocks, int excess_blocks, const Frame& frame, int integrations)
-{
-  auto volume = Fresh(main_blocks, excess_blocks);
-  for (int i = 0; i < 6; ++i) volume->SetView(frame);
-  DepthIntegrator integrator(volume);
-  for (int i = 0; i < integrations; ++i) integrator.Integrate(frame);
-  return volume;
-}
+#include "volume_test_support.h"
 
 static bool SameMatrices(const Transform& a, const Transform& b)
 {
@@ -195,22 +119,4 @@ TEST(Register, AGenericPoseThenTheMerge)
   ASSERT_TRUE(error / hits < 0.004);                 // half a voxel, as merge_pose_tests' raycast
 }
 
-int main(int argc, char** argv)
-{
-  int count = 0;
-  VK_ASSERT(vk_device_count(&count));
-  if (count == 0) { std::printf("register_tests: no HIP device\n"); return 2; }
-  const std::string filter = argc > 1 ? argv[1] : "";
-  int failed = 0, ran = 0;
-  for (const TestCase& t : Registry())
-  {
-    if (!filter.empty() && std::string(t.name).find(filter) == std::string::npos) continue;
-    ++ran;
-    try { t.body(); Device::Synchronize(); std::printf("[  OK  ] %s\n", t.name); }
-    catch (const Failure& f) { ++failed; std::printf("[FAILED] %s\n         %s\n", t.name, f.text.c_str()); }
-    catch (const std::exception& e) { ++failed; std::printf("[FAILED] %s\n         exception: %s\n", t.name, e.what()); }
-    std::fflush(stdout);
-  }
-  std::printf("%d test(s), %d failed\n", ran, failed);
-  return failed ? 1 : 0;
-}
+int main(int argc, char** argv) { return RunTests("register_tests", argc, argv); }

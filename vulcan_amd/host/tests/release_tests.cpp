@@ -1,66 +1,11 @@
 // release_tests.cpp — Volume::ReleaseBlocks through the C++ class layer -> C ABI -> HIP kernels (no upstream case: the
 // reference's volume only grows, src/volume.cu:304-368). The call's exact outcome is held against its CPU statement by
 // tests/test_gpu_release.py; these cases are what a user of the class sees: blocks come back, an exhausted volume
-// allocates again, and the call refuses to run on top of an announced frame. Harness as in host_tests.cpp.
+// allocates again, and the call refuses to run on top of an announced frame. Harness: volume_test_support.h.
 //
 //   ./release_tests            run everything (needs a GPU)
 //   ./release_tests <filter>   run the cases whose name contains <filter>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <functional>
-#include <string>
-#include <vector>
-
-#include <vulcan/vulcan.h>
-
-using namespace vulcan;
-
-struct Failure { std::string text; };
-
-#define STR2(x) #x
-#define STR(x) STR2(x)
-#define FAIL_HERE(msg) throw Failure{std::string(__FILE__ ":" STR(__LINE__) ": ") + (msg)}
-#define ASSERT_TRUE(c) do { if (!(c)) FAIL_HERE("expected true: " #c); } while (0)
-#define ASSERT_EQ(a, b) do { if (!((a) == (b))) FAIL_HERE("expected equal: " #a " vs " #b + \
-    (" (" + std::to_string((double)(a)) + " vs " + std::to_string((double)(b)) + ")")); } while (0)
-#define ASSERT_THROW(stmt) do { bool t__ = false; try { stmt; } catch (const Exception&) { t__ = true; } \
-    if (!t__) FAIL_HERE("expected vulcan::Exception: " #stmt); } while (0)
-
-struct TestCase { const char* name; std::function<void()> body; };
-static std::vector<TestCase>& Registry() { static std::vector<TestCase> r; return r; }
-struct Registrar { Registrar(const char* n, std::function<void()> f) { Registry().push_back({n, f}); } };
-#define TEST(suite, name) static void suite##_##name(); \
-    static Registrar reg_##suite##_##name(#suite "." #name, suite##_##name); static void suite##_##name()
-
-static const int kWidth = 160, kHeight = 120;
-
-static std::shared_ptr<Image> MakeDepth(const std::function<float(int, int)>& f)
-{
-  std::vector<float> host(size_t(kWidth) * kHeight);
-  for (int y = 0; y < kHeight; ++y) for (int x = 0; x < kWidth; ++x) host[size_t(y) * kWidth + x] = f(x, y);
-  auto image = std::make_shared<Image>(kWidth, kHeight);
-  image->CopyFromHost(host.data());
-  return image;
-}
-
-static Frame SlantedFrame(const Transform& pose)
-{
-  Frame frame;
-  frame.depth_projection.SetFocalLength(136, 136);
-  frame.depth_projection.SetCenterPoint(80, 60);
-  frame.depth_image = MakeDepth([](int x, int y) { return 1.5f + 0.001f * x + 0.0007f * y; });
-  frame.depth_to_world_transform = pose;
-  return frame;
-}
-
-static std::vector<vk_hash_entry> Entries(const Volume& volume)
-{
-  const vk_volume v = volume.ToVk();
-  std::vector<vk_hash_entry> host(size_t(v.main_block_count) + v.excess_block_count);
-  VK_ASSERT(vk_memcpy_d2h(host.data(), v.hash_entries, sizeof(vk_hash_entry) * host.size(), Device::GetStream()));
-  return host;
-}
+#include "volume_test_support.h"
 
 // a box release frees what lies outside the box, and nothing else
 TEST(Release, BoxFreesWhatLiesOutside)
@@ -164,22 +109,4 @@ TEST(Release, RefusedWhileAFrameIsAnnounced)
   ASSERT_EQ(announced, counts.kept);
 }
 
-int main(int argc, char** argv)
-{
-  int count = 0;
-  VK_ASSERT(vk_device_count(&count));
-  if (count == 0) { std::printf("release_tests: no HIP device\n"); return 2; }
-  const std::string filter = argc > 1 ? argv[1] : "";
-  int failed = 0, ran = 0;
-  for (const TestCase& t : Registry())
-  {
-    if (!filter.empty() && std::string(t.name).find(filter) == std::string::npos) continue;
-    ++ran;
-    try { t.body(); Device::Synchronize(); std::printf("[  OK  ] %s\n", t.name); }
-    catch (const Failure& f) { ++failed; std::printf("[FAILED] %s\n         %s\n", t.name, f.text.c_str()); }
-    catch (const std::exception& e) { ++failed; std::printf("[FAILED] %s\n         exception: %s\n", t.name, e.what()); }
-    std::fflush(stdout);
-  }
-  std::printf("%d test(s), %d failed\n", ran, failed);
-  return failed ? 1 : 0;
-}
+int main(int argc, char** argv) { return RunTests("release_tests", argc, argv); }
