@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_support import fake_volume
 import cast_reference as CR
 import merge_reference as M
 import register_reference as RR
@@ -170,26 +171,18 @@ def test_the_library_validates_before_touching_a_device():
     lib = api.lib()
     one, odd = C.c_void_p(4096), C.c_void_p(4096 + 8)
 
-    def volume(base=1 << 20):
-        v = T.Volume()
-        for k, name in enumerate(("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks",
-                                  "block_visibility", "visible_blocks", "counters")):
-            setattr(v, name, base + 4096 * k)
-        v.main_block_count, v.excess_block_count, v.voxel_length, v.truncation_length = 8, 8, 0.008, 0.04
-        return v
-
     def params(flags=0, max_steps=500, t_min=0.0, t_max=5.0):
         return T.CastParams(flags, max_steps, t_min, t_max)
 
-    def call(v=volume(), rays=one, count=8, pose=None, p=params(), t_out=one, status=one, samples=one, gradients=one):
+    def call(v=fake_volume(), rays=one, count=8, pose=None, p=params(), t_out=one, status=one, samples=one, gradients=one):
         return lib.vk_volume_cast_rays(C.byref(v) if v else None, rays, count, pose, C.byref(p) if p else None, t_out, status, samples,
                                        gradients, None)
 
     assert call(v=None) == -1 and call(p=None) == -1
-    broken = volume()
+    broken = fake_volume()
     broken.hash_entries = None
     assert call(v=broken) == -1
-    broken = volume()
+    broken = fake_volume()
     broken.voxel_length = 0.0
     assert call(v=broken) == -1
     for flags in (4, 8, -1, 1 << 16):

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_support import fake_volume
 import merge_reference as M
 import release_reference as R
 from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
@@ -166,19 +167,11 @@ def test_abi_validates_before_touching_a_device(api):
     one = C.c_void_p(16)
     assert lib.vk_volume_merge(None, None, None, None, None, None) == -1
 
-    def volume(base):
-        v = T.Volume()
-        for k, name in enumerate(("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks",
-                                  "block_visibility", "visible_blocks", "counters")):
-            setattr(v, name, base + 4096 * k)
-        v.main_block_count, v.excess_block_count, v.voxel_length, v.truncation_length = 8, 8, 0.008, 0.04
-        return v
-
     def call(dst, src, params, counts=one, workspace=one):
         return lib.vk_volume_merge(C.byref(dst), C.byref(src), C.byref(params), counts, workspace, None)
 
     good = T.MergeParams(0, 8, 16.0, 16.0)
-    dst, src = volume(1 << 20), volume(2 << 20)
+    dst, src = fake_volume(1 << 20), fake_volume(2 << 20)
     assert call(dst, src, good, counts=None) == -1
     assert call(dst, src, good, workspace=None) == -1
     assert lib.vk_volume_merge(C.byref(dst), C.byref(src), None, one, one, None) == -1
@@ -186,19 +179,19 @@ def test_abi_validates_before_touching_a_device(api):
     for params in (T.MergeParams(4, 8, 16.0, 16.0), T.MergeParams(0, 0, 16.0, 16.0), T.MergeParams(0, 8, 0.5, 16.0),
                    T.MergeParams(0, 8, 16.0, 32768.0), T.MergeParams(0, 8, float("nan"), 16.0)):
         assert call(dst, src, params) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.voxel_length = 0.005
     assert call(dst, other, good) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.truncation_length = 0.05
     assert call(dst, other, good) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.voxels += 8                                                             # not 16-byte aligned
     assert call(dst, other, good) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.main_block_count = 0
     assert call(dst, other, good) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.hash_entries = None
     assert call(dst, other, good) == -1
     assert lib.vk_volume_merge_workspace_bytes(0, 0) == 0

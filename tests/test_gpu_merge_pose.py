@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_support import fake_volume
 import merge_pose_reference as MP
 import merge_reference as M
 import release_reference as R
@@ -159,21 +160,13 @@ def test_abi_validates_before_touching_a_device(api):
     lib = api.lib()
     one = C.c_void_p(16)
 
-    def volume(base):
-        v = T.Volume()
-        for k, name in enumerate(("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks",
-                                  "block_visibility", "visible_blocks", "counters")):
-            setattr(v, name, base + 4096 * k)
-        v.main_block_count, v.excess_block_count, v.voxel_length, v.truncation_length = 8, 8, 0.008, 0.04
-        return v
-
     def call(dst, src, params, counts=one, workspace=one):
         return lib.vk_volume_merge_posed(C.byref(dst), C.byref(src), C.byref(params), counts, workspace, None)
 
     def params(pose=None, merge=None):
         return T.MergePoseParams(merge or T.MergeParams(0, 8, 16.0, 16.0), pose or T.Transform.identity())
 
-    dst, src = volume(1 << 20), volume(2 << 20)
+    dst, src = fake_volume(1 << 20), fake_volume(2 << 20)
     assert call(dst, src, params(), counts=None) == -1
     assert call(dst, src, params(), workspace=None) == -1
     assert call(dst, dst, params()) == -1                                         # into itself
@@ -188,12 +181,12 @@ def test_abi_validates_before_touching_a_device(api):
     for merge in (T.MergeParams(4, 8, 16.0, 16.0), T.MergeParams(0, 0, 16.0, 16.0), T.MergeParams(0, 8, 0.5, 16.0),
                   T.MergeParams(0, 8, 16.0, float("nan"))):
         assert call(dst, src, params(merge=merge)) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.voxel_length = 0.005
     assert call(dst, other, params()) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.truncation_length = 0.05
     assert call(dst, other, params()) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.voxels += 8                                                             # not 16-byte aligned
     assert call(dst, other, params()) == -1

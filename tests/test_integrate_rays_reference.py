@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_support import fake_volume
 import cast_reference as CR
 import integrate_rays_reference as IR
 import merge_reference as M
@@ -192,25 +193,17 @@ def test_the_library_validates_before_touching_a_device():
     lib = api.lib()
     one, odd = C.c_void_p(4096), C.c_void_p(4096 + 8)
 
-    def volume(base=1 << 20):
-        v = T.Volume()
-        for k, name in enumerate(("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks",
-                                  "block_visibility", "visible_blocks", "counters")):
-            setattr(v, name, base + 4096 * k)
-        v.main_block_count, v.excess_block_count, v.voxel_length, v.truncation_length = 8, 8, 0.008, 0.04
-        return v
-
     def params(flags=0, max_rounds=8, r_min=0.1, r_max=5.0, cap=16.0):
         return T.IntegrateRaysParams(flags, max_rounds, r_min, r_max, cap, 0)
 
-    def call(v=volume(), rays=one, ranges=one, count=8, pose=None, p=params(), counts=one, workspace=one):
+    def call(v=fake_volume(), rays=one, ranges=one, count=8, pose=None, p=params(), counts=one, workspace=one):
         return lib.vk_volume_integrate_rays(C.byref(v) if v else None, rays, ranges, count, pose, C.byref(p) if p else None, counts,
                                             workspace, None)
 
     assert call(v=None) == -1 and call(p=None) == -1 and call(counts=None) == -1 and call(workspace=None) == -1
     for field, value in (("hash_entries", None), ("voxel_length", 0.0), ("main_block_count", 0), ("voxels", (1 << 20) + 8),
                          ("truncation_length", 0.008 * 64.5)):
-        broken = volume()
+        broken = fake_volume()
         setattr(broken, field, value)
         assert call(v=broken) == -1, field
     for flags in (4, 8, -1, 1 << 16):

@@ -5,6 +5,7 @@ statement's own sample. No GPU: the device is held to the same statement in test
 import numpy as np
 import pytest
 
+from abi_support import fake_volume
 import merge_pose_reference as MP
 import register_reference as RR
 import release_reference as R
@@ -104,20 +105,12 @@ def test_the_library_validates_before_touching_a_device():
     lib = api.lib()
     one = C.c_void_p(4096)
 
-    def volume(base):
-        v = T.Volume()
-        for k, name in enumerate(("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks",
-                                  "block_visibility", "visible_blocks", "counters")):
-            setattr(v, name, base + 4096 * k)
-        v.main_block_count, v.excess_block_count, v.voxel_length, v.truncation_length = 8, 8, 0.008, 0.04
-        return v
-
     good = T.RegisterParams(0, 20, 0.75, 0)
 
     def loop(dst, src, params=good, pose=one, system=one, state=one, counts=one, workspace=one):
         return lib.vk_volume_register(C.byref(dst), C.byref(src), pose, C.byref(params), system, state, counts, None, workspace, None)
 
-    dst, src = volume(1 << 20), volume(2 << 20)
+    dst, src = fake_volume(1 << 20), fake_volume(2 << 20)
     for name in ("pose", "system", "state", "counts", "workspace"):
         assert loop(dst, src, **{name: None}) == -1
     assert lib.vk_volume_register(None, C.byref(src), one, C.byref(good), one, one, one, None, one, None) == -1
@@ -126,13 +119,13 @@ def test_the_library_validates_before_touching_a_device():
     for bad in (T.RegisterParams(1, 20, 0.75, 0), T.RegisterParams(0, 0, 0.75, 0), T.RegisterParams(0, 65, 0.75, 0),
                 T.RegisterParams(0, 20, 0.0, 0), T.RegisterParams(0, 20, 1.5, 0), T.RegisterParams(0, 20, float("nan"), 0)):
         assert loop(dst, src, params=bad) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.voxel_length = 0.005
     assert loop(dst, other) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.truncation_length = 0.05
     assert loop(dst, other) == -1
-    other = volume(2 << 20)
+    other = fake_volume(2 << 20)
     other.counters = None
     assert loop(dst, other) == -1 and loop(other, src) == -1
     assert lib.vk_volume_register_system(C.byref(dst), C.byref(src), one, C.byref(good), None, one, one, None) == -1

@@ -14,15 +14,12 @@ is the parent commit's file byte for byte, so the stage is the parent's. The cas
 
 ref: src/tracer.cu:317-451 (the march), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
-import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
 
 def pixel_rays(k, pose, w, h):
@@ -48,30 +45,10 @@ def main():
 
     import torch
     import bench
-    import scenes
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
 
-    # tools/kbench.py's steady state
-    k = T.Projection.make(*scenes.APP_INTRINSICS)
-    depth = bench.sphere_room_depth(k)
-    poses = [scenes.orbit_pose(i, bench.YAW_STEP) for i in range(args.frames + 1)]
-    vol = api.Volume(bench.MAIN, bench.EXCESS, voxel_length=bench.VOXEL, truncation_length=bench.TRUNC)
-    frame = api.Frame(depth, k, poses[0])
-    out = api.Frame(torch.zeros((bench.H, bench.W), dtype=torch.float32, device="cuda"), k, poses[0])
-    integ = api.DepthIntegrator(vol)
-    tracer = api.Tracer(vol)
-    for i in range(args.frames):
-        frame.depth_to_world = poses[i]
-        out.depth_to_world = poses[i]
-        vol.set_view(frame)
-        integ.integrate(frame)
-        tracer.trace(out)
-    view = poses[args.frames]
-    frame.depth_to_world = view
-    out.depth_to_world = view
-    vol.set_view(frame)
-    torch.cuda.synchronize()
+    k, vol, frame, out, integ, tracer, view = S.steady_state(args.frames)
     depths = torch.zeros((bench.H, bench.W), dtype=torch.float32, device="cuda")
     colors = torch.zeros((bench.H, bench.W, 3), dtype=torch.float32, device="cuda")
 
@@ -155,10 +132,7 @@ def main():
            "raycast_us": raycast, "cast_us": results}
     if other is not None:
         doc["variant"] = {"library": os.path.basename(args.variant), "cast_us": variant}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -21,16 +21,12 @@ view) and one cast_rays call, timed as tools/cast_bench.py times them. One JSON 
 ref: src/depth_integrator.cu:54-115 (the integrator the rays stand in for), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
 import ctypes as C
-import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
 PASSES = ("rounds", "mark", "zero", "add", "fold")
 BUFFERS = ("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks", "block_visibility",
@@ -50,31 +46,12 @@ def main():
 
     import torch
     import bench
-    import scenes
     from cast_bench import pixel_rays
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
     lib = api.lib()
 
-    # tools/cast_bench.py's steady state and view
-    k = T.Projection.make(*scenes.APP_INTRINSICS)
-    depth = bench.sphere_room_depth(k)
-    poses = [scenes.orbit_pose(i, bench.YAW_STEP) for i in range(args.frames + 1)]
-    vol = api.Volume(bench.MAIN, bench.EXCESS, voxel_length=bench.VOXEL, truncation_length=bench.TRUNC)
-    frame = api.Frame(depth, k, poses[0])
-    out = api.Frame(torch.zeros((bench.H, bench.W), dtype=torch.float32, device="cuda"), k, poses[0])
-    integ = api.DepthIntegrator(vol)
-    tracer = api.Tracer(vol)
-    for i in range(args.frames):
-        frame.depth_to_world = poses[i]
-        out.depth_to_world = poses[i]
-        vol.set_view(frame)
-        integ.integrate(frame)
-        tracer.trace(out)
-    view = poses[args.frames]
-    frame.depth_to_world = view
-    vol.set_view(frame)
-    torch.cuda.synchronize()
+    k, vol, frame, out, integ, tracer, view = S.steady_state(args.frames)
 
     def events(n):
         made = []
@@ -128,11 +105,10 @@ def main():
     per_update = 1 if count < (1 << 21) else 2
     results = {}
     for target, volume in (("populated", vol), ("fresh", fresh)):
-        saved = {name: getattr(volume, name).clone() for name in BUFFERS}
+        saved = S.save(volume, BUFFERS)
 
         def restore():
-            for name in BUFFERS:
-                getattr(volume, name).copy_(saved[name])
+            S.restore(volume, saved)
 
         for name, (rays, rng) in inputs.items():
             call = lambda: volume._integrate_rays_call(rays, rng, None, T.VK_RAYS_ONE_OBSERVATION, 8, r_min, r_max, 16.0)   # noqa: E731
@@ -167,10 +143,7 @@ def main():
            "method": f"HIP events; median of {args.reps} calls, the volume's buffers restored from a device copy in front of each; the "
                      "passes from the events the call records between them (vk_volume_integrate_rays_time_next)",
            "for_scale_us": scale, "integrate_rays_us": results}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -23,17 +23,11 @@ flushed the same way. One JSON line to --out (profiles/merge_bench.json).
 ref: src/volume.cu:304-368 (the allocator the rounds go through), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
 import ctypes as C
-import json
 import os
-import sys
 
-import numpy as np
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-STATE = ("hash_entries", "block_visibility", "free_voxel_blocks", "counters")
 BYTES_PER_FUSED_BLOCK = 3 * 10240
 
 
@@ -46,58 +40,31 @@ def main():
 
     import torch
     import bench
-    import scenes
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
     lib = api.lib()
 
-    vols = []
-    for half in range(2):
-        poses = [scenes.orbit_pose(half * args.frames + i, bench.YAW_STEP) for i in range(args.frames)]
-        loop = bench.FrameLoop("depth", poses)
-        for i in range(args.frames):
-            loop.step(i)          # (the last step announces no further frame: the volume is between SetView calls)
-        torch.cuda.synchronize()
-        vols.append(loop.vols[0]["vol"])
-        del loop
+    vols = S.replicas(args.frames)
     dst, src = vols
     fresh = api.Volume(src.main, src.excess, voxel_length=bench.VOXEL, truncation_length=bench.TRUNC)
     blocks = [int((v.host_entries()["data"] >= 0).sum()) for v in vols]
 
-    def snapshot():
-        return {name: getattr(dst, name).clone() for name in STATE}, dst.voxels.clone()
-
-    before = snapshot()
+    before = S.save(dst)
     workspace = api._dev_bytes(lib.vk_volume_merge_workspace_bytes(src.main, src.excess), "cuda")
     counts = torch.zeros(6, dtype=torch.int32, device="cuda")
     ddesc, sdesc, fdesc = dst.desc(), src.desc(), fresh.desc()
-    flush = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-
-    def restore(state):
-        for name in STATE:
-            getattr(dst, name).copy_(state[0][name])
-        dst.voxels.copy_(state[1])
-        flush.fill_(1)
+    flush = S.flush_buffer()
 
     def timed(state, source, max_rounds):
         params = T.MergeParams(0, max_rounds, 16.0, 16.0)
-        times = []
-        for rep in range(args.reps + 2):
-            restore(state)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+
+        def call():
             api.check(lib.vk_volume_merge(C.byref(ddesc), C.byref(source), C.byref(params), api._ptr(counts), api._ptr(workspace),
                                           api.stream()), "vk_volume_merge")
-            e1.record()
-            e1.synchronize()
-            if rep >= 2:                                   # two warm-up repetitions
-                times.append(e0.elapsed_time(e1) * 1e3)
-        t = np.array(times)
-        return {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max()),
-                "counts": [int(c) for c in counts.cpu().numpy()]}
+        return dict(S.timed(call, args.reps, flush, lambda: S.restore(dst, state)), counts=[int(c) for c in counts.cpu().numpy()])
 
     results = {"call": timed(before, sdesc, 8)}
-    merged = snapshot()                                    # the destination after a merge: every source block is present
+    merged = S.save(dst)                                   # the destination after a merge: every source block is present
     results["settled"] = timed(merged, sdesc, 8)
     results["settled_1"] = timed(merged, sdesc, 1)
     results["idle_1"] = timed(merged, fdesc, 1)
@@ -113,17 +80,7 @@ def main():
     # the same bytes moved by a device-to-device copy, flushed the same way
     half = torch.empty(fuse_bytes // 2, dtype=torch.uint8, device="cuda")
     other = torch.empty_like(half)
-    times = []
-    for rep in range(args.reps + 2):
-        flush.fill_(1)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        other.copy_(half)
-        e1.record()
-        e1.synchronize()
-        if rep >= 2:
-            times.append(e0.elapsed_time(e1) * 1e3)
-    copy_us = float(np.median(times))
+    copy_us = S.timed(lambda: other.copy_(half), args.reps, flush)["median_us"]
 
     def rate(us):
         return fuse_bytes / (us * 1e-6) / 1e12 if us > 0 else None
@@ -142,10 +99,7 @@ def main():
            "device_to_device_copy": {"what": "torch copy_ of bytes / 2 (read + write = the same bytes moved), same flush, same run",
                                      "us": copy_us, "bytes_moved": fuse_bytes, "TB_per_s": rate(copy_us)},
            "skip_unobserved": "not timed: the classification is one more read of the source's allocated blocks (10 240 B each)"}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

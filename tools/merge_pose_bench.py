@@ -18,34 +18,21 @@ One JSON line to --out (profiles/merge_pose_bench.json).
 ref: src/volume.cu:304-368 (the allocator the rounds go through), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
 import ctypes as C
-import csv
-import glob
-import json
 import os
-import sys
 
-import numpy as np
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-STATE = ("hash_entries", "block_visibility", "free_voxel_blocks", "counters")
 BLOCK_BYTES = 10240
 
 
-def kernels(directory):
+def kernel_summary(directory):
     """per kernel of a rocprofv3 --kernel-trace run: calls and the median / min / max duration in us"""
-    path = glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True)[0]
-    durations = {}
-    for row in csv.DictReader(open(path)):
-        name = row["Kernel_Name"].split("(")[0].replace("(anonymous namespace)::", "").replace("void ", "")
-        durations.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-3)
-    print(f"{'kernel':<44}{'calls':>6}{'median':>9}{'min':>9}{'max':>9}")
+    durations = S.kernel_durations(directory)
+    print(S.KERNEL_HEADER)
     for name in sorted(durations):
         if any(word in name for word in ("pose_", "merge_", "handle")):
-            t = np.array(durations[name])
-            print(f"{name:<44}{len(t):>6}{np.median(t):>9.2f}{t.min():>9.2f}{t.max():>9.2f}")
+            print(S.kernel_row(name, durations[name]))
     # the fuse pass by set-up: its launches in stream order, --reps + 2 per set-up
     for name in ("merge_fuse_kernel", "pose_fuse_kernel"):
         t = [d for key, values in durations.items() if name in key for d in values]
@@ -60,59 +47,41 @@ def main():
     ap.add_argument("--kernels", help="summarise the kernel trace in this directory instead of running")
     args = ap.parse_args()
     if args.kernels:
-        return kernels(args.kernels)
+        return kernel_summary(args.kernels)
 
     import torch
     import bench
     import merge_pose_reference as MP
-    import scenes
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
     lib = api.lib()
 
-    vols = []
-    for half in range(2):
-        poses = [scenes.orbit_pose(half * args.frames + i, bench.YAW_STEP) for i in range(args.frames)]
-        loop = bench.FrameLoop("depth", poses)
-        for i in range(args.frames):
-            loop.step(i)          # (the last step announces no further frame: the volume is between SetView calls)
-        torch.cuda.synchronize()
-        vols.append(loop.vols[0]["vol"])
-        del loop
+    vols = S.replicas(args.frames)
     dst, src = vols
     blocks = [int((v.host_entries()["data"] >= 0).sum()) for v in vols]
-    before = {name: getattr(dst, name).clone() for name in STATE}, dst.voxels.clone()
+    before = S.save(dst)
     plain_workspace = api._dev_bytes(lib.vk_volume_merge_workspace_bytes(src.main, src.excess), "cuda")
     posed_workspace = api._dev_bytes(lib.vk_volume_merge_posed_workspace_bytes(src.main, src.excess, dst.main, dst.excess), "cuda")
     counts = torch.zeros(8, dtype=torch.int32, device="cuda")
     ddesc, sdesc = dst.desc(), src.desc()
-    flush = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+    flush = S.flush_buffer()
 
     def timed(pose):
         merge = T.MergeParams(0, 8, 16.0, 16.0)
         posed = T.MergePoseParams(merge, pose) if pose is not None else None
-        times = []
-        for rep in range(args.reps + 2):
-            for name in STATE:
-                getattr(dst, name).copy_(before[0][name])
-            dst.voxels.copy_(before[1])
+
+        def before_each():
+            S.restore(dst, before)
             counts.zero_()
-            flush.fill_(1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+
+        def call():
             if posed is None:
                 api.check(lib.vk_volume_merge(C.byref(ddesc), C.byref(sdesc), C.byref(merge), api._ptr(counts),
                                               api._ptr(plain_workspace), api.stream()), "vk_volume_merge")
             else:
                 api.check(lib.vk_volume_merge_posed(C.byref(ddesc), C.byref(sdesc), C.byref(posed), api._ptr(counts),
                                                     api._ptr(posed_workspace), api.stream()), "vk_volume_merge_posed")
-            e1.record()
-            e1.synchronize()
-            if rep >= 2:                                   # two warm-up repetitions
-                times.append(e0.elapsed_time(e1) * 1e3)
-        t = np.array(times)
-        out = {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max()),
-               "counts": [int(c) for c in counts.cpu().numpy()][:8 if posed else 6]}
+        out = dict(S.timed(call, args.reps, flush, before_each), counts=[int(c) for c in counts.cpu().numpy()][:8 if posed else 6])
         if posed:
             # blocks a candidate took no sample into: allocated by the call and still Voxel::Empty()
             entries, voxels = dst.host_entries(), dst.host_voxels()
@@ -138,10 +107,7 @@ def main():
            "candidates_per_source_block": {k: results[k]["counts"][1] / max(results[k]["counts"][0], 1) for k in ("identity", "generic")},
            "fuse_pass_bytes": {"what": "2 x 10 240 B per fused dst block (read, write) + 10 240 B per source block (each read once at least)",
                                "identity": fuse_bytes(results["identity"]), "generic": fuse_bytes(results["generic"])}}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -20,36 +20,25 @@ The residual pass against the yardstick's fuse pass, kernel by kernel, comes fro
 ref: src/tracker.cpp:124-163 (the loop), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
 import ctypes as C
-import csv
-import glob
-import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
-STATE = ("hash_entries", "block_visibility", "free_voxel_blocks", "counters")
 BLOCK_BYTES = 10240
 
 
-def kernels(directory):
+def kernel_summary(directory):
     """per kernel of a rocprofv3 --kernel-trace run: calls and the median / min / max duration in us"""
-    path = glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True)[0]
-    durations = {}
-    for row in csv.DictReader(open(path)):
-        name = row["Kernel_Name"].split("(")[0].replace("(anonymous namespace)::", "").replace("void ", "")
-        durations.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-3)
-    print(f"{'kernel':<44}{'calls':>6}{'median':>9}{'min':>9}{'max':>9}")
+    durations = S.kernel_durations(directory)
+    print(S.KERNEL_HEADER)
     medians = {}
     for name in sorted(durations):
         if any(word in name for word in ("register_", "pose_fuse")):
-            t = np.array(durations[name])
-            medians[name.split("<")[0]] = float(np.median(t))
-            print(f"{name:<44}{len(t):>6}{np.median(t):>9.2f}{t.min():>9.2f}{t.max():>9.2f}")
+            medians[name.split("<")[0]] = float(np.median(durations[name]))
+            print(S.kernel_row(name, durations[name]))
     if "register_pass_kernel" in medians and "pose_fuse_kernel" in medians:
         print(f"residual pass / fuse pass: {medians['register_pass_kernel'] / medians['pose_fuse_kernel']:.2f}")
 
@@ -89,33 +78,23 @@ def main():
     ap.add_argument("--kernels", help="summarise the kernel trace in this directory instead of running")
     args = ap.parse_args()
     if args.kernels:
-        return kernels(args.kernels)
+        return kernel_summary(args.kernels)
 
     import torch
     import bench
     import merge_pose_reference as MP
-    import scenes
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
     lib = api.lib()
 
-    vols = []
-    for half in range(2):
-        poses = [scenes.orbit_pose(half * args.frames + i, bench.YAW_STEP) for i in range(args.frames)]
-        loop = bench.FrameLoop("depth", poses)
-        for i in range(args.frames):
-            loop.step(i)          # (the last step announces no further frame: the volume is between SetView calls)
-        torch.cuda.synchronize()
-        vols.append(loop.vols[0]["vol"])
-        del loop
-    dst, src = vols
+    dst, src = vols = S.replicas(args.frames)
     blocks = [int((v.host_entries()["data"] >= 0).sum()) for v in vols]
     pose = MP.generic()
-    before = {name: getattr(dst, name).clone() for name in STATE}, dst.voxels.clone()
+    before = S.save(dst)
     posed_workspace = api._dev_bytes(lib.vk_volume_merge_posed_workspace_bytes(src.main, src.excess, dst.main, dst.excess), "cuda")
     merge_counts = torch.zeros(8, dtype=torch.int32, device="cuda")
     ddesc, sdesc = dst.desc(), src.desc()
-    flush = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+    flush = S.flush_buffer()
     b, one = dst._register_setup(src, pose, 1, args.band)
     many = T.RegisterParams(0, args.iterations, float(args.band), 0)
     posed = T.MergePoseParams(T.MergeParams(0, 8, 16.0, 16.0), pose)
@@ -134,24 +113,12 @@ def main():
                                             api._ptr(posed_workspace), api.stream()), "vk_volume_merge_posed")
 
     def timed(call, restore=False):
-        times = []
-        for rep in range(args.reps + 2):
+        def before_each():
             if restore:
-                for name in STATE:
-                    getattr(dst, name).copy_(before[0][name])
-                dst.voxels.copy_(before[1])
+                S.restore(dst, before)
             api.check(lib.vk_transform_upload(api._ptr(b["pose"]), C.byref(pose), api.stream()), "vk_transform_upload")
             b["state"].zero_()
-            flush.fill_(1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            e1.synchronize()
-            if rep >= 2:                                   # two warm-up repetitions
-                times.append(e0.elapsed_time(e1) * 1e3)
-        t = np.array(times)
-        return {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max())}
+        return S.timed(call, args.reps, flush, before_each)
 
     results = {"system": timed(system)}
     results["system"]["counts"] = [int(c) for c in b["counts"].cpu().numpy()]
@@ -162,9 +129,7 @@ def main():
     banded_blocks, named = pass_bytes(dst, src, pose, args.band)           # (before the merge changes dst for good)
     results["merge"] = timed(merge, restore=True)
     results["merge"]["counts"] = [int(c) for c in merge_counts.cpu().numpy()]
-    for name in STATE:
-        getattr(dst, name).copy_(before[0][name])
-    dst.voxels.copy_(before[1])
+    S.restore(dst, before)
 
     counts = results["system"]["counts"]
     doc = {"tool": "tools/register_bench.py", "device": torch.cuda.get_device_name(0),
@@ -178,10 +143,7 @@ def main():
                                    "bytes": (counts[0] + named) * BLOCK_BYTES},
            "fuse_pass_bytes": {"what": "the yardstick: 2 x 10 240 B per fused dst block (read, write) + 10 240 B per source block",
                                "bytes": (2 * results["merge"]["counts"][2] + blocks[1]) * BLOCK_BYTES}}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

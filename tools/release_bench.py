@@ -18,19 +18,13 @@ image). One JSON line to --out (profiles/release_bench.json).
 ref: src/volume.cu:304-368 (the allocator that never returns a slot), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
 import ctypes as C
-import json
 import os
 import re
 import subprocess
 import sys
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-STATE = ("hash_entries", "block_visibility", "free_voxel_blocks", "counters")
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
 
 def main():
@@ -42,51 +36,26 @@ def main():
 
     import torch
     import bench
-    import scenes
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
     lib = api.lib()
 
-    poses = [scenes.orbit_pose(i, bench.YAW_STEP) for i in range(args.frames)]
-    loop = bench.FrameLoop("depth", poses)
-    for i in range(args.frames):
-        loop.step(i)          # (the last step announces no further frame: the volume is between SetView calls)
-    torch.cuda.synchronize()
-    vol = loop.vols[0]["vol"]
+    vol, = S.replicas(args.frames, 1)
     counters = vol.read_counters()
     visible = int(counters[T.VK_CTR_VISIBLE])
     allocated = int((vol.host_entries()["data"] >= 0).sum())
 
-    saved = {name: getattr(vol, name).clone() for name in STATE}
-    saved_voxels = vol.voxels.clone()
+    saved = S.save(vol)
     workspace = api._dev_bytes(lib.vk_volume_release_workspace_bytes(vol.main, vol.excess), "cuda")
     counts = torch.zeros(4, dtype=torch.int32, device="cuda")
     vdesc = vol.desc()
+    flush = S.flush_buffer()
 
-    flush = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-
-    def restore(voxels):
-        for name in STATE:
-            getattr(vol, name).copy_(saved[name])
-        if voxels:
-            vol.voxels.copy_(saved_voxels)
-            flush.fill_(1)
-
-    def timed(rule, restore_voxels):
-        times = []
-        for rep in range(args.reps + 2):
-            restore(restore_voxels)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+    def timed(rule):
+        def call():
             api.check(lib.vk_volume_release_blocks(C.byref(vdesc), C.byref(rule), api._ptr(counts), api._ptr(workspace), api.stream()),
                       "vk_volume_release_blocks")
-            e1.record()
-            e1.synchronize()
-            if rep >= 2:                                   # two warm-up repetitions
-                times.append(e0.elapsed_time(e1) * 1e3)
-        t = np.array(times)
-        return {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max()),
-                "counts": [int(c) for c in counts.cpu().numpy()]}
+        return dict(S.timed(call, args.reps, flush, lambda: S.restore(vol, saved)), counts=[int(c) for c in counts.cpu().numpy()])
 
     repair = T.ReleaseRule()
     read_all = T.ReleaseRule()
@@ -95,7 +64,7 @@ def main():
     box.flags = T.VK_RELEASE_OUTSIDE_BOX
     box.keep_lo[:] = [0, -32768, -32768]
     box.keep_hi[:] = [32767, 32767, 32767]
-    results = {"repair": timed(repair, True), "read_all": timed(read_all, True), "box_keeps_x_ge_0": timed(box, True)}
+    results = {"repair": timed(repair), "read_all": timed(read_all), "box_keeps_x_ge_0": timed(box)}
     assert results["read_all"]["counts"][0] == 0 and results["repair"]["counts"][1] == allocated
     stream_us = results["read_all"]["median_us"] - results["repair"]["median_us"]
     classify_gbs = allocated * 10240 / (stream_us * 1e-6) / 1e9 if stream_us > 0 else None
@@ -105,7 +74,7 @@ def main():
     volume = {"main_blocks": vol.main, "excess_blocks": vol.excess, "voxel_length": bench.VOXEL, "frames_fused": args.frames,
               "allocated_blocks": allocated, "visible_blocks": visible, "excess_pointer": int(counters[T.VK_CTR_EXCESS_PTR])}
     # the depth integrate launch on the same pool: tools/kbench.py's own figure, from a process of its own
-    del saved_voxels, flush, loop, vol
+    del saved, flush, vol
     torch.cuda.empty_cache()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kbench.py"), "--frames", str(args.frames), "--only", "integrate"],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300).stdout
@@ -126,10 +95,7 @@ def main():
            "depth_integrate": {"what": "python tools/kbench.py --only integrate, same run: vk_integrate_depth after the same frames, back-to-back "
                                        "launches (warm: each re-reads what the one before wrote; read + write of every visible block)",
                                "us": integrate_us, "visible_blocks": nvis, "GB_per_s_algorithmic": integrate_gbs}}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -20,42 +20,34 @@ One JSON line to --out (profiles/sample_bench.json). No threshold is set on thes
 ref: src/tracer.cu:238-299 (the trilinear sample of a ray), apps/vulcan/vulcan.cu:283-325 (the workload)."""
 import argparse
 import ctypes as C
-import csv
-import glob
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import volume_bench_support as S
+from volume_bench_support import ROOT
 
 SIDE = 512                       # 4 slices of SIDE x SIDE points = 2^20
 
 
-def kernels(directory):
+def kernel_summary(directory):
     """per kernel of a rocprofv3 --kernel-trace run: calls and the median / min / max duration in us; the sample kernels per
     point and the residual pass per in-band voxel, from the run's own JSON. A form's launches come in the run's order: the
     first half in slice order, the second shuffled."""
-    path = glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True)[0]
     run = json.loads(open(os.path.join(directory, "run.json")).read())
-    durations = {}
-    for row in sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"])):
-        name = row["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-        durations.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-3)
+    durations = S.kernel_durations(directory)
     rows = []
     for name in sorted(durations):
-        t = np.array(durations[name])
+        t = durations[name]
         if "sample_kernel" in name:
             rows.append((name + " slice order", t[:len(t) // 2], run["points"]))
             rows.append((name + " shuffled", t[len(t) // 2:], run["points"]))
         elif "register_pass" in name:
             rows.append((name, t, run["register_system"]["counts"][1]))
-    print(f"{'kernel':<44}{'calls':>6}{'median':>9}{'min':>9}{'max':>9}{'ns / item':>11}")
+    print(f"{S.KERNEL_HEADER}{'ns / item':>11}")
     for name, t, items in rows:
-        print(f"{name:<44}{len(t):>6}{np.median(t):>9.2f}{t.min():>9.2f}{t.max():>9.2f}{1e3 * np.median(t) / max(items, 1):>11.4f}")
+        print(f"{S.kernel_row(name, t)}{1e3 * np.median(t) / max(items, 1):>11.4f}")
     print(f"(an item: one of the {run['points']} points of sample_kernel, {run['points_with_a_distance_sample']} of which have a sample; "
           f"one of the {run['register_system']['counts'][1]} in-band source voxels of register_pass_kernel, "
           f"{run['register_system']['counts'][2]} of which give a residual)")
@@ -109,26 +101,16 @@ def main():
     ap.add_argument("--kernels", help="summarise the kernel trace in this directory instead of running")
     args = ap.parse_args()
     if args.kernels:
-        return kernels(args.kernels)
+        return kernel_summary(args.kernels)
 
     import torch
     import bench
     import merge_pose_reference as MP
-    import scenes
     from vulcan_amd import api, vk_types as T
     torch.cuda.set_device(0)
     lib = api.lib()
 
-    vols = []
-    for half in range(2):
-        poses = [scenes.orbit_pose(half * args.frames + i, bench.YAW_STEP) for i in range(args.frames)]
-        loop = bench.FrameLoop("depth", poses)
-        for i in range(args.frames):
-            loop.step(i)          # (the last step announces no further frame: the volume is between SetView calls)
-        torch.cuda.synchronize()
-        vols.append(loop.vols[0]["vol"])
-        del loop
-    dst, src = vols
+    dst, src = S.replicas(args.frames)
     ordered = slices(dst)
     count = len(ordered)
     shuffled = ordered[np.random.default_rng(17).permutation(count)]
@@ -136,30 +118,16 @@ def main():
     points = {"slice_order": torch.as_tensor(ordered).cuda(), "shuffled": torch.as_tensor(shuffled).cuda()}
     samples = torch.empty((count, 20), dtype=torch.uint8, device="cuda")
     gradients = torch.empty((count, 4), dtype=torch.float32, device="cuda")
-    flush = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+    flush = S.flush_buffer()
     b, one = dst._register_setup(src, MP.generic(), 1, args.band)
     ddesc, sdesc = dst.desc(), src.desc()
-
-    def timed(call):
-        times = []
-        for rep in range(args.reps + 2):
-            flush.fill_(1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            e1.synchronize()
-            if rep >= 2:                                   # two warm-up repetitions
-                times.append(e0.elapsed_time(e1) * 1e3)
-        t = np.array(times)
-        return {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max())}
 
     forms = {"distance_only": (T.VK_SAMPLE_DISTANCE_ONLY, (samples, None), 12 + 20, used * 8),
              "full": (0, (samples, gradients), 12 + 20 + 16, eight * 20)}
     results = {}
     for order, tensor in points.items():
         for form, (flags, out, per_point, voxel_bytes) in forms.items():
-            r = timed(lambda: dst._sample_call(tensor, None, flags, count=count, out=out))
+            r = S.timed(lambda: dst._sample_call(tensor, None, flags, count=count, out=out), args.reps, flush)
             r["points_per_second"] = count / (r["median_us"] * 1e-6)
             r["bytes"] = count * per_point + voxel_bytes
             r["gigabytes_per_second"] = r["bytes"] / (r["median_us"] * 1e-6) * 1e-9
@@ -171,7 +139,7 @@ def main():
         api.check(lib.vk_volume_register_system(C.byref(ddesc), C.byref(sdesc), api._ptr(b["pose"]), C.byref(one), api._ptr(b["system"]),
                                                 api._ptr(b["counts"]), api._ptr(b["workspace"]), api.stream()), "vk_volume_register_system")
 
-    register = timed(system)
+    register = S.timed(system, args.reps, flush)
     register["counts"] = [int(c) for c in b["counts"].cpu().numpy()]
 
     doc = {"tool": "tools/sample_bench.py", "device": torch.cuda.get_device_name(0),
@@ -182,10 +150,7 @@ def main():
            "method": f"HIP events around the enqueue on the stream, the Infinity Cache flushed in front of every repetition, 2 warm-up + {args.reps} timed, median",
            "bytes_what": "points x (12 in + 20 for a sample, + 16 for a gradient) + distinct voxels touched x 8 (distance only: the USED points) or 20 (full: all eight)",
            "sample_us": results, "register_system": register}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(doc) + "\n")
-    print(json.dumps(doc))
+    S.write(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -231,6 +231,33 @@ def to_numpy(t, dtype):
     return np.frombuffer(t.cpu().numpy().tobytes(), dtype=dtype).copy()
 
 
+# -- what the callers of the volume operations share
+def _as_pose(pose, device=False, identity=False):
+    """The pose argument of a volume operation. None: None, or the identity with `identity`. A T.Transform: itself. With
+    `device`, anything with data_ptr (a device buffer that holds a vk_transform): itself. Anything else is a 4x4 array:
+    the Transform of the matrix and its inverse, taken once, on the host."""
+    if pose is None:
+        return T.Transform.identity() if identity else None
+    if isinstance(pose, T.Transform) or (device and hasattr(pose, "data_ptr")):
+        return pose
+    matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+    return T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+
+
+def _float_tensor(x, last, message, rows=None):
+    """`x`, contiguous, if it is a float32 tensor [N, last] (`last` None: [N]; `rows`: with that N); VkError(message) if not"""
+    import torch
+    if not (hasattr(x, "data_ptr") and x.dtype == torch.float32 and x.dim() == (1 if last is None else 2)
+            and (last is None or x.shape[1] == last) and (rows is None or x.shape[0] == rows)):
+        raise VkError(message)
+    return x.contiguous()
+
+
+def _ints(counts):
+    """a device tensor of counts as a tuple of int: one blocking read"""
+    return tuple(int(c) for c in counts.cpu().numpy())
+
+
 _STAMP = [0]
 
 
@@ -410,6 +437,7 @@ class Volume:
         # a Tracer attaches its scratch and settings here
         self.view_bounds = None
         self._view_records = []      # every Tracer's record: all go stale when the visible list changes
+        self._workspaces = {}        # {operation: (size, device bytes of its workspace, its counts tensor)}, see _workspace
         check(lib().vk_volume_initialize(_ref(self.desc()), stream()), "vk_volume_initialize")
 
     def attach_view_bounds(self, record):
@@ -529,8 +557,36 @@ class Volume:
         check(lib().vk_requests_ahead_cancel(_ref(self.desc()), _ref(self.requests_ahead), int(rounds), stream()),
               "vk_requests_ahead_cancel")
 
-    _release_workspace = None   # device bytes of vk_volume_release_blocks, allocated by the first release_blocks
-    _release_counts = None
+    # -- what the volume operations below share
+    _sample_pose = None        # the device vk_transform a host pose of sample / cast_rays / integrate_rays is uploaded to
+
+    def _workspace(self, operation, size, workspace_bytes, counts, flags=0):
+        """(workspace, counts tensor) of `operation`: allocated by its first call, again for another `size` (the block
+        counts `workspace_bytes` takes) — which a call that continues the one before (VK_MERGE_CONTINUE) cannot start from"""
+        import torch
+        held = self._workspaces.get(operation)
+        if held is None or held[0] != size:
+            if flags & T.VK_MERGE_CONTINUE:
+                raise VkError("merge: nothing to continue")
+            held = self._workspaces[operation] = (size, _dev_bytes(workspace_bytes(*size), self.device),
+                                                  torch.zeros(counts, dtype=torch.int32, device=self.device))
+        return held[1], held[2]
+
+    def _pose_on_device(self, pose):
+        """`pose` as a launch reads it: a T.Transform is uploaded into this volume's device vk_transform (allocated by the
+        first) and that buffer returned; a device buffer or None passes through — no library call, no allocation"""
+        if not isinstance(pose, T.Transform):
+            return pose
+        if self._sample_pose is None:
+            self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
+        check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
+        return self._sample_pose
+
+    def _table_changes(self):
+        """the hash table and the visible list are about to change: what was made ahead for them is void"""
+        self._view_changed()
+        if self.light_prep is not None:
+            self.light_prep.valid = 0
 
     def release_blocks(self, unobserved=False, min_abs_distance=None, keep_box=None):
         """vk_volume_release_blocks (not upstream): give back the blocks a rule names — `unobserved`: no voxel was ever
@@ -541,7 +597,6 @@ class Volume:
         a frame is announced. The visible list is empty afterwards (the next set_view rebuilds it) and what was
         prepared ahead for the volume is void. Returns (blocks released, blocks kept, excess entries in use, free
         slots) from one blocking read."""
-        import torch
         self._no_requests_pending("release_blocks")
         rule = T.ReleaseRule()
         if unobserved:
@@ -553,73 +608,48 @@ class Volume:
             rule.flags |= T.VK_RELEASE_OUTSIDE_BOX
             rule.keep_lo[:] = [int(c) for c in keep_box[0]]
             rule.keep_hi[:] = [int(c) for c in keep_box[1]]
-        if self._release_workspace is None:
-            self._release_workspace = _dev_bytes(lib().vk_volume_release_workspace_bytes(self.main, self.excess), self.device)
-            self._release_counts = torch.zeros(4, dtype=torch.int32, device=self.device)
-        self._view_changed()
-        if self.light_prep is not None:
-            self.light_prep.valid = 0
-        check(lib().vk_volume_release_blocks(_ref(self.desc()), _ref(rule), _ptr(self._release_counts),
-                                             _ptr(self._release_workspace), stream()), "vk_volume_release_blocks")
-        return tuple(int(c) for c in self._release_counts.cpu().numpy())
-
-    _merge_workspace = None     # device bytes of vk_volume_merge, per source size, allocated by the first merge
-    _merge_counts = None
+        workspace, counts = self._workspace("release", (self.main, self.excess), lib().vk_volume_release_workspace_bytes, 4)
+        self._table_changes()
+        check(lib().vk_volume_release_blocks(_ref(self.desc()), _ref(rule), _ptr(counts), _ptr(workspace), stream()),
+              "vk_volume_release_blocks")
+        return _ints(counts)
 
     def _merge_call(self, other, flags, max_rounds, max_distance_weight, max_color_weight):
         """one vk_volume_merge(self <- other): the six counts from one blocking read"""
-        import torch
         self._no_requests_pending("merge")
         other._no_requests_pending("merge")
-        size = (other.main, other.excess)
-        if self._merge_workspace is None or self._merge_workspace[0] != size:
-            if flags & T.VK_MERGE_CONTINUE:
-                raise VkError("merge: nothing to continue")
-            self._merge_workspace = (size, _dev_bytes(lib().vk_volume_merge_workspace_bytes(*size), self.device))
-            self._merge_counts = torch.zeros(6, dtype=torch.int32, device=self.device)
+        workspace, counts = self._workspace("merge", (other.main, other.excess), lib().vk_volume_merge_workspace_bytes, 6, flags)
         params = T.MergeParams(int(flags), int(max_rounds), float(max_distance_weight), float(max_color_weight))
-        self._view_changed()
-        if self.light_prep is not None:
-            self.light_prep.valid = 0
-        check(lib().vk_volume_merge(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(self._merge_counts),
-                                    _ptr(self._merge_workspace[1]), stream()), "vk_volume_merge")
-        return tuple(int(c) for c in self._merge_counts.cpu().numpy())
-
-    _merge_pose_workspace = None    # device bytes of vk_volume_merge_posed, per pair of sizes
-    _merge_pose_counts = None
+        self._table_changes()
+        check(lib().vk_volume_merge(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(counts), _ptr(workspace), stream()),
+              "vk_volume_merge")
+        return _ints(counts)
 
     def _merge_posed_call(self, other, pose, flags, max_rounds, max_distance_weight, max_color_weight):
         """one vk_volume_merge_posed(self <- other through `pose`, a T.Transform): the eight counts from one blocking read"""
-        import torch
         self._no_requests_pending("merge")
         other._no_requests_pending("merge")
-        size = (other.main, other.excess, self.main, self.excess)
-        if self._merge_pose_workspace is None or self._merge_pose_workspace[0] != size:
-            if flags & T.VK_MERGE_CONTINUE:
-                raise VkError("merge: nothing to continue")
-            self._merge_pose_workspace = (size, _dev_bytes(lib().vk_volume_merge_posed_workspace_bytes(*size), self.device))
-            self._merge_pose_counts = torch.zeros(8, dtype=torch.int32, device=self.device)
+        workspace, counts = self._workspace("merge_posed", (other.main, other.excess, self.main, self.excess),
+                                            lib().vk_volume_merge_posed_workspace_bytes, 8, flags)
         params = T.MergePoseParams(T.MergeParams(int(flags), int(max_rounds), float(max_distance_weight), float(max_color_weight)), pose)
-        self._view_changed()
-        if self.light_prep is not None:
-            self.light_prep.valid = 0
-        check(lib().vk_volume_merge_posed(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(self._merge_pose_counts),
-                                          _ptr(self._merge_pose_workspace[1]), stream()), "vk_volume_merge_posed")
-        return tuple(int(c) for c in self._merge_pose_counts.cpu().numpy())
+        self._table_changes()
+        check(lib().vk_volume_merge_posed(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(counts), _ptr(workspace),
+                                          stream()), "vk_volume_merge_posed")
+        return _ints(counts)
 
-    def _merge_posed(self, other, pose, max_distance_weight, max_color_weight, skip_unobserved, max_rounds):
-        if not isinstance(pose, T.Transform):
-            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
-            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))      # the inverse once, on the host
-        flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
+    def _merge_rounds(self, call, max_rounds, left_out, rounds, summed):
+        """`call(0)`, then `call(VK_MERGE_CONTINUE)` while a call posted requests in every round, dropped none and still left
+        blocks out. Of the later calls' counts those at `summed` add up and the one at `left_out` replaces; the rest are
+        the first call's."""
         dropped = int(self.read_counters()[T.VK_CTR_DROPPED])
-        counts = self._merge_posed_call(other, pose, flags, max_rounds, max_distance_weight, max_color_weight)
-        considered, candidates, fused, allocated, left_out, rounds, skipped, sampled = counts
-        while counts[5] == int(max_rounds) and counts[4] > 0 and int(self.read_counters()[T.VK_CTR_DROPPED]) == dropped:
-            counts = self._merge_posed_call(other, pose, flags | T.VK_MERGE_CONTINUE, max_rounds, max_distance_weight, max_color_weight)
-            fused, allocated, left_out = fused + counts[2], allocated + counts[3], counts[4]
-            rounds, sampled = rounds + counts[5], sampled + counts[7]
-        return considered, candidates, fused, allocated, left_out, rounds, skipped, sampled
+        counts = call(0)
+        total = list(counts)
+        while counts[rounds] == int(max_rounds) and counts[left_out] > 0 and int(self.read_counters()[T.VK_CTR_DROPPED]) == dropped:
+            counts = call(T.VK_MERGE_CONTINUE)
+            for i in summed:
+                total[i] += counts[i]
+            total[left_out] = counts[left_out]
+        return tuple(total)
 
     def merge(self, other, pose=None, max_distance_weight=16, max_color_weight=16, skip_unobserved=False, max_rounds=8):
         """vk_volume_merge (not upstream): fuse the volume `other` — same voxel and truncation length, on this device,
@@ -637,16 +667,15 @@ class Volume:
         sample of `other`. Returns (source blocks considered, candidate blocks, candidates fused, blocks allocated,
         candidates left out, rounds that posted, source blocks skipped as unobserved, voxels that took a distance
         sample); a candidate no sample reaches stays allocated and empty (release_blocks(unobserved=True) frees those)."""
-        if pose is not None:
-            return self._merge_posed(other, pose, max_distance_weight, max_color_weight, skip_unobserved, max_rounds)
         flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
-        dropped = int(self.read_counters()[T.VK_CTR_DROPPED])
-        counts = self._merge_call(other, flags, max_rounds, max_distance_weight, max_color_weight)
-        considered, fused, allocated, left_out, rounds, skipped = counts
-        while counts[4] == int(max_rounds) and counts[3] > 0 and int(self.read_counters()[T.VK_CTR_DROPPED]) == dropped:
-            counts = self._merge_call(other, flags | T.VK_MERGE_CONTINUE, max_rounds, max_distance_weight, max_color_weight)
-            fused, allocated, left_out, rounds = fused + counts[1], allocated + counts[2], counts[3], rounds + counts[4]
-        return considered, fused, allocated, left_out, rounds, skipped
+        if pose is None:
+            # (considered, fused, allocated, left out, rounds, skipped)
+            return self._merge_rounds(lambda go_on: self._merge_call(other, flags | go_on, max_rounds, max_distance_weight,
+                                                                     max_color_weight), max_rounds, 3, 4, (1, 2, 4))
+        pose = _as_pose(pose)
+        # (considered, candidates, fused, allocated, left out, rounds, skipped, sampled)
+        return self._merge_rounds(lambda go_on: self._merge_posed_call(other, pose, flags | go_on, max_rounds, max_distance_weight,
+                                                                       max_color_weight), max_rounds, 4, 5, (2, 3, 5, 7))
 
     _register_buffers = None    # device buffers of vk_volume_register, per source size
 
@@ -654,11 +683,12 @@ class Volume:
         """the device buffers of a registration against `other`, the start pose uploaded: (buffers, vk_register_params)"""
         import torch
         size = (other.main, other.excess)
-        if self._register_buffers is None or self._register_buffers["size"] != size:
+        workspace, counts = self._workspace("register", size, lib().vk_volume_register_workspace_bytes, 4)
+        if self._register_buffers is None or self._register_buffers["workspace"] is not workspace:
             self._register_buffers = {
-                "size": size, "workspace": _dev_bytes(lib().vk_volume_register_workspace_bytes(*size), self.device),
-                "pose": _dev_bytes(C.sizeof(T.Transform), self.device), "system": torch.zeros(48, dtype=torch.float32, device=self.device),
-                "state": torch.zeros(2, dtype=torch.int32, device=self.device), "counts": torch.zeros(4, dtype=torch.int32, device=self.device),
+                "size": size, "workspace": workspace, "counts": counts, "pose": _dev_bytes(C.sizeof(T.Transform), self.device),
+                "system": torch.zeros(48, dtype=torch.float32, device=self.device),
+                "state": torch.zeros(2, dtype=torch.int32, device=self.device),
                 "update": torch.zeros(6, dtype=torch.float32, device=self.device)}
         b = self._register_buffers
         check(lib().vk_transform_upload(_ptr(b["pose"]), _ref(pose), stream()), "vk_transform_upload")
@@ -681,7 +711,7 @@ class Volume:
         b, params = self._register_setup(other, pose, 1, band)
         check(lib().vk_volume_register_system(_ref(self.desc()), _ref(other.desc()), _ptr(b["pose"]), _ref(params), _ptr(b["system"]),
                                               _ptr(b["counts"]), _ptr(b["workspace"]), stream()), "vk_volume_register_system")
-        return b["system"].cpu().numpy(), tuple(int(c) for c in b["counts"].cpu().numpy())
+        return b["system"].cpu().numpy(), _ints(b["counts"])
 
     def _register_call(self, other, pose, iterations, band):
         """one vk_volume_register from `pose` (a T.Transform): (pose, (steps, code), counts, system[48], update[6])"""
@@ -691,8 +721,7 @@ class Volume:
                                        _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]), _ptr(b["workspace"]), stream()),
               "vk_volume_register")
         out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
-        return (out, tuple(int(c) for c in b["state"].cpu().numpy()), tuple(int(c) for c in b["counts"].cpu().numpy()),
-                b["system"].cpu().numpy(), b["update"].cpu().numpy())
+        return out, _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy(), b["update"].cpu().numpy()
 
     def register(self, other, pose=None, iterations=20, max_abs_distance=0.75):
         """vk_volume_register (not upstream): refine the rigid pose T_self_other between this volume and `other` — same
@@ -705,16 +734,9 @@ class Volume:
         Registration: `pose` (the result; merge(other, pose=result.pose) fuses through it), `steps`, `converged`,
         `overlap` (False: a step found no voxel to compare and the pose is the one it had then), `residuals` and `rms`
         (in truncation lengths) of the last evaluated step."""
-        if pose is None:
-            pose = T.Transform.identity()
-        elif not isinstance(pose, T.Transform):
-            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
-            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
-        out, state, counts, system, _ = self._register_call(other, pose, iterations, max_abs_distance)
+        out, state, counts, system, _ = self._register_call(other, _as_pose(pose, identity=True), iterations, max_abs_distance)
         return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
                             float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0)
-
-    _sample_pose = None         # the device vk_transform a host pose of sample() is uploaded to
 
     def _sample_call(self, points, pose=None, flags=0, samples=True, gradients=True, count=None, out=None):
         """one vk_volume_sample at `points` (a float32 device tensor of 3 * count floats or more): the raw output buffers
@@ -722,11 +744,7 @@ class Volume:
         buffer that holds a vk_transform, or None."""
         import torch
         count = points.numel() // 3 if count is None else int(count)
-        if isinstance(pose, T.Transform):
-            if self._sample_pose is None:
-                self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
-            check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
-            pose = self._sample_pose
+        pose = self._pose_on_device(pose)
         if out is None:
             out = (torch.empty((count, 20), dtype=torch.uint8, device=self.device) if samples else None,
                    torch.empty((count, 4), dtype=torch.float32, device=self.device) if gradients else None)
@@ -742,15 +760,9 @@ class Volume:
         trilinear sample of the stored voxels, as merge(pose=) takes it at a voxel's centre; `gradient`: and the gradient of
         the distance. The volume is only read; one launch, nothing is read back. Returns a Samples: where a weight is 0
         there is no sample of that field and the distance reads 1.0, "far from any surface"."""
-        import torch
-        if not (hasattr(points, "data_ptr") and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3):
-            raise VkError("sample: points is a float32 [N, 3] device tensor")
-        points = points.contiguous()
-        if pose is not None and not isinstance(pose, T.Transform) and not hasattr(pose, "data_ptr"):
-            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
-            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        points = _float_tensor(points, 3, "sample: points is a float32 [N, 3] device tensor")
         flags = (T.VK_SAMPLE_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_SAMPLE_DISTANCE_ONLY)
-        samples, gradients = self._sample_call(points, pose, flags, True, bool(gradient), points.shape[0])
+        samples, gradients = self._sample_call(points, _as_pose(pose, device=True), flags, True, bool(gradient), points.shape[0])
         return Samples(samples, gradients, bool(color), self.truncation_length)
 
     def _cast_call(self, rays, pose=None, flags=0, t_min=0.0, t_max=5.0, max_steps=500, samples=True, gradients=True, count=None,
@@ -760,11 +772,7 @@ class Volume:
         T.Transform (uploaded), a device buffer that holds a vk_transform, or None."""
         import torch
         count = rays.numel() // 6 if count is None else int(count)
-        if isinstance(pose, T.Transform):
-            if self._sample_pose is None:
-                self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
-            check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
-            pose = self._sample_pose
+        pose = self._pose_on_device(pose)
         if out is None:
             out = (torch.empty(count, dtype=torch.float32, device=self.device), torch.empty(count, dtype=torch.int32, device=self.device),
                    torch.empty((count, 20), dtype=torch.uint8, device=self.device) if samples else None,
@@ -782,45 +790,28 @@ class Volume:
         unit; `t_max` None: the far end of the volume's depth range), at most `max_steps` steps: a surface is reported
         where the ray crosses it from its observed free side. The volume is only read; one launch, nothing is read back.
         Returns a RayHits: status, t and the sample (`gradient`: and the gradient) at every hit."""
-        import torch
-        if not (hasattr(rays, "data_ptr") and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6):
-            raise VkError("cast_rays: rays is a float32 [N, 6] device tensor")
-        rays = rays.contiguous()
-        if pose is not None and not isinstance(pose, T.Transform) and not hasattr(pose, "data_ptr"):
-            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
-            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        rays = _float_tensor(rays, 6, "cast_rays: rays is a float32 [N, 6] device tensor")
+        pose = _as_pose(pose, device=True)
         if t_max is None:
             t_max = float(np.float32(self.depth_range[1]) / np.float32(self.voxel_length)) if voxel_units else self.depth_range[1]
         flags = (T.VK_CAST_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_CAST_DISTANCE_ONLY)
         t, status, samples, gradients = self._cast_call(rays, pose, flags, t_min, t_max, max_steps, True, bool(gradient), rays.shape[0])
         return RayHits(t, status, samples, gradients, bool(color), self.truncation_length)
 
-    _rays_workspace = None      # device bytes of vk_volume_integrate_rays, allocated by the first call
-    _rays_counts = None
-
     def _integrate_rays_call(self, rays, ranges, pose=None, flags=0, max_rounds=8, r_min=0.1, r_max=5.0, max_distance_weight=16.0,
                              count=None):
         """one vk_volume_integrate_rays of `rays` and `ranges` (float32 device tensors of 6 * count and count floats or more):
         the eight counts from one blocking read. `pose`: a T.Transform (uploaded), a device buffer that holds a vk_transform,
         or None."""
-        import torch
         self._no_requests_pending("integrate_rays")
         count = ranges.numel() if count is None else int(count)
-        if isinstance(pose, T.Transform):
-            if self._sample_pose is None:
-                self._sample_pose = _dev_bytes(C.sizeof(T.Transform), self.device)
-            check(lib().vk_transform_upload(_ptr(self._sample_pose), _ref(pose), stream()), "vk_transform_upload")
-            pose = self._sample_pose
-        if self._rays_workspace is None:
-            self._rays_workspace = _dev_bytes(lib().vk_volume_integrate_rays_workspace_bytes(self.main, self.excess), self.device)
-            self._rays_counts = torch.zeros(8, dtype=torch.int32, device=self.device)
+        pose = self._pose_on_device(pose)
+        workspace, counts = self._workspace("integrate_rays", (self.main, self.excess), lib().vk_volume_integrate_rays_workspace_bytes, 8)
         params = T.IntegrateRaysParams(int(flags), int(max_rounds), float(r_min), float(r_max), float(max_distance_weight), 0)
-        self._view_changed()
-        if self.light_prep is not None:
-            self.light_prep.valid = 0
+        self._table_changes()
         check(lib().vk_volume_integrate_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(pose), _ref(params),
-                                             _ptr(self._rays_counts), _ptr(self._rays_workspace), stream()), "vk_volume_integrate_rays")
-        return tuple(int(c) for c in self._rays_counts.cpu().numpy())
+                                             _ptr(counts), _ptr(workspace), stream()), "vk_volume_integrate_rays")
+        return _ints(counts)
 
     def integrate_rays(self, rays, ranges, pose=None, r_min=None, r_max=None, max_distance_weight=16, one_observation=False,
                        voxel_units=False, max_rounds=8):
@@ -839,15 +830,9 @@ class Volume:
         set_view rebuilds it) and what was prepared ahead for this volume is void. Returns (rays integrated, valid rays
         without a measurement, invalid rays, blocks allocated, rounds that posted a request, blocks updated, voxels updated,
         cell visits lost to a block that could not be allocated)."""
-        import torch
-        if not (hasattr(rays, "data_ptr") and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6):
-            raise VkError("integrate_rays: rays is a float32 [N, 6] device tensor")
-        if not (hasattr(ranges, "data_ptr") and ranges.dtype == torch.float32 and ranges.dim() == 1 and ranges.shape[0] == rays.shape[0]):
-            raise VkError("integrate_rays: ranges is a float32 [N] device tensor, one range per ray")
-        rays, ranges = rays.contiguous(), ranges.contiguous()
-        if pose is not None and not isinstance(pose, T.Transform) and not hasattr(pose, "data_ptr"):
-            matrix = np.asarray(pose, dtype=np.float64).reshape(4, 4)
-            pose = T.Transform.from_matrices(matrix, np.linalg.inv(matrix))
+        rays = _float_tensor(rays, 6, "integrate_rays: rays is a float32 [N, 6] device tensor")
+        ranges = _float_tensor(ranges, None, "integrate_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        pose = _as_pose(pose, device=True)
         scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
         r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
         r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max

@@ -349,6 +349,16 @@ class Volume
     mutable int32_t* normals_late_;     // pinned: vk_view_bounds.late_host of the attached tracer's record
 
   private:
+    // what the volume operations above share on the caller's side
+    void AssertNoFrameAnnounced() const;                               // between SetView calls only
+    const vk_transform* PoseOnDevice(const Transform* pose) const;     // uploaded into sample_pose_; null stays null
+    void VoidMadeAhead() const;                 // the raycast bounds and the light preparation made for the old table
+    void EmptyVisibleList() const;              // VK_CTR_VISIBLE is 0 until the next SetView
+    // both Merge overloads: `call(dst, src, counts_dev, workspace)` is the library call with `merge` among its parameters,
+    // made again with VK_MERGE_CONTINUE until every block had its turn; `total` takes the `count` (6 or 8) summed counts
+    template <typename Call>
+    void MergeRounds(const Volume& other, vk_merge_params& merge, Buffer<unsigned char>& workspace, size_t bytes,
+        Buffer<int>& counts_dev, int count, int32_t* total, Call call);
     void Initialize();
     Volume(const Volume&);              // not copyable
     Volume& operator=(const Volume&);

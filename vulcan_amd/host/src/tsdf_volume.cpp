@@ -322,9 +322,36 @@ int Volume::GetAllocatedBlockCount() const
   return taken < max_block_count_ ? taken : max_block_count_;
 }
 
-ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
+void Volume::AssertNoFrameAnnounced() const
 {
   VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+}
+
+const vk_transform* Volume::PoseOnDevice(const Transform* pose) const
+{
+  if (!pose) return nullptr;
+  if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
+  const vk_transform seed = pose->ToVk();
+  vk_transform* pose_dev = reinterpret_cast<vk_transform*>(sample_pose_.GetData());
+  VK_ASSERT(vk_transform_upload(pose_dev, &seed, Device::GetStream()));
+  return pose_dev;
+}
+
+void Volume::VoidMadeAhead() const
+{
+  view_bounds_.valid = 0;
+  light_prep_.valid = 0;
+}
+
+void Volume::EmptyVisibleList() const
+{
+  visible_blocks_.Resize(0);
+  visible_count_stale_ = false;
+}
+
+ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
+{
+  AssertNoFrameAnnounced();
   vk_release_rule r;
   std::memset(&r, 0, sizeof(r));
   r.flags = (rule.unobserved ? VK_RELEASE_UNOBSERVED : 0) | (rule.no_surface ? VK_RELEASE_NO_SURFACE : 0) |
@@ -340,13 +367,10 @@ ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
     release_workspace_.Resize(vk_volume_release_workspace_bytes(main_block_count_, excess_block_count_));
     release_counts_.Resize(4);
   }
-  // what was made ahead for the old table and visible list is void
-  view_bounds_.valid = 0;
-  light_prep_.valid = 0;
+  VoidMadeAhead();
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_release_blocks(&v, &r, release_counts_.GetData(), release_workspace_.GetData(), Device::GetStream()));
-  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
-  visible_count_stale_ = false;
+  EmptyVisibleList();
   int32_t counts[4];
   release_counts_.CopyToHost(counts);
   ReleaseCounts out;
@@ -357,105 +381,93 @@ ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
   return out;
 }
 
-MergeCounts Volume::Merge(const Volume& other, const MergeOptions& options)
+static vk_merge_params ToVkMergeParams(const MergeOptions& options)
 {
-  const char* announced = "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first";
-  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, announced);
-  VULCAN_ASSERT_MSG(other.requests_ahead_.valid != 1, announced);
-  VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
   vk_merge_params p;
   p.flags = options.skip_unobserved ? VK_MERGE_SKIP_UNOBSERVED : 0;
   p.max_rounds = options.max_rounds;
   p.max_distance_weight = options.max_distance_weight;
   p.max_color_weight = options.max_color_weight;
-  const size_t bytes = vk_volume_merge_workspace_bytes(other.main_block_count_, other.excess_block_count_);
-  if (merge_workspace_.GetSize() != bytes) merge_workspace_.Resize(bytes);
-  if (merge_counts_.GetSize() == 0) merge_counts_.Resize(6);
-  // what was made ahead for the old table and visible list is void
-  view_bounds_.valid = 0;
-  light_prep_.valid = 0;
+  return p;
+}
+
+template <typename Call>
+void Volume::MergeRounds(const Volume& other, vk_merge_params& merge, Buffer<unsigned char>& workspace, size_t bytes,
+    Buffer<int>& counts_dev, int count, int32_t* total, Call call)
+{
+  AssertNoFrameAnnounced();
+  other.AssertNoFrameAnnounced();
+  VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
+  if (workspace.GetSize() != bytes) workspace.Resize(bytes);
+  if (counts_dev.GetSize() == 0) counts_dev.Resize(count);
+  VoidMadeAhead();
   const vk_volume dst = ToVk(), src = other.ToVk();
   int32_t counters[VK_CTR_PUBLIC];
   GetCounters(counters);
   const int32_t dropped = counters[VK_CTR_DROPPED];
-  MergeCounts out;
+  // the counts: considered, [candidates,] fused, allocated, left out, rounds that posted, skipped[, sampled]
+  const int k = count == 8 ? 1 : 0, fused = 1 + k, allocated = 2 + k, left_out = 3 + k, rounds = 4 + k;
   for (bool first = true;; first = false)
   {
-    VK_ASSERT(vk_volume_merge(&dst, &src, &p, merge_counts_.GetData(), merge_workspace_.GetData(), Device::GetStream()));
-    int32_t counts[6];
-    merge_counts_.CopyToHost(counts);
+    VK_ASSERT(call(&dst, &src, counts_dev.GetData(), workspace.GetData()));
+    int32_t counts[8];
+    counts_dev.CopyToHost(counts);
     if (first)
+      std::memcpy(total, counts, size_t(count) * sizeof(int32_t));     // considered, candidates and skipped are the first call's
+    else
     {
-      out.considered = counts[0];
-      out.skipped = counts[5];
-      out.fused = out.allocated = out.rounds = 0;
+      total[fused] += counts[fused];
+      total[allocated] += counts[allocated];
+      total[left_out] = counts[left_out];
+      total[rounds] += counts[rounds];
+      if (count == 8) total[7] += counts[7];
     }
-    out.fused += counts[1];
-    out.allocated += counts[2];
-    out.left_out = counts[3];
-    out.rounds += counts[4];
-    // every block once: while a call posted in all its rounds, dropped nothing and still left blocks out, the next
-    // call goes on with those
+    // every block (candidate) once: while a call posted in all its rounds, dropped nothing and still left some out, the
+    // next call goes on with those
     GetCounters(counters);
-    if (!(counts[4] == p.max_rounds && counts[3] > 0 && counters[VK_CTR_DROPPED] == dropped)) break;
-    p.flags |= VK_MERGE_CONTINUE;
+    if (!(counts[rounds] == merge.max_rounds && counts[left_out] > 0 && counters[VK_CTR_DROPPED] == dropped)) break;
+    merge.flags |= VK_MERGE_CONTINUE;
   }
   NotePoolExhaustion(counters[VK_CTR_DROPPED]);
-  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
-  visible_count_stale_ = false;
+  EmptyVisibleList();
+}
+
+MergeCounts Volume::Merge(const Volume& other, const MergeOptions& options)
+{
+  vk_merge_params p = ToVkMergeParams(options);
+  int32_t counts[6];
+  MergeRounds(other, p, merge_workspace_, vk_volume_merge_workspace_bytes(other.main_block_count_, other.excess_block_count_),
+      merge_counts_, 6, counts, [&p](const vk_volume* dst, const vk_volume* src, int32_t* counts_dev, void* workspace)
+      { return vk_volume_merge(dst, src, &p, counts_dev, workspace, Device::GetStream()); });
+  MergeCounts out;
+  out.considered = counts[0];
+  out.fused = counts[1];
+  out.allocated = counts[2];
+  out.left_out = counts[3];
+  out.rounds = counts[4];
+  out.skipped = counts[5];
   return out;
 }
 
 MergePoseCounts Volume::Merge(const Volume& other, const Transform& Tdst_src, const MergeOptions& options)
 {
-  const char* announced = "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first";
-  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, announced);
-  VULCAN_ASSERT_MSG(other.requests_ahead_.valid != 1, announced);
-  VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
   vk_merge_pose_params p;
-  p.merge.flags = options.skip_unobserved ? VK_MERGE_SKIP_UNOBSERVED : 0;
-  p.merge.max_rounds = options.max_rounds;
-  p.merge.max_distance_weight = options.max_distance_weight;
-  p.merge.max_color_weight = options.max_color_weight;
+  p.merge = ToVkMergeParams(options);
   p.pose = Tdst_src.ToVk();                       // the matrix and its inverse, from the one Transform
-  const size_t bytes = vk_volume_merge_posed_workspace_bytes(other.main_block_count_, other.excess_block_count_,
-      main_block_count_, excess_block_count_);
-  if (merge_pose_workspace_.GetSize() != bytes) merge_pose_workspace_.Resize(bytes);
-  if (merge_pose_counts_.GetSize() == 0) merge_pose_counts_.Resize(8);
-  // what was made ahead for the old table and visible list is void
-  view_bounds_.valid = 0;
-  light_prep_.valid = 0;
-  const vk_volume dst = ToVk(), src = other.ToVk();
-  int32_t counters[VK_CTR_PUBLIC];
-  GetCounters(counters);
-  const int32_t dropped = counters[VK_CTR_DROPPED];
+  int32_t counts[8];
+  MergeRounds(other, p.merge, merge_pose_workspace_, vk_volume_merge_posed_workspace_bytes(other.main_block_count_,
+      other.excess_block_count_, main_block_count_, excess_block_count_), merge_pose_counts_, 8, counts,
+      [&p](const vk_volume* dst, const vk_volume* src, int32_t* counts_dev, void* workspace)
+      { return vk_volume_merge_posed(dst, src, &p, counts_dev, workspace, Device::GetStream()); });
   MergePoseCounts out;
-  for (bool first = true;; first = false)
-  {
-    VK_ASSERT(vk_volume_merge_posed(&dst, &src, &p, merge_pose_counts_.GetData(), merge_pose_workspace_.GetData(), Device::GetStream()));
-    int32_t counts[8];
-    merge_pose_counts_.CopyToHost(counts);
-    if (first)
-    {
-      out.considered = counts[0];
-      out.candidates = counts[1];
-      out.skipped = counts[6];
-      out.fused = out.allocated = out.rounds = out.sampled = 0;
-    }
-    out.fused += counts[2];
-    out.allocated += counts[3];
-    out.left_out = counts[4];
-    out.rounds += counts[5];
-    out.sampled += counts[7];
-    // every candidate once: while a call posted in all its rounds, dropped nothing and still left candidates out, the
-    // next call goes on with those
-    GetCounters(counters);
-    if (!(counts[5] == p.merge.max_rounds && counts[4] > 0 && counters[VK_CTR_DROPPED] == dropped)) break;
-    p.merge.flags |= VK_MERGE_CONTINUE;
-  }
-  NotePoolExhaustion(counters[VK_CTR_DROPPED]);
-  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
-  visible_count_stale_ = false;
+  out.considered = counts[0];
+  out.candidates = counts[1];
+  out.fused = counts[2];
+  out.allocated = counts[3];
+  out.left_out = counts[4];
+  out.rounds = counts[5];
+  out.skipped = counts[6];
+  out.sampled = counts[7];
   return out;
 }
 
@@ -502,14 +514,7 @@ void Volume::Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, V
   vk_sample_params p;
   p.flags = (options.voxel_units ? VK_SAMPLE_VOXEL_UNITS : 0) | (options.distance_only ? VK_SAMPLE_DISTANCE_ONLY : 0);
   p.pad = 0;
-  const vk_transform* pose_dev = nullptr;
-  if (pose)
-  {
-    if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
-    const vk_transform seed = pose->ToVk();
-    VK_ASSERT(vk_transform_upload(reinterpret_cast<vk_transform*>(sample_pose_.GetData()), &seed, Device::GetStream()));
-    pose_dev = reinterpret_cast<const vk_transform*>(sample_pose_.GetData());
-  }
+  const vk_transform* pose_dev = PoseOnDevice(pose);
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_sample(&v, reinterpret_cast<const float*>(points_dev), count, pose_dev, &p, reinterpret_cast<vk_voxel*>(samples_dev),
       reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
@@ -524,14 +529,7 @@ void Volume::CastRays(const Ray* rays_dev, int count, float* t_dev, int* status_
   p.max_steps = options.max_steps;
   p.t_min = options.t_min;
   p.t_max = options.t_max;
-  const vk_transform* pose_dev = nullptr;
-  if (pose)
-  {
-    if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
-    const vk_transform seed = pose->ToVk();
-    VK_ASSERT(vk_transform_upload(reinterpret_cast<vk_transform*>(sample_pose_.GetData()), &seed, Device::GetStream()));
-    pose_dev = reinterpret_cast<const vk_transform*>(sample_pose_.GetData());
-  }
+  const vk_transform* pose_dev = PoseOnDevice(pose);
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_cast_rays(&v, reinterpret_cast<const float*>(rays_dev), count, pose_dev, &p, t_dev, status_dev,
       reinterpret_cast<vk_voxel*>(samples_dev), reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
@@ -541,7 +539,7 @@ IntegrateRaysCounts Volume::IntegrateRays(const Ray* rays_dev, const float* rang
     const IntegrateRaysOptions& options)
 {
   static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
-  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+  AssertNoFrameAnnounced();
   IntegrateRaysCounts out = {};
   vk_integrate_rays_params p;
   p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
@@ -553,21 +551,12 @@ IntegrateRaysCounts Volume::IntegrateRays(const Ray* rays_dev, const float* rang
   const size_t bytes = vk_volume_integrate_rays_workspace_bytes(main_block_count_, excess_block_count_);
   if (rays_workspace_.GetSize() != bytes) rays_workspace_.Resize(bytes);
   if (rays_counts_.GetSize() == 0) rays_counts_.Resize(8);
-  const vk_transform* pose_dev = nullptr;
-  if (pose && count > 0)
-  {
-    if (sample_pose_.GetSize() == 0) sample_pose_.Resize(32);
-    const vk_transform seed = pose->ToVk();
-    VK_ASSERT(vk_transform_upload(reinterpret_cast<vk_transform*>(sample_pose_.GetData()), &seed, Device::GetStream()));
-    pose_dev = reinterpret_cast<const vk_transform*>(sample_pose_.GetData());
-  }
+  const vk_transform* pose_dev = PoseOnDevice(count > 0 ? pose : nullptr);      // no rays: no upload
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_integrate_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose_dev, &p, rays_counts_.GetData(),
       rays_workspace_.GetData(), Device::GetStream()));
   if (count == 0) return out;                      // nothing was launched and the counts were not written
-  // what was made ahead for the old table and visible list is void
-  view_bounds_.valid = 0;
-  light_prep_.valid = 0;
+  VoidMadeAhead();
   int32_t counts[8];
   rays_counts_.CopyToHost(counts);
   out.integrated = counts[0];
@@ -581,14 +570,13 @@ IntegrateRaysCounts Volume::IntegrateRays(const Ray* rays_dev, const float* rang
   int32_t counters[VK_CTR_PUBLIC];
   GetCounters(counters);
   NotePoolExhaustion(counters[VK_CTR_DROPPED]);
-  visible_blocks_.Resize(0);      // VK_CTR_VISIBLE is 0 until the next SetView
-  visible_count_stale_ = false;
+  EmptyVisibleList();
   return out;
 }
 
 void Volume::ResetBlockVisibility()
 {
-  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+  AssertNoFrameAnnounced();
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_reset_block_visibility(&v, Device::GetStream()));
 }
@@ -607,7 +595,7 @@ void Volume::UpdateBlockVisibility(const Frame& frame)
 
 void Volume::CreateAllocationRequests(const Frame& frame)
 {
-  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+  AssertNoFrameAnnounced();
   const vk_volume v = ToVk();
   const vk_projection k = frame.depth_projection.ToVk();
   const vk_transform Twd = frame.depth_to_world_transform.ToVk();
@@ -617,7 +605,7 @@ void Volume::CreateAllocationRequests(const Frame& frame)
 
 void Volume::HandleAllocationRequests()
 {
-  VULCAN_ASSERT_MSG(requests_ahead_.valid != 1, "a frame announced by Tracer::Trace(keyframe, next_frame) has its requests in the volume: SetView(that frame) or CancelRequestsAhead() first");
+  AssertNoFrameAnnounced();
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_handle_allocation_requests(&v, Device::GetStream()));
 }
