@@ -1635,6 +1635,65 @@ VK_API int vk_volume_integrate_rays(const vk_volume* v, const float* rays /* dev
  * (NULL, 0) cancels. `count` must be 6. Not a stream operation: nothing is enqueued by this call. */
 VK_API int vk_volume_integrate_rays_time_next(void* const* events, int32_t count);
 
+/* -------------------------------------------------------------- carve rays -- */
+
+typedef struct vk_carve_rays_params {
+  int32_t flags;               /* VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION; any other bit is VK_ERR_ARGUMENT */
+  int32_t max_blocks;          /* 1 .. 4096: blocks a ray's carve may cross */
+  float   r_min, r_max;        /* a ray has a measurement iff r_min <= range <= r_max (vk_volume_integrate_rays' rule) */
+  float   t_from;              /* the carve starts here along the ray, in the origin's unit; finite, >= 0 */
+  float   max_distance_weight; /* 1 .. 32767 */
+} vk_carve_rays_params;        /* 24 bytes */
+
+/* Carve free space along `count` range rays: every voxel of an existing block whose cell a ray crosses between t_from and the
+ * start of the band around its measurement takes one observation of "free", the distance 1 that the reference integrator
+ * writes in front of a surface (min(1, d / truncation), ref: src/depth_integrator.cu:54-74). vk_volume_integrate_rays fuses
+ * the band and nothing in front of it, so a surface that was fused once and is gone stays until a ray carves it. No upstream
+ * counterpart. The definition is this comment; tests/carve_rays_reference.py states it on the CPU and the device is held to
+ * it bit for bit. All arithmetic is fp32, one rounding per operation, no contraction, IEEE division and a correctly rounded
+ * square root.
+ * PRECONDITIONS: vk_volume_integrate_rays' — between SetView calls, no frame announced (the class layers enforce it).
+ * ACCESS: rays, ranges, the pose, the hash table are only read; of the volume only voxels are written. THE CALL ALLOCATES
+ * NOTHING: the hash table, the free list, the visibility and allocation arrays, the visible list and every VK_CTR_* keep their
+ * bytes, and the lists of the last SetView stay valid. Everything is enqueued on `stream`, nothing is read back, no workgroup
+ * waits on another; the block walk is bounded by max_blocks, a cell walk by G <= 48 and a chain walk by the table size: it
+ * cannot hang a device. `workspace`: vk_volume_carve_rays_workspace_bytes(main, excess) bytes, 16-byte aligned, need not be
+ * initialised.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): v, p, counts_dev or workspace null, a volume that vk_volume_merge would
+ * refuse, a flag other than the two, max_blocks outside 1 .. 4096, a cap outside 1 .. 32767, r_min or r_max not finite or not
+ * 0 <= r_min < r_max, t_from not finite or < 0, count < 0 or count > 1 << 22, rays or ranges null with count > 0, a workspace
+ * not 16-byte aligned, truncation_length / voxel_length > 64. count == 0 returns 0, launches nothing and leaves counts_dev alone.
+ * (the ray) vk_volume_integrate_rays' word for word: units, pose, n, the INVALID rule, r, the measurement test.
+ * (the carve interval) tr = truncation_length / L, t0 = t_from / L (t0 = t_from with VK_RAYS_VOXEL_UNITS), te = r - tr. A ray
+ * CARVES iff it is valid, has a measurement and t0 < te (false for a NaN; r is finite for a measured ray unless range / L
+ * overflows, and te = +infinity then carves up to max_blocks blocks like any long ray).
+ * (the block walk) vk_volume_integrate_rays' traversal with a cell edge of 8: p_a = o_a + t0 * n_a, B_a = c_a >> 3 with
+ * c_a = (int)floorf(p_a), saturating, clamped to +-2^30. Per axis: n_a > 0: bstep_a = 1, bmax_a = t0 + ((float)(8 (B_a + 1))
+ * - p_a) / n_a, bdelta_a = 8.0f / n_a; n_a < 0: bstep_a = -1, bmax_a = t0 + ((float)(8 B_a) - p_a) / n_a, bdelta_a = 8.0f /
+ * fabsf(n_a); n_a == 0: bstep_a = 0, both +infinity. t_in = t0. At most max_blocks times: least = the smallest bmax, x before y
+ * before z on a tie (bmax_y < bmax_x, then bmax_z < the smaller: a NaN is never smaller); t_out = fminf(least, te); visit
+ * block B over [t_in, t_out]; !(least < te): end; B_a += bstep_a, bmax_a = bmax_a + bdelta_a, t_in = least. A ray whose turns
+ * run out first is CUT SHORT: what it did not reach is not carved.
+ * (visiting a block) a block with a coordinate outside the int16 range, or absent from the table (the chain walk), is passed
+ * over. A present block runs vk_volume_integrate_rays' cell walk with ta = t_in and tb = t_out: the same p, c, tmax, tdelta,
+ * tie rule and guard G = 3 * (min((int)ceilf(tb - ta), 1024) + 2), the conversion saturating and a NaN giving 0 (tb - ta is at
+ * most a block's diagonal, under 14, so G <= 48 for finite ends; a non-finite difference meets the clamp at 1024, never int
+ * arithmetic). A visited cell c takes a carve iff c >> 3 == B on all three axes and the walk leaves it before the band begins:
+ * least' <= te, least' the smallest tmax right after the visit (the walk's own next test is least' <= tb). The cell that
+ * straddles te is the band walk's, which starts inside it.
+ * (accumulation) a carve adds 1 to the voxel's 32-bit count N (N <= count <= 2^22). Every carve observes min(1, raw / tr) for
+ * raw > tr, exactly 1: there is no sum and nothing to quantise. No float atomic touches a voxel or an accumulator.
+ * (the fold) for every voxel with N > 0: ws = VK_RAYS_ONE_OBSERVATION ? 1.0f : (float)N, wd = (float)distance_weight,
+ * distance = wd == 0 ? 1.0f : (wd * distance + ws) / (wd + ws), distance_weight = (int16)fminf(max_distance_weight, wd + ws).
+ * The colour fields and the colour weight keep their bytes; a voxel with N == 0 keeps all its bytes.
+ * counts_dev int32[8]: rays that carved; measured rays with nothing to carve (!(t0 < te)); valid rays without a measurement;
+ * invalid rays; rays cut short by max_blocks; blocks that took an update; voxels updated; carves (the sum of all N, wrapping
+ * at 2^32). */
+VK_API size_t vk_volume_carve_rays_workspace_bytes(int32_t main, int32_t excess);
+VK_API int vk_volume_carve_rays(const vk_volume* v, const float* rays /* device [6*count]: origin, direction */,
+    const float* ranges /* device [count] */, int32_t count, const vk_transform* pose_dev /* optional: T_volume_rays */,
+    const vk_carve_rays_params* p, int32_t* counts_dev /* [8] */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

@@ -132,6 +132,8 @@ _SIGNATURES = {
     "vk_volume_integrate_rays_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
     "vk_volume_integrate_rays": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
     "vk_volume_integrate_rays_time_next": ([_P, C.c_int32], _I),
+    "vk_volume_carve_rays_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
+    "vk_volume_carve_rays": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -840,6 +842,43 @@ class Volume:
         if rays.shape[0] == 0:
             return (0,) * 8
         return self._integrate_rays_call(rays, ranges, pose, flags, max_rounds, r_min, r_max, max_distance_weight, rays.shape[0])
+
+    def _carve_rays_call(self, rays, ranges, pose=None, flags=0, max_blocks=1024, r_min=0.1, r_max=5.0, t_from=0.0,
+                         max_distance_weight=16.0, count=None):
+        """one vk_volume_carve_rays of `rays` and `ranges` (float32 device tensors of 6 * count and count floats or more): the
+        eight counts from one blocking read. `pose`: a T.Transform (uploaded), a device buffer that holds a vk_transform, or
+        None. The table and the visible list are left alone, so nothing made ahead is void."""
+        self._no_requests_pending("carve_rays")
+        count = ranges.numel() if count is None else int(count)
+        pose = self._pose_on_device(pose)
+        workspace, counts = self._workspace("carve_rays", (self.main, self.excess), lib().vk_volume_carve_rays_workspace_bytes, 8)
+        params = T.CarveRaysParams(int(flags), int(max_blocks), float(r_min), float(r_max), float(t_from), float(max_distance_weight))
+        check(lib().vk_volume_carve_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(pose), _ref(params),
+                                         _ptr(counts), _ptr(workspace), stream()), "vk_volume_carve_rays")
+        return _ints(counts)
+
+    def carve_rays(self, rays, ranges, pose=None, t_from=0.0, r_min=None, r_max=None, max_distance_weight=16, one_observation=False,
+                   voxel_units=False, max_blocks=1024):
+        """vk_volume_carve_rays (not upstream): carve the free space in front of range measurements — what is no longer
+        there. `rays`, `ranges`, `pose`, `r_min`, `r_max` and `voxel_units` are integrate_rays'. Every voxel of an existing
+        block whose cell a measured ray crosses between `t_from` (along the ray, in the origins' unit) and the start of the
+        band that integrate_rays fuses, one truncation length in front of the measurement, takes an observation of the
+        distance 1, "free": weighted with the number of rays through it (`one_observation`: with 1), the weight capped at
+        `max_distance_weight`. A ray crosses at most `max_blocks` blocks; what it does not reach is not carved. Nothing is
+        allocated: absent blocks are passed over, and the table, the free list, the visible list and the counters keep their
+        bytes. Colours are left alone. The result does not depend on the order of the rays. Between SetView calls only:
+        raises while a frame is announced. Returns (rays that carved, measured rays with nothing to carve, valid rays
+        without a measurement, invalid rays, rays cut short by `max_blocks`, blocks updated, voxels updated, carves)."""
+        rays = _float_tensor(rays, 6, "carve_rays: rays is a float32 [N, 6] device tensor")
+        ranges = _float_tensor(ranges, None, "carve_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        pose = _as_pose(pose, device=True)
+        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
+        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
+        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
+        flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
+        if rays.shape[0] == 0:
+            return (0,) * 8
+        return self._carve_rays_call(rays, ranges, pose, flags, max_blocks, r_min, r_max, t_from, max_distance_weight, rays.shape[0])
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

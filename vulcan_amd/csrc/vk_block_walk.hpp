@@ -1,5 +1,6 @@
 // vk_block_walk.hpp — what the operations on a voxel-hashed volume share (vk_merge.hip, vk_merge_pose.hip, vk_register.hip,
-// vk_sample.hip, vk_cast.hip, vk_integrate_rays.hip; the allocation rounds are in vk_alloc_rounds.hpp beside it):
+// vk_sample.hip, vk_cast.hip, vk_integrate_rays.hip, vk_carve_rays.hip; the allocation rounds are in vk_alloc_rounds.hpp beside
+// it, the walk of a range ray's cells in vk_range_rays.hpp):
 //   wave_add, wave_min                      sums and minima over a wave
 //   voxel_rows, carry_rows, apply           the pose as three rows in voxel units, and a point through them
 //   find_block, mark_chain                  the chain walk that finds a block; the one that lists a bucket's blocks

@@ -22,6 +22,7 @@
 //   finish    the eight counts, VK_CTR_VISIBLE and VK_CTR_BANDED
 // Every loop is bounded: the walk by its guard G, a chain walk by the table size. No workgroup waits on another.
 #include "vk_alloc_rounds.hpp"
+#include "vk_range_rays.hpp"
 
 using namespace vk;
 
@@ -33,7 +34,6 @@ constexpr int kMaxCount = 1 << 22;
 constexpr int kPackedCount = 1 << 21;       // below this many rays a voxel's N and biased sum share one 64-bit word
 constexpr int kCountShift = 43;
 constexpr int kBias = 1 << 20;
-constexpr int kMaxGuardCells = 1024;         // ceilf(tb - ta) saturates here; tb - ta <= 4 tr <= 256, so it never does
 
 enum : uint8_t { kHeldBefore = 1, kVisited = 2 };
 // the words that carry the sums, behind the ones that steer the rounds
@@ -56,90 +56,18 @@ struct RaysParams
   int32_t* counts;              // [8] output
 };
 
-enum { kIntegrated = 0, kNoMeasurement = 1, kInvalid = 2 };
-
-// vk_volume_cast_rays' ray (load_ray), and its range
-struct RangeRay : Ray
-{
-  float r;                      // the range in voxels
-  int kind;
-};
-
+// ray i as the call carries it (load_range_ray, vk_range_rays.hpp)
 __device__ __forceinline__ RangeRay load_range_ray(const RaysParams& P, size_t i)
 {
-  RangeRay ray;
-  static_cast<Ray&>(ray) = load_ray(P.rays, i, P.pose, P.v.voxel_length, P.voxel_units != 0);
-  const float range = P.ranges[i];
-  ray.r = P.voxel_units ? range : range / P.v.voxel_length;
-  const bool measured = P.r_min <= range && range <= P.r_max;         // false for a NaN
-  ray.kind = ray.valid ? (measured ? kIntegrated : kNoMeasurement) : kInvalid;
-  return ray;
+  return vk::load_range_ray(P.rays, P.ranges, i, P.pose, P.v.voxel_length, P.voxel_units != 0, P.r_min, P.r_max);
 }
 
-// the first crossing along one axis and the distance between crossings: +infinity for an axis the ray does not move along
-__device__ __forceinline__ void axis_setup(float ta, float p, float n, int c, int& step, float& tmax, float& tdelta)
-{
-  step = n > 0.0f ? 1 : (n < 0.0f ? -1 : 0);
-  tmax = tdelta = INFINITY;
-  if (n > 0.0f)
-  {
-    tmax = ta + ((float)(c + 1) - p) / n;
-    tdelta = 1.0f / n;
-  }
-  else if (n < 0.0f)
-  {
-    tmax = ta + ((float)c - p) / n;
-    tdelta = 1.0f / fabsf(n);
-  }
-}
-
-// The exact traversal of the cells the ray crosses between ta = max(r - tr, 0) and tb = r + tr: visit(cx, cy, cz) per cell,
-// at most G of them.
+// the cells of the ray's band, between ta = max(r - tr, 0) and tb = r + tr: visit(cx, cy, cz) per cell
 template <class Visit>
 __device__ __forceinline__ void walk(const RangeRay& ray, float tr, Visit&& visit)
 {
-  const float ta = fmaxf(ray.r - tr, 0.0f), tb = ray.r + tr;
-  const float px = ray.o.x + ta * ray.n.x, py = ray.o.y + ta * ray.n.y, pz = ray.o.z + ta * ray.n.z;
-  int cx = cell_of(px), cy = cell_of(py), cz = cell_of(pz);
-  int sx, sy, sz;
-  float mx, my, mz, dx, dy, dz;
-  axis_setup(ta, px, ray.n.x, cx, sx, mx, dx);
-  axis_setup(ta, py, ray.n.y, cy, sy, my, dy);
-  axis_setup(ta, pz, ray.n.z, cz, sz, mz, dz);
-  const int guard = 3 * (vclampi(f2i(ceilf(tb - ta)), 0, kMaxGuardCells) + 2);
-  for (int turn = 0; turn < guard; ++turn)
-  {
-    visit(cx, cy, cz);
-    // the axis of the smallest tmax, x before y before z on a tie (a NaN is never the smaller)
-    int axis = 0;
-    float least = mx;
-    if (my < least) { axis = 1;  least = my; }
-    if (mz < least) { axis = 2;  least = mz; }
-    if (!(least <= tb)) break;
-    if (axis == 0) { cx += sx;  mx = mx + dx; }
-    else if (axis == 1) { cy += sy;  my = my + dy; }
-    else { cz += sz;  mz = mz + dz; }
-  }
+  vk::walk(ray, fmaxf(ray.r - tr, 0.0f), ray.r + tr, [&](int cx, int cy, int cz, float) { visit(cx, cy, cz); });
 }
-
-// the block of the last visited cell and its slot (-1: absent, or beyond the int16 range), kept across the cells of a walk
-struct Held
-{
-  bool any = false, inside = false;
-  int x = 0, y = 0, z = 0, slot = -1;
-  Entry main_entry;
-
-  // true when (bx, by, bz) is another block than the last: the chain was walked
-  __device__ __forceinline__ bool move_to(const RaysParams& P, int bx, int by, int bz)
-  {
-    if (any && bx == x && by == y && bz == z) return false;
-    any = true;  x = bx;  y = by;  z = bz;
-    inside = in_int16(bx, by, bz);
-    slot = -1;
-    if (inside) find_block(P.v, P.total, bx, by, bz, slot, main_entry);
-    return true;
-  }
-};
 
 // (the control words and the marks are zero: one memset in front of this launch)
 __global__ __launch_bounds__(kThreads) void rays_snapshot_kernel(RaysParams P)
@@ -167,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void rays_request_kernel(RaysParams P)
       const float tr = P.v.truncation_length / P.v.voxel_length;
       Held held;
       walk(ray, tr, [&](int cx, int cy, int cz) {
-        if (!held.move_to(P, cx >> 3, cy >> 3, cz >> 3) || !held.inside || held.slot >= 0) return;
+        if (!held.move_to(P.v, P.total, cx >> 3, cy >> 3, cz >> 3) || !held.inside || held.slot >= 0) return;
         request_block(P.v, held.x, held.y, held.z, held.main_entry);
         posted = 1;
       });
@@ -187,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void rays_mark_kernel(RaysParams P)
   const float tr = P.v.truncation_length / P.v.voxel_length;
   Held held;
   walk(ray, tr, [&](int cx, int cy, int cz) {
-    if (!held.move_to(P, cx >> 3, cy >> 3, cz >> 3) || held.slot < 0) return;
+    if (!held.move_to(P.v, P.total, cx >> 3, cy >> 3, cz >> 3) || held.slot < 0) return;
     const uint8_t mark = P.marks[held.slot];
     if (!(mark & kVisited)) P.marks[held.slot] = mark | kVisited;
   });
@@ -227,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void rays_add_kernel(RaysParams P)
       const float tr = P.v.truncation_length / P.v.voxel_length;
       Held held;
       walk(ray, tr, [&](int cx, int cy, int cz) {
-        held.move_to(P, cx >> 3, cy >> 3, cz >> 3);
+        held.move_to(P.v, P.total, cx >> 3, cy >> 3, cz >> 3);
         if (!held.inside) return;
         if (held.slot < 0) { ++lost;  return; }
         const float ex = (float)cx + 0.5f, ey = (float)cy + 0.5f, ez = (float)cz + 0.5f;

@@ -148,6 +148,31 @@ struct IntegrateRaysCounts
   int lost;             // cell visits lost to a block that found no room
 };
 
+// Not upstream: how Volume::CarveRays reads its rays and ranges and what it carves (vk_carve_rays_params)
+struct CarveRaysOptions
+{
+  bool voxel_units = false;           // the origins, the ranges, r_min, r_max and t_from are in voxels, not metres
+  bool one_observation = false;       // a voxel's carves count as one observation, not as one per ray through it
+  float r_min = 0.1f;                 // IntegrateRays' rule: a ray whose range lies outside [r_min, r_max] carries no
+  float r_max = 5.0f;                 //   measurement and carves nothing
+  float t_from = 0.0f;                // the carve starts here along the ray
+  float max_distance_weight = 16.0f;  // the cap an integrator would apply (integrator.cu:7-13)
+  int max_blocks = 1024;              // blocks a ray's carve may cross; what it does not reach is not carved
+};
+
+// Volume::CarveRays (vk_volume_carve_rays' eight counts)
+struct CarveRaysCounts
+{
+  int carved;           // rays that carved
+  int nothing;          // measured rays with nothing to carve: the carve would start at the band, or behind it
+  int unmeasured;       // valid rays without a measurement
+  int invalid;          // rays CastRays would call VK_RAY_INVALID
+  int cut_short;        // rays whose carve ended at max_blocks
+  int blocks;           // blocks that took an update
+  int voxels;           // voxels updated
+  unsigned carves;      // cells carved, over all rays
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -261,6 +286,16 @@ class Volume
     IntegrateRaysCounts IntegrateRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform* pose = nullptr,
         const IntegrateRaysOptions& options = IntegrateRaysOptions());
 
+    // Not upstream: carve the free space in front of `count` range measurements (vk_volume_carve_rays) — what is no
+    // longer there. Rays, ranges and pose are IntegrateRays'. Every voxel of an existing block whose cell a measured ray
+    // crosses between options.t_from and the start of the band IntegrateRays fuses takes an observation of the distance 1,
+    // "free"; colours are left alone, and the order of the rays does not matter. Nothing is allocated: absent blocks are
+    // passed over, and the hash table, the free list, the visible list and what was made ahead stay as they are. Between
+    // SetView calls only: throws while a frame announced by Tracer::Trace(keyframe, next_frame) is outstanding. Both
+    // buffers are device memory and only read. One blocking readback (the eight counts); count == 0 does nothing.
+    CarveRaysCounts CarveRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform* pose = nullptr,
+        const CarveRaysOptions& options = CarveRaysOptions());
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -325,9 +360,11 @@ class Volume
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
     Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
     Buffer<int> register_ints_;                    // the state (2), the counts (4)
-    mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays: the pose on the device (32)
+    mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays, CarveRays: the pose on the device (32)
     Buffer<unsigned char> rays_workspace_;         // IntegrateRays: allocated by the first call
     Buffer<int> rays_counts_;
+    Buffer<unsigned char> carve_workspace_;        // CarveRays: allocated by the first call
+    Buffer<int> carve_counts_;
 
     Vector2f depth_range_;
     int max_block_count_;

@@ -574,6 +574,41 @@ IntegrateRaysCounts Volume::IntegrateRays(const Ray* rays_dev, const float* rang
   return out;
 }
 
+CarveRaysCounts Volume::CarveRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform* pose,
+    const CarveRaysOptions& options)
+{
+  static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
+  AssertNoFrameAnnounced();
+  CarveRaysCounts out = {};
+  vk_carve_rays_params p;
+  p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+  p.max_blocks = options.max_blocks;
+  p.r_min = options.r_min;
+  p.r_max = options.r_max;
+  p.t_from = options.t_from;
+  p.max_distance_weight = options.max_distance_weight;
+  const size_t bytes = vk_volume_carve_rays_workspace_bytes(main_block_count_, excess_block_count_);
+  if (carve_workspace_.GetSize() != bytes) carve_workspace_.Resize(bytes);
+  if (carve_counts_.GetSize() == 0) carve_counts_.Resize(8);
+  const vk_transform* pose_dev = PoseOnDevice(count > 0 ? pose : nullptr);      // no rays: no upload
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_carve_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose_dev, &p, carve_counts_.GetData(),
+      carve_workspace_.GetData(), Device::GetStream()));
+  if (count == 0) return out;                      // nothing was launched and the counts were not written
+  // the table and the visible list are as they were: nothing made ahead is void
+  int32_t counts[8];
+  carve_counts_.CopyToHost(counts);
+  out.carved = counts[0];
+  out.nothing = counts[1];
+  out.unmeasured = counts[2];
+  out.invalid = counts[3];
+  out.cut_short = counts[4];
+  out.blocks = counts[5];
+  out.voxels = counts[6];
+  out.carves = unsigned(counts[7]);
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   AssertNoFrameAnnounced();
