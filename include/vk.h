@@ -734,7 +734,10 @@ VK_API int vk_trace_normals_settle(vk_view_bounds* ahead, void* stream);
 
 /* ------------------------------------------------------------------- image -- */
 
-/* ref: src/image.cu:101-165,183-211 Image::Downsample (nearest or 2x2 box) */
+/* ref: src/image.cu:101-165,183-211 Image::Downsample (nearest or 2x2 box). dst is (src_w / 2) x (src_h / 2),
+ * rounded down: an odd size loses its last column / row, which is what upstream's kernels compute (its host
+ * wrapper asks for even sizes in debug builds only); nothing is launched for an empty dst. The same holds for
+ * vk_color_image_downsample and vk_frame_downsample. */
 VK_API int vk_image_downsample(int src_w, int src_h, const float* src,
     float* dst, int nearest, void* stream);
 
@@ -745,7 +748,7 @@ VK_API int vk_color_image_downsample(int src_w, int src_h, const float* src,
 /* ref: src/frame.cpp:38-51 Frame::Downsample's three image passes in one launch: depth and
  * normals nearest, colour 2x2 box (exactly vk_image_downsample / vk_color_image_downsample).
  * An output that is NULL is skipped; depth and normals have the size frame->width x height,
- * the colour image its own (color_width x color_height, 0 = the same); all sizes even. */
+ * the colour image its own (color_width x color_height, 0 = the same). */
 VK_API int vk_frame_downsample(const vk_frame* frame, float* depth_out, float* color_out,
     float* normals_out, void* stream);
 

@@ -227,3 +227,25 @@ def test_fused_begin_and_frame_downsample_match_the_staged_calls(api, orc):
         sync()
         for a, b in ((d1, d2), (c1, c2), (n1, n2)):
             assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (w, h)
+
+
+def test_downsample_of_odd_sizes_matches_the_oracle(api, orc):
+    """An odd image size loses its last column / row (image.cu:101-165 reads the 2x2 pixels from (2x, 2y) for
+    x < w / 2, y < h / 2): Frame.downsample's staged entry points and vk_frame_downsample against the oracle."""
+    import torch
+    rng = np.random.default_rng(11)
+    for (w, h) in ((101, 75), (202, 151), (65, 9), (3, 3), (2, 5)):
+        depth = rng.random((h, w), dtype=np.float32)
+        color = rng.random((h, w, 3), dtype=np.float32)
+        normals = rng.random((h, w, 3), dtype=np.float32)
+        frm = api.Frame(depth, T.Projection.make(0.85 * w, 0.85 * w, w / 2, h / 2), T.Transform.identity(), color=color, normals=normals)
+        want = (orc.downsample(depth, True), orc.downsample(color, False), orc.downsample(normals, True))
+        assert want[0].shape == (h // 2, w // 2)
+        half = frm.downsample()
+        new = lambda *shape: torch.full(shape, -7.0, dtype=torch.float32, device="cuda")
+        d2, c2, n2 = new(h // 2, w // 2), new(h // 2, w // 2, 3), new(h // 2, w // 2, 3)
+        api.check(api.lib().vk_frame_downsample(C.byref(frm.desc()), api._ptr(d2), api._ptr(c2), api._ptr(n2), api.stream()), "frame down")
+        sync()
+        for got, fused, ref in zip((half.depth, half.color, half.normals), (d2, c2, n2), want):
+            assert np.array_equal(bits(got.cpu().numpy()), bits(ref)), (w, h)
+            assert np.array_equal(bits(fused.cpu().numpy()), bits(ref)), (w, h)

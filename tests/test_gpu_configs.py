@@ -207,7 +207,7 @@ def curved_depth(w, h):
     return (1.0 + 0.05 * np.cos(3.0 * x / w) * np.sin(2.0 * y / h)).astype(np.float32)
 
 
-@pytest.mark.parametrize("size", [(320, 240), (640, 480), (1280, 960)])
+@pytest.mark.parametrize("size", [(320, 240), (640, 480), (1280, 960), (202, 150)])
 def test_pyramid_tracker_two_views_matches_oracle(api, orc, size):
     """The second case bench.py's pyramid-icp leg times (configs[3], round 6; bench.pyramid_case "two views"): the room scene
     rendered from two poses 33 mm / 2.6 deg apart, the frame started at the key frame's pose — different images, so both
@@ -239,7 +239,7 @@ def test_pyramid_tracker_two_views_matches_oracle(api, orc, size):
     assert bytes(tracker.track(df)) == bytes(got)
 
 
-@pytest.mark.parametrize("size", [(320, 240), (640, 480), (1280, 960)])
+@pytest.mark.parametrize("size", [(320, 240), (640, 480), (1280, 960), (202, 150)])
 def test_pyramid_tracker_matches_oracle(api, orc, size):
     """PyramidTracker<DepthTracker>::Track: downsampled levels bit-exact, final pose within
     2e-5 per matrix entry of the oracle's pyramid loop (float tree sums vs float64 sums are

@@ -1033,11 +1033,12 @@ int vk_icp_solve_update_rig(const float* hessian, const float* gradient, int tra
 
 int vk_frame_downsample(const vk_frame* frame, float* depth_out, float* color_out, float* normals_out, void* stream)
 {
-  VK_REQUIRE(frame && frame->width > 0 && frame->height > 0 && (frame->width % 2) == 0 && (frame->height % 2) == 0);
+  // an odd size loses its last column / row (dst = src / 2, rounded down, so the 2x2 source pixels of every
+  // destination pixel exist): what upstream's kernels compute
+  VK_REQUIRE(frame && frame->width > 0 && frame->height > 0);
   VK_REQUIRE((!depth_out || frame->depth) && (!color_out || frame->color) && (!normals_out || frame->normals));
   const int cw = frame->color_width > 0 ? frame->color_width : frame->width;
   const int ch = frame->color_height > 0 ? frame->color_height : frame->height;
-  VK_REQUIRE(!color_out || ((cw % 2) == 0 && (ch % 2) == 0));
   FrameLevel L;
   const float* src[3] = {frame->depth, frame->color, frame->normals};
   float* dst[3] = {depth_out, color_out, normals_out};
@@ -1052,7 +1053,7 @@ int vk_frame_downsample(const vk_frame* frame, float* depth_out, float* color_ou
     L.dst_h[job] = h / 2;
     if (dst[job]) { gw = gw > w / 2 ? gw : w / 2; gh = gh > h / 2 ? gh : h / 2; }
   }
-  if (gw == 0) return VK_OK;
+  if (gw == 0 || gh == 0) return VK_OK;
   hipLaunchKernelGGL(frame_downsample_kernel, dim3((gw + 63) / 64, (gh + 3) / 4, 3), dim3(256), 0, vk_s(stream), L);
   VK_LAUNCH_CHECK();
   return VK_OK;
@@ -1060,8 +1061,9 @@ int vk_frame_downsample(const vk_frame* frame, float* depth_out, float* color_ou
 
 int vk_image_downsample(int src_w, int src_h, const float* src, float* dst, int nearest, void* stream)
 {
-  VK_REQUIRE(src && dst && src_w > 0 && src_h > 0 && (src_w % 2) == 0 && (src_h % 2) == 0);
-  const int dst_w = src_w / 2, dst_h = src_h / 2;
+  VK_REQUIRE(src && dst && src_w > 0 && src_h > 0);
+  const int dst_w = src_w / 2, dst_h = src_h / 2;     // rounded down: an odd size loses its last column / row
+  if (dst_w == 0 || dst_h == 0) return VK_OK;
   const dim3 grid((dst_w + 63) / 64, (dst_h + 3) / 4);
   hipLaunchKernelGGL(downsample_kernel, grid, dim3(256), 0, vk_s(stream), src_w, dst_w, dst_h, src, dst, nearest);
   VK_LAUNCH_CHECK();
@@ -1070,8 +1072,9 @@ int vk_image_downsample(int src_w, int src_h, const float* src, float* dst, int 
 
 int vk_color_image_downsample(int src_w, int src_h, const float* src, float* dst, int nearest, void* stream)
 {
-  VK_REQUIRE(src && dst && src_w > 0 && src_h > 0 && (src_w % 2) == 0 && (src_h % 2) == 0);
-  const int dst_w = src_w / 2, dst_h = src_h / 2;
+  VK_REQUIRE(src && dst && src_w > 0 && src_h > 0);
+  const int dst_w = src_w / 2, dst_h = src_h / 2;     // rounded down: an odd size loses its last column / row
+  if (dst_w == 0 || dst_h == 0) return VK_OK;
   const dim3 grid((dst_w + 63) / 64, (dst_h + 3) / 4);
   hipLaunchKernelGGL(downsample3_kernel, grid, dim3(256), 0, vk_s(stream), src_w, dst_w, dst_h, src, dst, nearest);
   VK_LAUNCH_CHECK();
