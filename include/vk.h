@@ -1697,6 +1697,73 @@ VK_API int vk_volume_carve_rays(const vk_volume* v, const float* rays /* device 
     const float* ranges /* device [count] */, int32_t count, const vk_transform* pose_dev /* optional: T_volume_rays */,
     const vk_carve_rays_params* p, int32_t* counts_dev /* [8] */, void* workspace, void* stream);
 
+/* -------------------------------------------------------------- color rays -- */
+
+typedef struct vk_color_rays_params {
+  int32_t flags;               /* VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION; any other bit is VK_ERR_ARGUMENT */
+  float   r_min, r_max;        /* a ray has a measurement iff r_min <= range <= r_max (vk_volume_integrate_rays' rule) */
+  float   band;                /* half width of the coloured stretch around the measurement, in the origin's unit; > 0, finite */
+  float   max_color_weight;    /* 1 .. 32767 */
+  int32_t pad;
+} vk_color_rays_params;        /* 24 bytes */
+
+/* Fuse a colour per range ray into the volume: every voxel of an existing block whose cell a coloured ray crosses within
+ * `band` of its measurement, and whose stored distance says it is near the surface, continues its colour's running average
+ * with the mean colour of the rays through it — a LiDAR return coloured by a camera, or the colour vk_volume_cast_rays
+ * returned for another volume. vk_volume_integrate_rays and vk_volume_carve_rays leave the colour alone; this call writes
+ * nothing else. No upstream counterpart (the reference colours only from the pixels of one pinhole image); ref:
+ * src/color_integrator.cu:121 for the test that a voxel is near the surface, src/color_integrator.cu:125-129 for the running
+ * average and its cap. The definition is this comment; tests/color_rays_reference.py states it on the CPU and the device is
+ * held to it bit for bit. All arithmetic is fp32, one rounding per operation, no contraction, IEEE division and a correctly
+ * rounded square root.
+ * PRECONDITIONS: vk_volume_integrate_rays' — between SetView calls, no frame announced (the class layers enforce it).
+ * ACCESS: rays, ranges, colors, the pose, the hash table are only read; of the volume only the colour and the colour weight
+ * of voxels are written. THE CALL ALLOCATES NOTHING: the hash table, the free list, the visibility and allocation arrays, the
+ * visible list and every VK_CTR_* keep their bytes, and the lists of the last SetView stay valid; so do distance and
+ * distance_weight of every voxel. Everything is enqueued on `stream`, nothing is read back, no workgroup waits on another; the
+ * walk is bounded by G <= 390 and a chain walk by the table size: it cannot hang a device. `workspace`:
+ * vk_volume_color_rays_workspace_bytes(main, excess) bytes (16 per pool voxel), 16-byte aligned, need not be initialised.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): v, p, counts_dev or workspace null, a volume that vk_volume_merge would
+ * refuse, a flag other than the two, a cap outside 1 .. 32767, r_min or r_max not finite or not 0 <= r_min < r_max, band not
+ * finite or <= 0 or band / L > 64 (band > 64 with VK_RAYS_VOXEL_UNITS), count < 0 or count > 1 << 21, rays, ranges or colors
+ * null with count > 0, a workspace not 16-byte aligned, truncation_length / voxel_length > 64. count == 0 returns 0, launches
+ * nothing and leaves counts_dev alone.
+ * (the ray) vk_volume_integrate_rays' word for word: units, pose, n, the INVALID rule, r, the measurement test.
+ * (has a colour) c_k = colors[3i + k]. A measured ray HAS A COLOUR iff 0 <= c_k <= 1 for all three channels (false for a
+ * NaN). A ray is, by the first that applies: invalid; without a measurement; without a colour; COLOURED. Only a coloured
+ * ray walks.
+ * (the walk) b = band / L (b = band with VK_RAYS_VOXEL_UNITS), ta = fmaxf(r - b, 0), tb = r + b, and from there
+ * vk_volume_integrate_rays' cell walk unchanged: the same p, c, tmax, tdelta, tie rule and guard G = 3 * (min((int)ceilf(tb -
+ * ta), 1024) + 2), the conversion saturating and a NaN giving 0 (tb - ta <= 2 b <= 128, so G <= 390 for finite ends). A
+ * visited cell whose block B = c >> 3 has a coordinate outside the int16 range is passed over: counted nowhere. A visited
+ * cell whose block is absent from the table (the chain walk) is a LOST visit: counted, and skipped.
+ * (accumulation) every other visit adds q_k = (int)rintf(c_k * 1024.0f) (ties to even) to the voxel's three sums S_k and 1 to
+ * its N. With count <= 2^21 and c_k <= 1 every S_k <= 2^31 and N <= 2^21: two 64-bit words per voxel, S_0 | S_1 << 32 and
+ * S_2 | N << 32, hold the four with no carry between them, and a visit is two 64-bit integer atomics. Integer sums commute:
+ * S_k and N do not depend on the order of the rays or on timing. No float atomic touches a voxel or an accumulator.
+ * (the fold) for every voxel with N > 0: it is NEAR THE SURFACE iff fabsf(distance) < 1.0f, the stored distance (false for
+ * a NaN; a voxel nothing was fused into holds 1). A near voxel: m_k = ((float)S_k / (float)N) * 0x1p-10f (both conversions
+ * exact or round to nearest even), ws = VK_RAYS_ONE_OBSERVATION ? 1.0f : (float)N, wc = (float)color_weight, color_k =
+ * wc == 0 ? m_k : (wc * color_k + ws * m_k) / (wc + ws), color_weight = (int16)fminf(max_color_weight, wc + ws):
+ * vk_volume_merge's continuation with the reference's cap. A voxel that is not near is counted and keeps all its bytes, as
+ * does every voxel with N == 0.
+ * counts_dev int32[8]: rays coloured; measured rays without a colour; valid rays without a measurement; invalid rays; blocks
+ * that took an update; voxels updated; voxels visited (N > 0) but not near the surface; visits lost to an absent block (the sum
+ * wraps at 2^32). */
+VK_API size_t vk_volume_color_rays_workspace_bytes(int32_t main, int32_t excess);
+VK_API int vk_volume_color_rays(const vk_volume* v, const float* rays /* device [6*count]: origin, direction */,
+    const float* ranges /* device [count] */, const float* colors /* device [3*count]: r, g, b in [0, 1] */, int32_t count,
+    const vk_transform* pose_dev /* optional: T_volume_rays */, const vk_color_rays_params* p, int32_t* counts_dev /* [8] */,
+    void* workspace, void* stream);
+
+/* Measurement only: the next vk_volume_color_rays of this host thread records events[0 .. 4] (vk_event_create) on its stream
+ * in front of its first pass, behind the mark pass, the zero pass, the add pass and the fold, so that
+ * tools/color_rays_bench.py can say what each pass costs; no upstream counterpart (ref: the reference times its integrators
+ * from outside, src/color_integrator.cu:144-148). One CALL only, as with
+ * vk_volume_integrate_rays_time_next: the events are used up by the next call even when it returns an error before its
+ * launches, and a call with count == 0 records none; (NULL, 0) cancels. `count` must be 5. Not a stream operation. */
+VK_API int vk_volume_color_rays_time_next(void* const* events, int32_t count);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

@@ -134,6 +134,9 @@ _SIGNATURES = {
     "vk_volume_integrate_rays_time_next": ([_P, C.c_int32], _I),
     "vk_volume_carve_rays_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
     "vk_volume_carve_rays": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
+    "vk_volume_color_rays_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
+    "vk_volume_color_rays": ([_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
+    "vk_volume_color_rays_time_next": ([_P, C.c_int32], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -879,6 +882,48 @@ class Volume:
         if rays.shape[0] == 0:
             return (0,) * 8
         return self._carve_rays_call(rays, ranges, pose, flags, max_blocks, r_min, r_max, t_from, max_distance_weight, rays.shape[0])
+
+    def _color_rays_call(self, rays, ranges, colors, pose=None, flags=0, r_min=0.1, r_max=5.0, band=0.04, max_color_weight=16.0,
+                         count=None):
+        """one vk_volume_color_rays of `rays`, `ranges` and `colors` (float32 device tensors of 6 * count, count and 3 * count
+        floats or more): the eight counts from one blocking read. `pose`: a T.Transform (uploaded), a device buffer that
+        holds a vk_transform, or None. The table and the visible list are left alone, so nothing made ahead is void."""
+        self._no_requests_pending("color_rays")
+        count = ranges.numel() if count is None else int(count)
+        pose = self._pose_on_device(pose)
+        workspace, counts = self._workspace("color_rays", (self.main, self.excess), lib().vk_volume_color_rays_workspace_bytes, 8)
+        params = T.ColorRaysParams(int(flags), float(r_min), float(r_max), float(band), float(max_color_weight), 0)
+        check(lib().vk_volume_color_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), _ptr(colors), count, _ptr(pose), _ref(params),
+                                         _ptr(counts), _ptr(workspace), stream()), "vk_volume_color_rays")
+        return _ints(counts)
+
+    def color_rays(self, rays, ranges, colors, pose=None, band=None, r_min=None, r_max=None, max_color_weight=16,
+                   one_observation=False, voxel_units=False):
+        """vk_volume_color_rays (not upstream): fuse a colour per range ray — a LiDAR return coloured by a camera, or the
+        colour cast_rays returned for another volume. `rays`, `ranges`, `pose`, `r_min`, `r_max` and `voxel_units` are
+        integrate_rays'; `colors` is a float32 [N, 3] device tensor of r, g, b in [0, 1]: a measured ray with a channel
+        outside that, a NaN included, has no colour and is skipped. Every voxel of an existing block whose cell a coloured
+        ray crosses within `band` of its measurement (in the origins' unit; None: the truncation length), and whose stored
+        distance is near the surface (|distance| < 1), continues its colour's running average with the mean colour of the
+        rays through it, weighted with their number (`one_observation`: with 1), the weight capped at `max_color_weight`.
+        Nothing is allocated — colouring where no block exists is a lost visit, so call integrate_rays first — and the
+        distances, their weights, the table, the free list, the visible list and the counters keep their bytes. The result
+        does not depend on the order of the rays. At most 1 << 21 rays a call. Between SetView calls only: raises while a
+        frame is announced. Returns (rays coloured, measured rays without a colour, valid rays without a measurement,
+        invalid rays, blocks updated, voxels updated, voxels visited but not near a surface, visits lost to an absent
+        block)."""
+        rays = _float_tensor(rays, 6, "color_rays: rays is a float32 [N, 6] device tensor")
+        ranges = _float_tensor(ranges, None, "color_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        colors = _float_tensor(colors, 3, "color_rays: colors is a float32 [N, 3] device tensor, one colour per ray", rays.shape[0])
+        pose = _as_pose(pose, device=True)
+        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
+        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
+        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
+        band = float(np.float32(self.truncation_length) / scale) if band is None else band
+        flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
+        if rays.shape[0] == 0:
+            return (0,) * 8
+        return self._color_rays_call(rays, ranges, colors, pose, flags, r_min, r_max, band, max_color_weight, rays.shape[0])
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

@@ -173,6 +173,30 @@ struct CarveRaysCounts
   unsigned carves;      // cells carved, over all rays
 };
 
+// Not upstream: how Volume::ColorRays reads its rays, ranges and colours and what it colours (vk_color_rays_params)
+struct ColorRaysOptions
+{
+  bool voxel_units = false;           // the origins, the ranges, r_min, r_max and band are in voxels, not metres
+  bool one_observation = false;       // a voxel's mean colour counts as one observation, not as one per ray through it
+  float r_min = 0.1f;                 // IntegrateRays' rule: a ray whose range lies outside [r_min, r_max] carries no
+  float r_max = 5.0f;                 //   measurement and colours nothing
+  float band = 0.0f;                  // half width of the coloured stretch around the measurement; 0: the truncation length
+  float max_color_weight = 16.0f;     // the cap a ColorIntegrator would apply (color_integrator.cu:125-129)
+};
+
+// Volume::ColorRays (vk_volume_color_rays' eight counts)
+struct ColorRaysCounts
+{
+  int coloured;         // rays that coloured
+  int colourless;       // measured rays without a colour: a channel outside [0, 1], a NaN included
+  int unmeasured;       // valid rays without a measurement
+  int invalid;          // rays CastRays would call VK_RAY_INVALID
+  int blocks;           // blocks that took an update
+  int voxels;           // voxels updated
+  int not_near;         // voxels visited whose stored distance is not near a surface: left alone
+  unsigned lost;        // cell visits lost to a block that does not exist
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -296,6 +320,18 @@ class Volume
     CarveRaysCounts CarveRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform* pose = nullptr,
         const CarveRaysOptions& options = CarveRaysOptions());
 
+    // Not upstream: fuse a colour per range ray (vk_volume_color_rays) — a LiDAR return coloured by a camera, or the colour
+    // CastRays returned for another volume. Rays, ranges and pose are IntegrateRays'; colors_dev[i] is r, g, b in [0, 1].
+    // Every voxel of an existing block whose cell a coloured ray crosses within options.band of its measurement, and whose
+    // stored distance is near the surface, continues its colour's running average with the mean colour of the rays
+    // through it; the order of the rays does not matter. Nothing is allocated — a cell without a block is a lost visit:
+    // call IntegrateRays first — and the distances, the hash table, the free list, the visible list and what was made
+    // ahead stay as they are. At most 1 << 21 rays a call. Between SetView calls only: throws while a frame announced by
+    // Tracer::Trace(keyframe, next_frame) is outstanding. The three buffers are device memory and only read. One blocking
+    // readback (the eight counts); count == 0 does nothing.
+    ColorRaysCounts ColorRays(const Ray* rays_dev, const float* ranges_dev, const Vector3f* colors_dev, int count,
+        const Transform* pose = nullptr, const ColorRaysOptions& options = ColorRaysOptions());
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -360,11 +396,13 @@ class Volume
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
     Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
     Buffer<int> register_ints_;                    // the state (2), the counts (4)
-    mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays, CarveRays: the pose on the device (32)
+    mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays, CarveRays, ColorRays: the pose on the device (32)
     Buffer<unsigned char> rays_workspace_;         // IntegrateRays: allocated by the first call
     Buffer<int> rays_counts_;
     Buffer<unsigned char> carve_workspace_;        // CarveRays: allocated by the first call
     Buffer<int> carve_counts_;
+    Buffer<unsigned char> color_rays_workspace_;   // ColorRays: allocated by the first call
+    Buffer<int> color_rays_counts_;
 
     Vector2f depth_range_;
     int max_block_count_;

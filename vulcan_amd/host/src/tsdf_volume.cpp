@@ -609,6 +609,41 @@ CarveRaysCounts Volume::CarveRays(const Ray* rays_dev, const float* ranges_dev, 
   return out;
 }
 
+ColorRaysCounts Volume::ColorRays(const Ray* rays_dev, const float* ranges_dev, const Vector3f* colors_dev, int count,
+    const Transform* pose, const ColorRaysOptions& options)
+{
+  static_assert(sizeof(Ray) == 6 * sizeof(float) && sizeof(Vector3f) == 3 * sizeof(float), "Ray and colour layout");
+  AssertNoFrameAnnounced();
+  ColorRaysCounts out = {};
+  const vk_volume v = ToVk();
+  vk_color_rays_params p;
+  p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+  p.r_min = options.r_min;
+  p.r_max = options.r_max;
+  p.band = options.band != 0.0f ? options.band : (options.voxel_units ? v.truncation_length / v.voxel_length : v.truncation_length);
+  p.max_color_weight = options.max_color_weight;
+  p.pad = 0;
+  const size_t bytes = vk_volume_color_rays_workspace_bytes(main_block_count_, excess_block_count_);
+  if (color_rays_workspace_.GetSize() != bytes) color_rays_workspace_.Resize(bytes);
+  if (color_rays_counts_.GetSize() == 0) color_rays_counts_.Resize(8);
+  const vk_transform* pose_dev = PoseOnDevice(count > 0 ? pose : nullptr);      // no rays: no upload
+  VK_ASSERT(vk_volume_color_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, reinterpret_cast<const float*>(colors_dev),
+      count, pose_dev, &p, color_rays_counts_.GetData(), color_rays_workspace_.GetData(), Device::GetStream()));
+  if (count == 0) return out;                      // nothing was launched and the counts were not written
+  // the table and the visible list are as they were: nothing made ahead is void
+  int32_t counts[8];
+  color_rays_counts_.CopyToHost(counts);
+  out.coloured = counts[0];
+  out.colourless = counts[1];
+  out.unmeasured = counts[2];
+  out.invalid = counts[3];
+  out.blocks = counts[4];
+  out.voxels = counts[5];
+  out.not_near = counts[6];
+  out.lost = unsigned(counts[7]);
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   AssertNoFrameAnnounced();

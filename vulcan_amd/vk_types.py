@@ -29,7 +29,7 @@ VK_REGISTER_NO_OVERLAP = 2                                                      
 VK_SAMPLE_VOXEL_UNITS, VK_SAMPLE_DISTANCE_ONLY = 1, 2                            # vk_sample_params.flags
 VK_CAST_VOXEL_UNITS, VK_CAST_DISTANCE_ONLY = 1, 2                                # vk_cast_params.flags
 VK_RAY_MISS, VK_RAY_HIT, VK_RAY_STEPS, VK_RAY_INVALID = 0, 1, 2, 3               # vk_volume_cast_rays: status[i]
-VK_RAYS_VOXEL_UNITS, VK_RAYS_ONE_OBSERVATION = 1, 2                              # vk_integrate_rays_params.flags, vk_carve_rays_params.flags
+VK_RAYS_VOXEL_UNITS, VK_RAYS_ONE_OBSERVATION = 1, 2                              # vk_integrate_rays_params.flags, vk_carve_rays_params.flags, vk_color_rays_params.flags
 
 voxel_dtype = np.dtype([("distance", "<f4"), ("color", "<f4", (3,)),
                         ("distance_weight", "<i2"), ("color_weight", "<i2")])
@@ -248,6 +248,13 @@ class CarveRaysParams(C.Structure):
     many blocks a ray may cross, which ranges are measurements, where the carve starts and the cap of the distance weight"""
     _fields_ = [("flags", C.c_int32), ("max_blocks", C.c_int32), ("r_min", C.c_float), ("r_max", C.c_float),
                 ("t_from", C.c_float), ("max_distance_weight", C.c_float)]
+
+
+class ColorRaysParams(C.Structure):
+    """vk_color_rays_params (vk.h): the units of vk_volume_color_rays' origins, ranges and band, the weight of a voxel's mean
+    colour, which ranges are measurements, the half width of the coloured stretch and the cap of the colour weight"""
+    _fields_ = [("flags", C.c_int32), ("r_min", C.c_float), ("r_max", C.c_float), ("band", C.c_float),
+                ("max_color_weight", C.c_float), ("pad", C.c_int32)]
 
 
 class PyramidAhead(C.Structure):
