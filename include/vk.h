@@ -1210,7 +1210,7 @@ VK_API int vk_compact_offsets(const int32_t* counts, int32_t count, int32_t* off
  * belongs to a block that is not listed, blocks listed}. Counts are the full totals even when
  * a capacity is too small (nothing is written past a capacity). Order: blocks in list order,
  * cubes by z*64 + y*8 + x, vertices by axis, faces in table order — reproducible.
- * workspace: device, vk_extract_workspace_bytes(main, excess) bytes. Four launches, no readback. */
+ * workspace: device, vk_extract_workspace_bytes(main, excess) bytes, need not be initialised. Four launches, no readback. */
 VK_API size_t vk_extract_workspace_bytes(int32_t main_block_count, int32_t excess_block_count);
 VK_API int vk_extract_mesh(const vk_volume* v, int all_allocated, int interpolate, float* points,
     int32_t point_capacity, int32_t* faces, int32_t face_capacity, int32_t* counts_dev,
@@ -1277,7 +1277,7 @@ typedef struct vk_release_rule {
  * list. Anything prepared ahead for the volume is VOID after the call and must be invalidated by the caller: the
  * vk_view_bounds records (valid = 0), a vk_light_prep (valid = 0), and no vk_requests_ahead record may be valid.
  * v->voxels 16-byte aligned. workspace: device, vk_volume_release_workspace_bytes(main, excess) bytes (0 for sizes that
- * are not a volume's). Thirteen short launches on `stream` (the two ordered scans are vk_compact_offsets'); only released blocks' voxels are written
+ * are not a volume's), need not be initialised. Thirteen short launches on `stream` (the two ordered scans are vk_compact_offsets'); only released blocks' voxels are written
  * and only allocated blocks' voxels are read (none when OUTSIDE_BOX is the only rule). */
 VK_API size_t vk_volume_release_workspace_bytes(int32_t main_block_count, int32_t excess_block_count);
 VK_API int vk_volume_release_blocks(const vk_volume* v, const vk_release_rule* rule,
@@ -1331,7 +1331,8 @@ typedef struct vk_merge_params {
  * is the last handle pass's; anything prepared ahead for dst is VOID as after vk_volume_release_blocks. counts_dev:
  * device int32[6] = {source blocks considered, blocks fused, blocks allocated by the call, source blocks left out,
  * rounds that posted a request, source blocks skipped as unobserved}. workspace: device,
- * vk_volume_merge_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's). 5 + 4 * max_rounds
+ * vk_volume_merge_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's), need not be
+ * initialised: the one thing a workspace carries from call to call is what a CONTINUE call takes over. 5 + 4 * max_rounds
  * short launches on `stream` and one pass of one wave per source block over the two voxel pools. Moving a replica
  * between devices is the caller's: both volumes' buffers are on the stream's device. */
 VK_API size_t vk_volume_merge_workspace_bytes(int32_t src_main, int32_t src_excess);
@@ -1386,7 +1387,8 @@ typedef struct vk_merge_pose_params {
  * (afterwards) as vk_volume_merge. counts_dev: device int32[8] = {source blocks considered, candidate dst blocks (of a
  * CONTINUE call: those not fused before), candidates fused, blocks allocated by the call, candidates left out, rounds
  * that posted, source blocks skipped as unobserved (0 in a CONTINUE call), voxels that took a distance sample}.
- * workspace: device, vk_volume_merge_posed_workspace_bytes(...) bytes (0 for sizes that are not a volume's). */
+ * workspace: device, vk_volume_merge_posed_workspace_bytes(...) bytes (0 for sizes that are not a volume's), need not be
+ * initialised (a CONTINUE call's excepted, as vk_volume_merge's). */
 VK_API size_t vk_volume_merge_posed_workspace_bytes(int32_t src_main, int32_t src_excess, int32_t dst_main, int32_t dst_excess);
 VK_API int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_merge_pose_params* p,
     int32_t* counts_dev /* [8] */, void* workspace, void* stream);
@@ -1447,7 +1449,8 @@ typedef struct vk_register_params {
  * vk_volume_register_system: one evaluation at the pose. vk_volume_register_terms: for source pool slot q and voxel i,
  * valid[q*512+i], residuals[q*512+i] and jacobians[(q*512+i)*6 ..], zeros where no residual exists; the three buffers
  * hold (src main + excess) * 512 voxels.
- * workspace: device, vk_volume_register_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's). */
+ * workspace: device, vk_volume_register_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's),
+ * need not be initialised. */
 VK_API size_t vk_volume_register_workspace_bytes(int32_t src_main, int32_t src_excess);
 VK_API int vk_volume_register_terms(const vk_volume* dst, const vk_volume* src, const vk_transform* pose_dev,
     const vk_register_params* p, float* residuals, float* jacobians, uint8_t* valid, void* workspace, void* stream);
