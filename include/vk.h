@@ -1767,6 +1767,79 @@ VK_API int vk_volume_color_rays(const vk_volume* v, const float* rays /* device 
  * launches, and a call with count == 0 records none; (NULL, 0) cancels. `count` must be 5. Not a stream operation. */
 VK_API int vk_volume_color_rays_time_next(void* const* events, int32_t count);
 
+/* ----------------------------------------------------------- register rays -- */
+
+typedef struct vk_register_rays_params {
+  int32_t flags;             /* VK_RAYS_VOXEL_UNITS; any other bit VK_ERR_ARGUMENT */
+  int32_t iterations;        /* 1 .. 64 */
+  float   r_min, r_max;      /* a ray has a measurement iff r_min <= range <= r_max (vk_volume_integrate_rays' rule) */
+  float   max_abs_distance;  /* band, in truncation lengths: 0 < band <= 1 */
+  int32_t pad;
+} vk_register_rays_params;   /* 24 bytes */
+
+/* Localise a sweep of range rays in the volume: refine the sensor's pose T_volume_rays — the pose vk_volume_integrate_rays,
+ * vk_volume_carve_rays and vk_volume_color_rays take as given — by Gauss-Newton on "the endpoint of a return lies on the
+ * mapped surface": every measured ray's endpoint is carried into the volume, the field is sampled there, and the pose moves
+ * so that the sample is 0. It REFINES a guess that already brings the endpoints within roughly a truncation length of the
+ * surface; it searches nothing. No upstream counterpart (the reference tracks pinhole depth images against a raycast
+ * keyframe); ref: src/tracker.cpp:124-163 for the loop and its end, src/color_tracker.cpp:45-95 for the step,
+ * src/tracer.cu:238-299 for the trilinear sample. The definition is this comment; tests/register_rays_reference.py states
+ * it on the CPU. All arithmetic is fp32, one rounding per operation, no contraction, IEEE division and a correctly rounded
+ * square root.
+ * ACCESS: the volume, rays and ranges are only read: the call may run while a frame is announced, like vk_volume_sample.
+ * HOST CHECKS (VK_ERR_ARGUMENT, nothing enqueued): v, p, pose_dev, an output (update_dev alone may be null) or the workspace
+ * null, a volume that vk_volume_sample would refuse, a flag other than VK_RAYS_VOXEL_UNITS, iterations outside 1 .. 64, the
+ * band not in (0, 1] (a NaN included), r_min or r_max not finite or not 0 <= r_min < r_max, count < 0 or count > 1 << 22,
+ * rays or ranges null with count > 0, a workspace not 16-byte aligned. count == 0 returns 0, launches nothing and leaves
+ * every output's bytes alone.
+ * (the ray) vk_volume_integrate_rays' word for word: units, pose_dev = T_volume_rays, n, the INVALID rule, r, the
+ * measurement test. Here pose_dev is required: it is the unknown. m is used as given; the solve rewrites m and inv together.
+ * (endpoint) of a valid ray with a measurement: e_a = o_a + r * n_a (mul, add), in voxels, in the volume's frame. A measured
+ * ray with a non-finite e_a has no sample.
+ * (sample) vk_volume_register's at p = e: g_a = e_a - 0.5f, b_a = floorf(g_a), f_a = g_a - b_a, the eight lattice points
+ * b + k found by the chain walk, absent when a block coordinate leaves the int16 range; the sample exists iff all eight are
+ * present with distance_weight != 0 (no "used points" rule); D and gx, gy, gz by the very lerp sequence written there.
+ * (residual) exists iff the ray is valid and measured, the sample exists and fabsf(D) < band. Then r_i = D — the endpoint
+ * of a return lies on the surface, so the target is 0 — weight 1,
+ *   J0 = e1*gz - e2*gy, J1 = e2*gx - e0*gz, J2 = e0*gy - e1*gx,  J3 = gx*iv, J4 = gy*iv, J5 = gz*iv,
+ * iv = 1.0f / voxel_length computed once: vk_volume_register's form; the unknown is a twist applied on the left of
+ * T_volume_rays, in the volume's frame. THE BAND IS THE ONLY OUTLIER RULE: a return further than `band` truncation lengths
+ * from the mapped surface (a moved object, a spurious return) takes no part; there are no per-ray weights and no robust loss.
+ * (system) vk_volume_register's layout: system[0..21) the packed lower triangle of sum J J^T, system[36..42) sum J r,
+ * system[42] sum r^2, the rest 0. A workgroup owns a fixed run of consecutive rays and writes its row of partial sums
+ * whatever it found; one workgroup then adds the rows in a fixed order. The order depends on `count` alone: the same inputs
+ * give the same bytes every call. counts_dev = {valid rays with a measurement, of those with a sample, residuals, invalid
+ * rays}.
+ * (step, state, end of the loop) vk_volume_register's, word for word: state_dev = {steps run, code} zeroed by the caller;
+ * code 1 when |update| < 1e-6; VK_REGISTER_NO_OVERLAP when a step has no residual, which counts as a step, leaves the
+ * pose's bytes alone and writes a zero update; an update of six zeros leaves the pose's bytes alone. A sweep that sees a
+ * single plane gives a rank-deficient system: the library's LDL^T answers that with the zero update, so the loop ends with
+ * code 1 at the pose it had — the caller must judge observability from the scene.
+ * vk_volume_register_rays enqueues `iterations` steps on `stream`, launch per stage (the residual pass, the sum, a one-wave
+ * solve), nothing read back. Nothing waits on another workgroup, there is no float atomic and a chain walk is bounded by
+ * the table size: it cannot hang a device. A stage that finds state_dev[1] != 0 returns at once, so system_dev and
+ * counts_dev hold the last evaluated step's values, those of the pose BEFORE that step's update.
+ * vk_volume_register_rays_system: one evaluation at the pose. vk_volume_register_rays_terms: valid[i], residuals[i] and
+ * jacobians[6i ..] of ray i, zeros where no residual exists; nothing past `count` is written.
+ * workspace: device, vk_volume_register_rays_workspace_bytes(count) bytes (0 for a count the call would refuse), 16-byte
+ * aligned, need not be initialised. */
+/* ref: src/tracker.cpp:124-163 (the loop whose sums this sizes; no upstream counterpart) */
+VK_API size_t vk_volume_register_rays_workspace_bytes(int32_t count);
+/* ref: src/tracer.cu:238-299 (the trilinear sample of every term; no upstream counterpart). rays: device [6*count], origin and
+ * direction; ranges: device [count]; pose_dev: T_volume_rays; residuals [count], jacobians [6*count], valid [count]. */
+VK_API int vk_volume_register_rays_terms(const vk_volume* v, const float* rays, const float* ranges, int32_t count,
+    const vk_transform* pose_dev, const vk_register_rays_params* p, float* residuals, float* jacobians, uint8_t* valid,
+    void* workspace, void* stream);
+/* ref: src/tracker.cpp:124-163 (one evaluation of the loop's system; no upstream counterpart). system_dev [48], counts_dev [4]. */
+VK_API int vk_volume_register_rays_system(const vk_volume* v, const float* rays, const float* ranges, int32_t count,
+    const vk_transform* pose_dev, const vk_register_rays_params* p, float* system_dev, int32_t* counts_dev, void* workspace,
+    void* stream);
+/* ref: src/tracker.cpp:124-163 for the loop and its end, src/color_tracker.cpp:45-95 for the step (no upstream counterpart).
+ * pose_dev in: the start, out: the result; system_dev [48], state_dev [2], counts_dev [4], update_dev optional [6]. */
+VK_API int vk_volume_register_rays(const vk_volume* v, const float* rays, const float* ranges, int32_t count, vk_transform* pose_dev,
+    const vk_register_rays_params* p, float* system_dev, int32_t* state_dev, int32_t* counts_dev, float* update_dev, void* workspace,
+    void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

@@ -137,6 +137,10 @@ _SIGNATURES = {
     "vk_volume_color_rays_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
     "vk_volume_color_rays": ([_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P], _I),
     "vk_volume_color_rays_time_next": ([_P, C.c_int32], _I),
+    "vk_volume_register_rays_workspace_bytes": ([C.c_int32], C.c_size_t),
+    "vk_volume_register_rays_terms": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_register_rays_system": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_register_rays": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -374,10 +378,13 @@ class Frame:
 
 
 class Registration:
-    """what Volume.register returns"""
+    """what Volume.register and Volume.register_rays return. `device_pose` (register_rays; None from register): a device
+    buffer of its own that holds `pose` as a vk_transform — what integrate_rays, carve_rays, color_rays, cast_rays and sample
+    take as `pose` without a copy through the host."""
 
-    def __init__(self, pose, steps, converged, overlap, residuals, rms):
+    def __init__(self, pose, steps, converged, overlap, residuals, rms, device_pose=None):
         self.pose, self.steps, self.converged, self.overlap, self.residuals, self.rms = pose, steps, converged, overlap, residuals, rms
+        self.device_pose = device_pose
 
     def __repr__(self):
         return (f"Registration(steps={self.steps}, converged={self.converged}, overlap={self.overlap}, "
@@ -924,6 +931,86 @@ class Volume:
         if rays.shape[0] == 0:
             return (0,) * 8
         return self._color_rays_call(rays, ranges, colors, pose, flags, r_min, r_max, band, max_color_weight, rays.shape[0])
+
+    _register_rays_buffers = None    # device buffers of vk_volume_register_rays, per ray count
+
+    def _register_rays_setup(self, count, pose, iterations, band, flags, r_min, r_max):
+        """the device buffers of a registration of `count` rays, the start pose uploaded: (buffers, vk_register_rays_params)"""
+        import torch
+        workspace, counts = self._workspace("register_rays", (int(count),), lib().vk_volume_register_rays_workspace_bytes, 4)
+        if self._register_rays_buffers is None or self._register_rays_buffers["workspace"] is not workspace:
+            self._register_rays_buffers = {
+                "workspace": workspace, "counts": counts, "pose": _dev_bytes(C.sizeof(T.Transform), self.device),
+                "system": torch.zeros(48, dtype=torch.float32, device=self.device),
+                "state": torch.zeros(2, dtype=torch.int32, device=self.device),
+                "update": torch.zeros(6, dtype=torch.float32, device=self.device)}
+        b = self._register_rays_buffers
+        check(lib().vk_transform_upload(_ptr(b["pose"]), _ref(pose), stream()), "vk_transform_upload")
+        return b, T.RegisterRaysParams(int(flags), int(iterations), float(r_min), float(r_max), float(band), 0)
+
+    def _register_rays_terms_call(self, rays, ranges, pose, band, flags=0, r_min=0.1, r_max=5.0, count=None, out=None):
+        """vk_volume_register_rays_terms at `pose` (a T.Transform) of `rays` and `ranges` (float32 device tensors of 6 * count and
+        count floats or more): the device buffers (valid uint8 [n], residuals [n], jacobians [n, 6]), allocated here or `out`'s"""
+        import torch
+        count = ranges.numel() if count is None else int(count)
+        b, params = self._register_rays_setup(count, pose, 1, band, flags, r_min, r_max)
+        if out is None:
+            out = (torch.empty(count, dtype=torch.uint8, device=self.device), torch.empty(count, dtype=torch.float32, device=self.device),
+                   torch.empty((count, 6), dtype=torch.float32, device=self.device))
+        check(lib().vk_volume_register_rays_terms(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
+                                                  _ptr(out[1]), _ptr(out[2]), _ptr(out[0]), _ptr(b["workspace"]), stream()),
+              "vk_volume_register_rays_terms")
+        return out
+
+    def _register_rays_system_call(self, rays, ranges, pose, band, flags=0, r_min=0.1, r_max=5.0, count=None):
+        """vk_volume_register_rays_system at `pose`: (system[48], the four counts) from one blocking read each"""
+        count = ranges.numel() if count is None else int(count)
+        b, params = self._register_rays_setup(count, pose, 1, band, flags, r_min, r_max)
+        check(lib().vk_volume_register_rays_system(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
+                                                   _ptr(b["system"]), _ptr(b["counts"]), _ptr(b["workspace"]), stream()),
+              "vk_volume_register_rays_system")
+        return b["system"].cpu().numpy(), _ints(b["counts"])
+
+    def _register_rays_call(self, rays, ranges, pose, iterations, band, flags=0, r_min=0.1, r_max=5.0, count=None):
+        """one vk_volume_register_rays from `pose` (a T.Transform): (pose, (steps, code), counts, system[48], update[6]); the
+        result stays in the buffers' "pose" on the device"""
+        count = ranges.numel() if count is None else int(count)
+        b, params = self._register_rays_setup(count, pose, iterations, band, flags, r_min, r_max)
+        b["state"].zero_()
+        check(lib().vk_volume_register_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
+                                            _ptr(b["system"]), _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]),
+                                            _ptr(b["workspace"]), stream()), "vk_volume_register_rays")
+        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
+        return out, _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy(), b["update"].cpu().numpy()
+
+    def register_rays(self, rays, ranges, pose=None, iterations=20, max_abs_distance=0.75, r_min=None, r_max=None, voxel_units=False):
+        """vk_volume_register_rays (not upstream): where the sensor is — refine the pose T_volume_rays of a sweep of range
+        rays (a LiDAR revolution, a fisheye depth image, a point cloud with known origins) against this volume, by
+        Gauss-Newton on "the endpoint of a return lies on the mapped surface". `rays`, `ranges`, `r_min`, `r_max` and
+        `voxel_units` are integrate_rays'. `pose` (a 4x4 array or a Transform; None: the identity) is the guess to start from:
+        it has to bring the endpoints within roughly a truncation length of the surface — this call refines, it does not
+        search. A return whose endpoint samples a distance of `max_abs_distance` truncation lengths or more (a moved object,
+        a spurious return), or lies where the map holds nothing, takes no part: that band is the only outlier rule. A sweep
+        that sees a single plane does not fix the pose: the step is then zero and the call reports convergence where it
+        started. The volume is only read, so the call is allowed while a frame is announced. At most `iterations` steps
+        (1 .. 64), all enqueued at once; one blocking read at the end. Returns a Registration: `pose`, and `device_pose`,
+        the same on the device for integrate_rays(pose=...); `steps`, `converged`, `overlap` (False: a step found no return
+        to compare and the pose is the one it had then), `residuals` and `rms` (in truncation lengths) of the last evaluated
+        step."""
+        rays = _float_tensor(rays, 6, "register_rays: rays is a float32 [N, 6] device tensor")
+        ranges = _float_tensor(ranges, None, "register_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        start = _as_pose(pose, identity=True)
+        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
+        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
+        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
+        flags = T.VK_RAYS_VOXEL_UNITS if voxel_units else 0
+        if rays.shape[0] == 0:
+            return Registration(start, 0, False, False, 0, 0.0, self._pose_on_device(start).clone())
+        out, state, counts, system, _ = self._register_rays_call(rays, ranges, start, iterations, max_abs_distance, flags, r_min, r_max,
+                                                                 rays.shape[0])
+        return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
+                            float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0,
+                            self._register_rays_buffers["pose"].clone())
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

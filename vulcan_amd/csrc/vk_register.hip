@@ -13,9 +13,10 @@
 //             The workgroup's 27 + 3 sums go to its own row of partials (store_partial): a row per workgroup whatever
 //             it found, so the rows and their order depend on the source's table alone
 //   sum       one workgroup: sum_partials' fixed order into system[48], the integer counts
-//   solve     one wave: staged_pose_step<6, -1> and rigid_from, as color_solve_kernel
+//   solve     one wave: staged_pose_step<6, -1> and rigid_from, as color_solve_kernel (register_solve_kernel,
+//             vk_register_step.hpp, shared with vk_register_rays.hip)
 #include "vk_block_walk.hpp"
-#include "vk_gauss_newton.hpp"
+#include "vk_register_step.hpp"
 
 using namespace vk;
 
@@ -204,37 +205,6 @@ __global__ __launch_bounds__(256) void register_sum_kernel(const float* __restri
     counts[2] = totals[1];
     counts[3] = 0;
   }
-}
-
-// One wave: the colour trackers' step on T_dst_src itself. M = Tinc(update) * m, pose <- rigid_from(M).
-__global__ __launch_bounds__(64) void register_solve_kernel(const float* __restrict__ system, const int32_t* __restrict__ counts,
-    vk_transform* pose, int32_t* state, float* update_out)
-{
-  if (state[1]) return;
-  if (counts[2] == 0)
-  {
-    if (threadIdx.x == 0)
-    {
-      state[0] += 1;
-      state[1] = VK_REGISTER_NO_OVERLAP;
-      if (update_out)
-        for (int i = 0; i < 6; ++i) update_out[i] = 0.0f;
-    }
-    return;
-  }
-  float update[6], M[16], out_m[16], out_i[16];
-  staged_pose_step<6, -1>(system, system + 36, pose->m, M, update);
-  if (threadIdx.x != 0) return;
-  bool moves = false;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) moves = moves || update[i] != 0.0f;
-  if (moves)                                      // a zero update (no gradient, or a rank-deficient system) leaves the bytes alone
-  {
-    rigid_from(M, out_m, out_i);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { pose->m[i] = out_m[i]; pose->inv[i] = out_i[i]; }
-  }
-  finish_step<6>(update, state, update_out);
 }
 
 inline int groups_of(int src_total) { return (src_total + kWavesPerGroup - 1) / kWavesPerGroup; }

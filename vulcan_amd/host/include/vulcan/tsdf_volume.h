@@ -89,14 +89,14 @@ struct MergePoseCounts
   int sampled;          // voxels that took a distance sample
 };
 
-// Volume::Register (vk_volume_register)
+// Volume::Register (vk_volume_register) and Volume::RegisterRays (vk_volume_register_rays)
 struct Registration
 {
-  Transform pose;       // Tdst_src after the last step: what Merge(other, pose) takes
+  Transform pose;       // Tdst_src after the last step: what Merge(other, pose) takes; RegisterRays: Tvolume_rays, IntegrateRays' pose
   int steps;            // Gauss-Newton steps run
   bool converged;       // the last step was shorter than 1e-6
-  bool overlap;         // false: a step found no voxel to compare; the pose is the one it had then
-  int residuals;        // voxels compared in the last evaluated step
+  bool overlap;         // false: a step found no voxel (no return) to compare; the pose is the one it had then
+  int residuals;        // voxels (returns) compared in the last evaluated step
   float rms;            // sqrt(sum r^2 / residuals) of that step, in truncation lengths
 };
 
@@ -195,6 +195,17 @@ struct ColorRaysCounts
   int voxels;           // voxels updated
   int not_near;         // voxels visited whose stored distance is not near a surface: left alone
   unsigned lost;        // cell visits lost to a block that does not exist
+};
+
+// Not upstream: how Volume::RegisterRays reads its rays and ranges and which returns take part (vk_register_rays_params)
+struct RegisterRaysOptions
+{
+  bool voxel_units = false;           // the origins, the ranges, r_min and r_max are in voxels, not metres
+  int iterations = 20;                // 1 .. 64 Gauss-Newton steps at most, enqueued at once
+  float r_min = 0.1f;                 // IntegrateRays' rule: a ray whose range lies outside [r_min, r_max] carries no
+  float r_max = 5.0f;                 //   measurement and takes no part
+  float max_abs_distance = 0.75f;     // the band, in truncation lengths: a return that samples a distance this far from the
+                                      //   mapped surface (a moved object, a spurious return) takes no part; the only outlier rule
 };
 
 class Block;
@@ -332,6 +343,18 @@ class Volume
     ColorRaysCounts ColorRays(const Ray* rays_dev, const float* ranges_dev, const Vector3f* colors_dev, int count,
         const Transform* pose = nullptr, const ColorRaysOptions& options = ColorRaysOptions());
 
+    // Not upstream: where the sensor is (vk_volume_register_rays) — refine the pose Tvolume_rays of a sweep of `count` range
+    // rays, the pose IntegrateRays, CarveRays and ColorRays take as given, by Gauss-Newton on "the endpoint of a return lies
+    // on the mapped surface": every measured ray's endpoint is carried into the volume through `start` (then the refined
+    // pose) and the trilinear sample there is driven to 0. Rays and ranges are IntegrateRays'. `start` has to bring the
+    // endpoints within roughly a truncation length of the surface: the call refines a guess, it does not search, and a
+    // sweep that sees a single plane does not fix the pose (the step is then zero and the call reports convergence where
+    // it started). The volume is only read and the call writes nothing of it: like Sample and CastRays it is allowed while
+    // a frame announced by Tracer::Trace(keyframe, next_frame) is outstanding. Both buffers are device memory and only
+    // read. All steps are enqueued at once on Device::GetStream(); blocking readbacks at the end; count == 0 does nothing.
+    Registration RegisterRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform& start,
+        const RegisterRaysOptions& options = RegisterRaysOptions()) const;
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -403,6 +426,9 @@ class Volume
     Buffer<int> carve_counts_;
     Buffer<unsigned char> color_rays_workspace_;   // ColorRays: allocated by the first call
     Buffer<int> color_rays_counts_;
+    mutable Buffer<unsigned char> register_rays_workspace_;   // RegisterRays: again for another number of rays
+    mutable Buffer<float> register_rays_floats_;              // the pose (32), the system (48), the update (6)
+    mutable Buffer<int> register_rays_ints_;                  // the state (2), the counts (4)
 
     Vector2f depth_range_;
     int max_block_count_;

@@ -644,6 +644,54 @@ ColorRaysCounts Volume::ColorRays(const Ray* rays_dev, const float* ranges_dev, 
   return out;
 }
 
+Registration Volume::RegisterRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform& start,
+    const RegisterRaysOptions& options) const
+{
+  static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
+  // the volume is only read: allowed while a frame is announced, like Sample and CastRays
+  vk_register_rays_params p;
+  p.flags = options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0;
+  p.iterations = options.iterations;
+  p.r_min = options.r_min;
+  p.r_max = options.r_max;
+  p.max_abs_distance = options.max_abs_distance;
+  p.pad = 0;
+  const size_t bytes = vk_volume_register_rays_workspace_bytes(count);
+  if (bytes != 0 && register_rays_workspace_.GetSize() != bytes) register_rays_workspace_.Resize(bytes);
+  if (register_rays_floats_.GetSize() == 0) register_rays_floats_.Resize(32 + 48 + 8);
+  if (register_rays_ints_.GetSize() == 0) register_rays_ints_.Resize(2 + 4);
+  vk_transform* pose = reinterpret_cast<vk_transform*>(register_rays_floats_.GetData());
+  float* system = register_rays_floats_.GetData() + 32;
+  float* update = system + 48;
+  int* state = register_rays_ints_.GetData();
+  int* counts = state + 2;
+  Registration out = {};
+  out.pose = start;
+  const vk_transform seed = start.ToVk();
+  const vk_volume v = ToVk();
+  if (count > 0)                                   // no rays: no upload
+  {
+    VK_ASSERT(vk_transform_upload(pose, &seed, Device::GetStream()));
+    VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
+  }
+  VK_ASSERT(vk_volume_register_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose, &p, system, state, counts, update,
+      register_rays_workspace_.GetData(), Device::GetStream()));
+  if (count == 0) return out;                      // nothing was launched and nothing was written
+  std::vector<float> floats(register_rays_floats_.GetSize());
+  std::vector<int> ints(register_rays_ints_.GetSize());
+  register_rays_floats_.CopyToHost(floats.data());
+  register_rays_ints_.CopyToHost(ints.data());
+  vk_transform result;
+  std::memcpy(&result, floats.data(), sizeof(result));
+  out.pose = Transform::FromVk(result);
+  out.steps = ints[0];
+  out.converged = ints[1] == 1;
+  out.overlap = ints[1] != VK_REGISTER_NO_OVERLAP;
+  out.residuals = ints[4];
+  out.rms = ints[4] > 0 ? std::sqrt(floats[32 + 42] / float(ints[4])) : 0.0f;
+  return out;
+}
+
 void Volume::ResetBlockVisibility()
 {
   AssertNoFrameAnnounced();

@@ -257,6 +257,13 @@ class ColorRaysParams(C.Structure):
                 ("max_color_weight", C.c_float), ("pad", C.c_int32)]
 
 
+class RegisterRaysParams(C.Structure):
+    """vk_register_rays_params (vk.h): the units of vk_volume_register_rays' origins and ranges, the steps, which ranges are
+    measurements and the band, in truncation lengths, outside which a return takes no part"""
+    _fields_ = [("flags", C.c_int32), ("iterations", C.c_int32), ("r_min", C.c_float), ("r_max", C.c_float),
+                ("max_abs_distance", C.c_float), ("pad", C.c_int32)]
+
+
 class PyramidAhead(C.Structure):
     """vk_pyramid_ahead (vk.h): ABI 7's record of the retired pyramid ride; the library leaves it invalid"""
     _fields_ = [("key_depths", C.c_void_p), ("key_normals", C.c_void_p), ("frame_depths", C.c_void_p), ("frame_normals", C.c_void_p),
