@@ -1840,6 +1840,71 @@ VK_API int vk_volume_register_rays(const vk_volume* v, const float* rays, const 
     const vk_register_rays_params* p, float* system_dev, int32_t* state_dev, int32_t* counts_dev, float* update_dev, void* workspace,
     void* stream);
 
+/* ------------------------------------------------------------- score poses -- */
+
+typedef struct vk_score_poses_params {
+  int32_t flags;             /* VK_RAYS_VOXEL_UNITS; any other bit VK_ERR_ARGUMENT */
+  int32_t min_residuals;     /* >= 1: vk_volume_score_poses_best names no pose with fewer */
+  float   r_min, r_max;      /* a ray has a measurement iff r_min <= range <= r_max (vk_volume_integrate_rays' rule) */
+  float   max_abs_distance;  /* band, in truncation lengths: 0 < band <= 1 */
+  int32_t pad;
+} vk_score_poses_params;     /* 24 bytes */
+
+typedef struct vk_pose_score {
+  int32_t measured, sampled, residuals, invalid;  /* vk_volume_register_rays' four counts at this pose */
+  int64_t sum_abs;           /* sum over residuals of (int64) rintf(fabsf(D) * 1048576.0f) */
+  int64_t sum_squares;       /* sum over residuals of (int64) rintf((D * D) * 1048576.0f) */
+} vk_pose_score;             /* 32 bytes */
+
+/* Score many candidate poses T_volume_rays for one sweep of range rays, and name the one that explains the sweep best: the
+ * start vk_volume_register_rays needs and cannot find — a sensor switched on somewhere in a known map, a tracker that lost
+ * its pose, a loop-closure candidate to verify. It evaluates vk_volume_register_rays' residual test at every (pose, ray)
+ * pair; producing the candidates (a grid, a sampler) is the caller's. No upstream counterpart (the reference tracks pinhole
+ * depth images against a raycast keyframe); ref: src/tracker.cpp:124-163 for the loop whose start this finds,
+ * src/color_tracker.cpp:45-95 for the step, src/tracer.cu:238-299 for the trilinear sample. The definition is this comment;
+ * tests/score_poses_reference.py states it on the CPU. The float arithmetic is vk_volume_register_rays'.
+ * ACCESS: the volume, rays, ranges and poses are only read: the calls may run while a frame is announced, like
+ * vk_volume_sample and vk_volume_register_rays.
+ * HOST CHECKS (VK_ERR_ARGUMENT, nothing enqueued): vk_volume_register_rays' (v, p, poses_dev, scores_dev or the workspace
+ * null, a volume that vk_volume_sample would refuse, a flag other than VK_RAYS_VOXEL_UNITS, the band not in (0, 1], r_min or
+ * r_max not finite or not 0 <= r_min < r_max, count < 0 or count > 1 << 22, rays or ranges null with count > 0, a workspace
+ * not 16-byte aligned), and pose_count outside 1 .. 65 536, (int64) count * pose_count > 1 << 28 (one call stays bounded on
+ * a shared machine), min_residuals < 1. count == 0 returns 0, launches nothing and leaves every output's bytes alone.
+ * (pair) for pose k and ray i the terms are vk_volume_register_rays' word for word with poses_dev[k] as T_volume_rays: the
+ * ray, its INVALID rule and its measurement test, the endpoint, the sample, and the residual test fabsf(D) < band. D is the
+ * very float32 vk_volume_register_rays_terms writes to residuals[i] at that pose. No Jacobian, no gradient.
+ * (score) scores_dev[k] = {valid rays with a measurement, of those with a sample, residuals, invalid rays} — what
+ * vk_volume_register_rays_system writes to counts_dev at that pose — and, over the residuals, sum_abs and sum_squares as
+ * written at vk_pose_score: float32 products (the one with 2^20 is exact), rintf, then INTEGER sums. They commute, so a score
+ * does not depend on how pairs are dealt to lanes, waves and workgroups, or on timing: the same inputs give the same bytes,
+ * and permuted rays give the same score. A term is <= 2^20, a wave's sum <= 2^26, a pose's <= 2^42. The mean |D| of pose k
+ * is sum_abs / 2^20 / residuals and its rms sqrtf(sum_squares / 2^20 / residuals), in truncation lengths, each term within
+ * half a unit (2^-21).
+ * (shape) a workgroup owns 256 consecutive rays x 8 consecutive poses, one lane per ray looping over the poses, and writes
+ * its partial scores whatever it found; a second launch adds them per pose. Nothing waits on another workgroup, there is no
+ * atomic and a chain walk is bounded by the table size: it cannot hang a device. Every vk_pose_score up to pose_count is
+ * written, nothing beyond; scores_dev needs no initial contents.
+ * workspace: device, vk_volume_score_poses_workspace_bytes(count, pose_count) bytes (0 for a shape the call would refuse),
+ * 16-byte aligned, need not be initialised.
+ * vk_volume_score_poses_best: one small launch. The best pose is the one with the most residuals, then the smallest
+ * sum_abs, then the smallest index: a total order. If it has residuals >= p->min_residuals, best_dev[0] = its index k and
+ * poses_dev[k]'s 128 bytes are copied to pose_out_dev; otherwise best_dev[0] = -1 and pose_out_dev's bytes are left alone.
+ * vk_volume_register_rays can be enqueued from pose_out_dev right behind it: score, choose, refine is one enqueue with no
+ * host round trip (after a -1 it refines whatever pose_out_dev held: read best_dev before trusting the result). HOST CHECKS:
+ * a null pointer, pose_count outside 1 .. 65 536, a flag other than VK_RAYS_VOXEL_UNITS, min_residuals < 1; the rest of p
+ * is not used. */
+/* ref: src/tracker.cpp:124-163 (the loop whose candidate starts this sizes; no upstream counterpart) */
+VK_API size_t vk_volume_score_poses_workspace_bytes(int32_t count, int32_t pose_count);
+/* ref: src/tracer.cu:238-299 (the trilinear sample of every pair; no upstream counterpart). rays: device [6*count], origin and
+ * direction; ranges: device [count]; poses_dev: device [pose_count] T_volume_rays; scores_dev: device [pose_count]. */
+VK_API int vk_volume_score_poses(const vk_volume* v, const float* rays, const float* ranges, int32_t count,
+    const vk_transform* poses_dev, int32_t pose_count, const vk_score_poses_params* p, vk_pose_score* scores_dev, void* workspace,
+    void* stream);
+/* ref: src/tracker.cpp:124-163 (the loop this chooses the start of; no upstream counterpart). best_dev: device int32[1];
+ * pose_out_dev: device vk_transform. */
+VK_API int vk_volume_score_poses_best(const vk_pose_score* scores_dev, const vk_transform* poses_dev, int32_t pose_count,
+    const vk_score_poses_params* p, int32_t* best_dev, vk_transform* pose_out_dev, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

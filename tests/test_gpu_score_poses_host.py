@@ -1,0 +1,22 @@
+"""Volume::ScorePoses and Volume::LocalizeRays through the C++ class layer:
+vulcan_amd/host/tests/score_poses_tests.cpp, run as test_gpu_register_rays_host.py runs register_rays_tests."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "vulcan_amd", "host", "bin")
+
+
+@pytest.mark.gpu
+def test_cpp_score_poses_tests_pass():
+    exe = os.path.join(BIN, "score_poses_tests")
+    assert os.path.exists(exe), "run __graft_entry__.build() first"
+    proc = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    print(proc.stdout)
+    assert proc.returncode == 0, proc.stdout[-4000:]
+    assert re.search(r"3 test\(s\), 0 failed", proc.stdout)
+    for name in ("ScorePoses.ASweepFromFarAwayIsLocalisedThenFused", "ScorePoses.NoRaysAreNoCall", "ScorePoses.AllowedWhileAFrameIsAnnounced"):
+        assert f"[  OK  ] {name}" in proc.stdout

@@ -141,6 +141,9 @@ _SIGNATURES = {
     "vk_volume_register_rays_terms": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_register_rays_system": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_register_rays": ([_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_score_poses_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
+    "vk_volume_score_poses": ([_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P], _I),
+    "vk_volume_score_poses_best": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -389,6 +392,55 @@ class Registration:
     def __repr__(self):
         return (f"Registration(steps={self.steps}, converged={self.converged}, overlap={self.overlap}, "
                 f"residuals={self.residuals}, rms={self.rms:.3g})")
+
+
+class PoseScores:
+    """what Volume.score_poses returns: `scores`, the device buffer of vk_pose_score vk_volume_score_poses wrote, and `poses`,
+    the device buffer of the `count` candidate vk_transforms it scored. Nothing is read until host() is called."""
+
+    def __init__(self, scores, poses, count, device):
+        self.scores, self.poses, self.count, self.device = scores, poses, int(count), device
+        self._host = None
+
+    def __len__(self):
+        return self.count
+
+    def host(self):
+        """the scores as a structured array (vk_types.pose_score_dtype): one blocking read, kept"""
+        if self._host is None:
+            self._host = to_numpy(self.scores[:self.count * T.pose_score_dtype.itemsize], T.pose_score_dtype)
+        return self._host
+
+    def _per_residual(self, field):
+        h = self.host()
+        return np.where(h["residuals"] > 0, h[field] / 1048576.0 / np.maximum(h["residuals"], 1), 0.0)
+
+    @property
+    def mean_abs(self):
+        """per pose, the mean |D| over its residuals in truncation lengths (0 where there is none)"""
+        return self._per_residual("sum_abs")
+
+    @property
+    def rms(self):
+        """per pose, the root of the mean D^2 over its residuals in truncation lengths (0 where there is none)"""
+        return np.sqrt(self._per_residual("sum_squares"))
+
+    def _best_call(self, min_residuals, best, pose_out):
+        params = T.ScorePosesParams(0, int(min_residuals), 0.0, 0.0, 0.0, 0)
+        check(lib().vk_volume_score_poses_best(_ptr(self.scores), _ptr(self.poses), self.count, _ref(params), _ptr(best), _ptr(pose_out),
+                                               stream()), "vk_volume_score_poses_best")
+
+    def best(self, min_residuals=1):
+        """vk_volume_score_poses_best: (index, device_pose) of the pose with the most residuals, then the smallest sum of |D|,
+        then the smallest index — `device_pose` a device buffer of its own that holds that vk_transform, what register_rays,
+        integrate_rays and the other ray operations take as `pose` — or (-1, None) when that pose has fewer than
+        `min_residuals` residuals. One blocking read of the index."""
+        import torch
+        best = torch.zeros(1, dtype=torch.int32, device=self.device)
+        pose_out = _dev_bytes(C.sizeof(T.Transform), self.device)
+        self._best_call(min_residuals, best, pose_out)
+        index = int(best.cpu()[0])
+        return (index, pose_out) if index >= 0 else (-1, None)
 
 
 class Samples:
@@ -1011,6 +1063,96 @@ class Volume:
         return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
                             float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0,
                             self._register_rays_buffers["pose"].clone())
+
+    def _poses_on_device(self, poses, what):
+        """(device buffer of vk_transforms, how many): `poses` a sequence of T.Transform (or 4x4 arrays), uploaded, or a device
+        tensor that holds whole vk_transforms, passed through"""
+        import torch
+        if hasattr(poses, "data_ptr"):
+            size = poses.numel() * poses.element_size()
+            if size == 0 or size % C.sizeof(T.Transform) or not poses.is_contiguous():
+                raise VkError(f"{what}: poses is a contiguous device tensor of whole vk_transforms (128 bytes each)")
+            return poses, size // C.sizeof(T.Transform)
+        host = b"".join(bytes(_as_pose(pose)) for pose in poses)
+        if not host:
+            raise VkError(f"{what}: no pose to score")
+        return torch.from_numpy(np.frombuffer(host, dtype=np.uint8).copy()).to(self.device), len(host) // C.sizeof(T.Transform)
+
+    def _score_poses_call(self, rays, ranges, poses, pose_count, band, flags=0, r_min=0.1, r_max=5.0, count=None, scores=None,
+                          workspace=None):
+        """vk_volume_score_poses of `rays` and `ranges` (float32 device tensors of 6 * count and count floats or more) at the
+        `pose_count` vk_transforms of the device buffer `poses`: the device buffer of scores, allocated here or `scores`"""
+        count = ranges.numel() if count is None else int(count)
+        if workspace is None:
+            workspace, _ = self._workspace("score_poses", (count, int(pose_count)), lib().vk_volume_score_poses_workspace_bytes, 1)
+        if scores is None:
+            scores = _dev_bytes(int(pose_count) * C.sizeof(T.PoseScore), self.device)
+        params = T.ScorePosesParams(int(flags), 1, float(r_min), float(r_max), float(band), 0)
+        check(lib().vk_volume_score_poses(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(poses), int(pose_count), _ref(params),
+                                          _ptr(scores), _ptr(workspace), stream()), "vk_volume_score_poses")
+        return scores
+
+    def _score_poses_arguments(self, what, rays, ranges, poses, r_min, r_max, voxel_units):
+        rays = _float_tensor(rays, 6, f"{what}: rays is a float32 [N, 6] device tensor")
+        ranges = _float_tensor(ranges, None, f"{what}: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        poses, pose_count = self._poses_on_device(poses, what)
+        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
+        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
+        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
+        return rays, ranges, poses, pose_count, r_min, r_max, T.VK_RAYS_VOXEL_UNITS if voxel_units else 0
+
+    def score_poses(self, rays, ranges, poses, max_abs_distance=0.75, r_min=None, r_max=None, voxel_units=False):
+        """vk_volume_score_poses (not upstream): how well each of many candidate poses T_volume_rays explains a sweep of range
+        rays — the search register_rays does not make. `rays`, `ranges`, `r_min`, `r_max` and `voxel_units` are
+        integrate_rays'; `poses` is a sequence of Transforms (or 4x4 arrays), or a device tensor of vk_transforms; producing
+        the candidates is the caller's. At every pose, every ray is put to register_rays' residual test (a measured return
+        whose endpoint samples a distance below `max_abs_distance` truncation lengths where the map holds all eight
+        voxels): the score is register_rays' four counts at that pose and the sums of |D| and D^2 over the residuals as
+        integers in units of 2^-20, so it does not depend on the order of the rays or on timing. At most 65 536 poses,
+        1 << 22 rays and 1 << 28 pairs a call. The volume is only read, so the call is allowed while a frame is announced;
+        nothing is read back. Returns a PoseScores: host(), mean_abs, rms, best(min_residuals)."""
+        rays, ranges, poses, pose_count, r_min, r_max, flags = self._score_poses_arguments("score_poses", rays, ranges, poses, r_min,
+                                                                                          r_max, voxel_units)
+        import torch
+        if rays.shape[0] == 0:          # no rays are no call: every pose scores nothing
+            return PoseScores(torch.zeros(pose_count * C.sizeof(T.PoseScore), dtype=torch.uint8, device=self.device), poses, pose_count,
+                              self.device)
+        scores = self._score_poses_call(rays, ranges, poses, pose_count, max_abs_distance, flags, r_min, r_max, rays.shape[0])
+        return PoseScores(scores, poses, pose_count, self.device)
+
+    def localize_rays(self, rays, ranges, poses, min_residuals=None, iterations=20, max_abs_distance=0.75, r_min=None, r_max=None,
+                      voxel_units=False):
+        """where the sensor is, from far away: score_poses at the candidates `poses`, the best of them chosen on the device,
+        and register_rays from it — three calls enqueued before anything is read. Returns register_rays' Registration with
+        `best_index`, the candidate the refinement started from. Raises VkError when no candidate reaches `min_residuals`
+        residuals (None: half the rays whose range is a measurement, counted with one read before the enqueue), or when there
+        is no ray. `result.scores` is the PoseScores of the candidates."""
+        rays, ranges, poses, pose_count, r_min, r_max, flags = self._score_poses_arguments("localize_rays", rays, ranges, poses, r_min,
+                                                                                          r_max, voxel_units)
+        import torch
+        count = rays.shape[0]
+        if count == 0:
+            raise VkError("localize_rays: no rays")
+        if min_residuals is None:       # half the measured rays: the measurement test does not depend on the pose
+            min_residuals = max(1, int(((ranges >= r_min) & (ranges <= r_max)).sum()) // 2)
+        b, params = self._register_rays_setup(count, T.Transform.identity(), iterations, max_abs_distance, flags, r_min, r_max)
+        b["state"].zero_()
+        best = torch.zeros(1, dtype=torch.int32, device=self.device)
+        scored = PoseScores(self._score_poses_call(rays, ranges, poses, pose_count, max_abs_distance, flags, r_min, r_max, count), poses,
+                            pose_count, self.device)
+        scored._best_call(min_residuals, best, b["pose"])
+        check(lib().vk_volume_register_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
+                                            _ptr(b["system"]), _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]),
+                                            _ptr(b["workspace"]), stream()), "vk_volume_register_rays")
+        index = int(best.cpu()[0])
+        if index < 0:
+            raise VkError(f"localize_rays: none of the {pose_count} candidates has {min_residuals} residuals")
+        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
+        state, counts, system = _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy()
+        result = Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
+                              float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0, b["pose"].clone())
+        result.best_index, result.scores = index, scored
+        return result
 
     def _no_requests_pending(self, stage):
         # the staged SetView stages on top of an announced frame's requests would mix two frames' state (vk.h)

@@ -12,7 +12,9 @@
 //     GetVisibleBlocks() after it (volume.cu:494 synchronised every frame).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
+#include <vector>
 #include <vk.h>
 #include <vulcan/buffer.h>
 #include <vulcan/matrix.h>
@@ -208,6 +210,35 @@ struct RegisterRaysOptions
                                       //   mapped surface (a moved object, a spurious return) takes no part; the only outlier rule
 };
 
+// Not upstream: how Volume::ScorePoses and Volume::LocalizeRays read their rays and ranges and which returns count
+// (vk_score_poses_params)
+struct ScorePosesOptions
+{
+  bool voxel_units = false;           // the origins, the ranges, r_min and r_max are in voxels, not metres
+  float r_min = 0.1f;                 // IntegrateRays' rule: a ray whose range lies outside [r_min, r_max] carries no
+  float r_max = 5.0f;                 //   measurement and takes no part
+  float max_abs_distance = 0.75f;     // the band, in truncation lengths: RegisterRays' residual test
+};
+
+// Volume::ScorePoses: how well one candidate pose explains a sweep (vk_pose_score)
+struct PoseScore
+{
+  int measured;           // valid rays with a measurement
+  int sampled;            // of those, endpoints where the map holds all eight voxels
+  int residuals;          // of those, |D| below the band: what RegisterRays would compare at this pose
+  int invalid;            // invalid rays
+  long long sum_abs;      // sum of rint(|D| * 2^20) over the residuals: integers, so the order of the rays does not matter
+  long long sum_squares;  // sum of rint(D * D * 2^20)
+  double MeanAbs() const { return residuals > 0 ? double(sum_abs) / 1048576.0 / residuals : 0.0; }      // truncation lengths
+  double Rms() const { return residuals > 0 ? std::sqrt(double(sum_squares) / 1048576.0 / residuals) : 0.0; }
+};
+
+// Volume::LocalizeRays: RegisterRays' result and the candidate it started from
+struct Localization : Registration
+{
+  int best_index;         // -1: no candidate reached min_residuals; nothing was refined and `pose` is the identity
+};
+
 class Block;
 struct Frame;
 class HashEntry;
@@ -355,6 +386,22 @@ class Volume
     Registration RegisterRays(const Ray* rays_dev, const float* ranges_dev, int count, const Transform& start,
         const RegisterRaysOptions& options = RegisterRaysOptions()) const;
 
+    // Not upstream: how well each of many candidate poses Tvolume_rays explains a sweep (vk_volume_score_poses) — the search
+    // RegisterRays does not make: a sensor switched on somewhere in a known map, a tracker that lost its pose, a loop closure
+    // to verify. Every ray is put to RegisterRays' residual test at every pose; producing the candidates is the caller's.
+    // At most 65 536 poses, 1 << 22 rays and 1 << 28 pairs a call. The volume is only read: allowed while a frame is
+    // announced. One blocking readback (the scores); count == 0 does nothing and gives scores of zeros.
+    std::vector<PoseScore> ScorePoses(const Ray* rays_dev, const float* ranges_dev, int count, const std::vector<Transform>& poses,
+        const ScorePosesOptions& options = ScorePosesOptions()) const;
+
+    // Not upstream: where the sensor is, from far away — ScorePoses at `poses`, the best of them chosen on the device (the
+    // most residuals, then the smallest sum of |D|, then the smallest index: vk_volume_score_poses_best) and RegisterRays
+    // from it, all enqueued before anything is read. A best candidate with fewer than `min_residuals` (>= 1) residuals is
+    // none: best_index is -1 and nothing is refined. Rays, ranges and options are RegisterRays'. Allowed while a frame is
+    // announced; count == 0 does nothing (best_index -1).
+    Localization LocalizeRays(const Ray* rays_dev, const float* ranges_dev, int count, const std::vector<Transform>& poses,
+        int min_residuals, const RegisterRaysOptions& options = RegisterRaysOptions()) const;
+
     // Raycast bounds prepared ahead of time (vk_view_bounds, not upstream): a Tracer
     // registers its scratch buffer and settings here, the integrators then compute
     // the bounds of the view they integrate inside their own launch and
@@ -429,6 +476,10 @@ class Volume
     mutable Buffer<unsigned char> register_rays_workspace_;   // RegisterRays: again for another number of rays
     mutable Buffer<float> register_rays_floats_;              // the pose (32), the system (48), the update (6)
     mutable Buffer<int> register_rays_ints_;                  // the state (2), the counts (4)
+    mutable Buffer<unsigned char> score_poses_workspace_;     // ScorePoses: again for another number of rays or poses
+    mutable Buffer<unsigned char> score_poses_scores_;        // [poses] vk_pose_score
+    mutable Buffer<float> score_poses_poses_;                 // [poses] vk_transform
+    mutable Buffer<int> score_poses_best_;                    // LocalizeRays: the chosen index (1)
 
     Vector2f depth_range_;
     int max_block_count_;
@@ -453,6 +504,7 @@ class Volume
     // what the volume operations above share on the caller's side
     void AssertNoFrameAnnounced() const;                               // between SetView calls only
     const vk_transform* PoseOnDevice(const Transform* pose) const;     // uploaded into sample_pose_; null stays null
+    int ScorePosesBuffers(int count, const std::vector<Transform>& poses) const;    // the candidates uploaded: how many
     void VoidMadeAhead() const;                 // the raycast bounds and the light preparation made for the old table
     void EmptyVisibleList() const;              // VK_CTR_VISIBLE is 0 until the next SetView
     // both Merge overloads: `call(dst, src, counts_dev, workspace)` is the library call with `merge` among its parameters,

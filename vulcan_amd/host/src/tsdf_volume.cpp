@@ -508,6 +508,118 @@ Registration Volume::Register(const Volume& other, const Transform& start, int i
   return out;
 }
 
+// the candidates on the device, and the scores and the workspace sized for them: how many poses there are
+int Volume::ScorePosesBuffers(int count, const std::vector<Transform>& poses) const
+{
+  static_assert(sizeof(vk_transform) == 32 * sizeof(float), "vk_transform layout");
+  const int pose_count = int(poses.size());
+  const size_t bytes = vk_volume_score_poses_workspace_bytes(count, pose_count);
+  if (bytes != 0 && score_poses_workspace_.GetSize() != bytes) score_poses_workspace_.Resize(bytes);
+  if (pose_count > 0 && score_poses_scores_.GetSize() != poses.size() * sizeof(vk_pose_score))
+  {
+    score_poses_scores_.Resize(poses.size() * sizeof(vk_pose_score));
+    score_poses_poses_.Resize(poses.size() * 32);
+  }
+  if (count > 0 && pose_count > 0)                 // no rays: no upload
+  {
+    std::vector<vk_transform> host(poses.size());
+    for (size_t k = 0; k < poses.size(); ++k) host[k] = poses[k].ToVk();
+    score_poses_poses_.CopyFromHost(reinterpret_cast<const float*>(host.data()));
+  }
+  return pose_count;
+}
+
+std::vector<PoseScore> Volume::ScorePoses(const Ray* rays_dev, const float* ranges_dev, int count, const std::vector<Transform>& poses,
+    const ScorePosesOptions& options) const
+{
+  static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
+  // the volume is only read: allowed while a frame is announced, like Sample and RegisterRays
+  vk_score_poses_params p;
+  p.flags = options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0;
+  p.min_residuals = 1;
+  p.r_min = options.r_min;
+  p.r_max = options.r_max;
+  p.max_abs_distance = options.max_abs_distance;
+  p.pad = 0;
+  const int pose_count = ScorePosesBuffers(count, poses);
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_score_poses(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count,
+      reinterpret_cast<const vk_transform*>(score_poses_poses_.GetData()), pose_count, &p,
+      reinterpret_cast<vk_pose_score*>(score_poses_scores_.GetData()), score_poses_workspace_.GetData(), Device::GetStream()));
+  std::vector<PoseScore> out(poses.size(), PoseScore{0, 0, 0, 0, 0, 0});
+  if (count == 0) return out;                      // nothing was launched and nothing was written
+  std::vector<vk_pose_score> scores(poses.size());
+  score_poses_scores_.CopyToHost(reinterpret_cast<unsigned char*>(scores.data()));
+  for (size_t k = 0; k < poses.size(); ++k)
+    out[k] = PoseScore{scores[k].measured, scores[k].sampled, scores[k].residuals, scores[k].invalid, (long long)scores[k].sum_abs,
+        (long long)scores[k].sum_squares};
+  return out;
+}
+
+Localization Volume::LocalizeRays(const Ray* rays_dev, const float* ranges_dev, int count, const std::vector<Transform>& poses,
+    int min_residuals, const RegisterRaysOptions& options) const
+{
+  vk_score_poses_params sp;
+  sp.flags = options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0;
+  sp.min_residuals = min_residuals;
+  sp.r_min = options.r_min;
+  sp.r_max = options.r_max;
+  sp.max_abs_distance = options.max_abs_distance;
+  sp.pad = 0;
+  vk_register_rays_params p;
+  p.flags = sp.flags;
+  p.iterations = options.iterations;
+  p.r_min = options.r_min;
+  p.r_max = options.r_max;
+  p.max_abs_distance = options.max_abs_distance;
+  p.pad = 0;
+  const int pose_count = ScorePosesBuffers(count, poses);
+  const size_t bytes = vk_volume_register_rays_workspace_bytes(count);
+  if (bytes != 0 && register_rays_workspace_.GetSize() != bytes) register_rays_workspace_.Resize(bytes);
+  if (register_rays_floats_.GetSize() == 0) register_rays_floats_.Resize(32 + 48 + 8);
+  if (register_rays_ints_.GetSize() == 0) register_rays_ints_.Resize(2 + 4);
+  if (score_poses_best_.GetSize() == 0) score_poses_best_.Resize(1);
+  vk_transform* pose = reinterpret_cast<vk_transform*>(register_rays_floats_.GetData());
+  float* system = register_rays_floats_.GetData() + 32;
+  float* update = system + 48;
+  int* state = register_rays_ints_.GetData();
+  int* counts = state + 2;
+  Localization out = {};
+  out.best_index = -1;
+  const float* rays = reinterpret_cast<const float*>(rays_dev);
+  const vk_transform* candidates = reinterpret_cast<const vk_transform*>(score_poses_poses_.GetData());
+  vk_pose_score* scores = reinterpret_cast<vk_pose_score*>(score_poses_scores_.GetData());
+  const vk_transform seed = Transform().ToVk();
+  const vk_volume v = ToVk();
+  // score, choose, refine: one enqueue. The identity stands in the pose buffer for the case that nothing is chosen
+  if (count > 0)
+  {
+    VK_ASSERT(vk_transform_upload(pose, &seed, Device::GetStream()));
+    VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
+  }
+  VK_ASSERT(vk_volume_score_poses(&v, rays, ranges_dev, count, candidates, pose_count, &sp, scores, score_poses_workspace_.GetData(),
+      Device::GetStream()));
+  if (count == 0) return out;                      // nothing was launched and nothing was written
+  VK_ASSERT(vk_volume_score_poses_best(scores, candidates, pose_count, &sp, score_poses_best_.GetData(), pose, Device::GetStream()));
+  VK_ASSERT(vk_volume_register_rays(&v, rays, ranges_dev, count, pose, &p, system, state, counts, update,
+      register_rays_workspace_.GetData(), Device::GetStream()));
+  score_poses_best_.CopyToHost(&out.best_index);
+  if (out.best_index < 0) return out;              // what the loop refined from the identity is not a result
+  std::vector<float> floats(register_rays_floats_.GetSize());
+  std::vector<int> ints(register_rays_ints_.GetSize());
+  register_rays_floats_.CopyToHost(floats.data());
+  register_rays_ints_.CopyToHost(ints.data());
+  vk_transform result;
+  std::memcpy(&result, floats.data(), sizeof(result));
+  out.pose = Transform::FromVk(result);
+  out.steps = ints[0];
+  out.converged = ints[1] == 1;
+  out.overlap = ints[1] != VK_REGISTER_NO_OVERLAP;
+  out.residuals = ints[4];
+  out.rms = ints[4] > 0 ? std::sqrt(floats[32 + 42] / float(ints[4])) : 0.0f;
+  return out;
+}
+
 void Volume::Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, Vector4f* gradients_dev, const Transform* pose,
     const SampleOptions& options) const
 {

@@ -264,6 +264,25 @@ class RegisterRaysParams(C.Structure):
                 ("max_abs_distance", C.c_float), ("pad", C.c_int32)]
 
 
+class ScorePosesParams(C.Structure):
+    """vk_score_poses_params (vk.h): the units of vk_volume_score_poses' origins and ranges, the residuals below which
+    vk_volume_score_poses_best names no pose, which ranges are measurements and the band, in truncation lengths"""
+    _fields_ = [("flags", C.c_int32), ("min_residuals", C.c_int32), ("r_min", C.c_float), ("r_max", C.c_float),
+                ("max_abs_distance", C.c_float), ("pad", C.c_int32)]
+
+
+class PoseScore(C.Structure):
+    """vk_pose_score (vk.h): vk_volume_register_rays' four counts at one pose and the two integer sums over its residuals,
+    in units of 2^-20 truncation lengths (squared)"""
+    _fields_ = [("measured", C.c_int32), ("sampled", C.c_int32), ("residuals", C.c_int32), ("invalid", C.c_int32),
+                ("sum_abs", C.c_int64), ("sum_squares", C.c_int64)]
+
+
+pose_score_dtype = np.dtype([("measured", "<i4"), ("sampled", "<i4"), ("residuals", "<i4"), ("invalid", "<i4"),
+                             ("sum_abs", "<i8"), ("sum_squares", "<i8")])
+assert C.sizeof(ScorePosesParams) == 24 and C.sizeof(PoseScore) == 32 and pose_score_dtype.itemsize == 32
+
+
 class PyramidAhead(C.Structure):
     """vk_pyramid_ahead (vk.h): ABI 7's record of the retired pyramid ride; the library leaves it invalid"""
     _fields_ = [("key_depths", C.c_void_p), ("key_normals", C.c_void_p), ("frame_depths", C.c_void_p), ("frame_normals", C.c_void_p),
