@@ -1,0 +1,321 @@
+"""A chain of tests/map_life.py as files: what vulcan_amd/host/bin/chain_replay reads to make the same calls through the C++
+class layer (vulcan_amd/host), and what it writes back.
+
+write(run, directory, fill) puts one host run into `directory`:
+  volumes.txt       one line per start volume: name main excess voxel_length truncation_length depth_min depth_max
+  <name>.<buffer>   its eight buffers, raw little-endian, as oracle.HostVolume holds them
+  script.txt        one line per step: the step's index, the operation, then key=value tokens separated by blanks, nothing quoted
+  *.bin             the arrays the steps read: rays, ranges, colours, points, poses (128-byte vk_transforms), depth images, the
+                    projection; an array several steps share is written once
+  fill.txt          the workspace fill the run is meant for (chain_replay takes it as its second argument)
+Every float of a line is the hex of its 32 bits: the class layer gets the bytes the statements used.
+
+chain_replay writes into <directory>/out, read(directory) returns it as numpy arrays with the dtypes of vulcan_amd/vk_types.py.
+
+CALLS names, for every operation a script can hold, the one call of the class layer the step stands for; this file and
+vulcan_amd/host/tests/chain_replay.cpp are both written against it. Two steps of map_life compare the terms of a
+registration, which the class layer does not expose: there they stand for the loop of map_life.LOOP_STEPS steps from the same
+pose, and the statement is the step's class_host."""
+import os
+import struct
+
+import numpy as np
+
+import cast_reference as CR
+import map_life as ML
+import release_reference as R
+import score_poses_reference as SP
+import test_gpu_release as RT
+from vulcan_amd import vk_types as T
+
+CALLS = {
+    "integrate_rays": "Volume::IntegrateRays",
+    "color_rays": "Volume::ColorRays",
+    "carve_rays": "Volume::CarveRays",
+    "release_blocks": "Volume::ReleaseBlocks",
+    "merge": "Volume::Merge(other)",
+    "merge_posed": "Volume::Merge(other, Tdst_src)",
+    "frame": "Volume::SetView(frame, 3), or three SetView(frame) where the statement ran dry; DepthIntegrator::Integrate; Tracer::Trace",
+    "raycast": "Tracer::Trace",
+    "sample": "Volume::Sample, voxel units, gradients",
+    "cast_rays": "Volume::CastRays, samples and gradients",
+    "extract": "Extractor::Extract(Mesh&)",
+    "score_poses": "Volume::ScorePoses",
+    "register_terms": "Volume::Register(other, pose, 3)",
+    "register_rays_terms": "Volume::RegisterRays(rays, ranges, count, start, iterations 3)",
+    # not a step of map_life: a new Volume takes the eight buffers of `on`, device to device, and stands in for it from here on
+    "second_volume": "Volume(main, excess), vk_memcpy_d2d of the eight buffers",
+}
+FILLS = ("as-allocated", "ones", "noise")
+BUFFERS = ("voxels",) + ML.SMALL
+SENTINEL = 0x5A5A5A5A
+IMAGES = (("depth", np.float32, ()), ("color", np.float32, (3,)), ("normals", np.float32, (3,)))
+# what a read step writes: (name, dtype, trailing shape) in the order of the statement's tuple
+RETURNS = {
+    "frame": IMAGES, "raycast": IMAGES,
+    "sample": (("samples", T.voxel_dtype, ()), ("gradients", np.float32, (4,))),
+    "cast_rays": (("status", np.int32, ()), ("t", np.float32, ()), ("samples", T.voxel_dtype, ()), ("gradients", np.float32, (4,))),
+    "extract": (("points", np.float32, (3,)), ("faces", np.int32, (3,)), ("colors", np.float32, (3,)), ("normals", np.float32, (3,))),
+    "score_poses": (("scores", T.pose_score_dtype, ()),),
+}
+LOOPS = ("register_terms", "register_rays_terms")
+
+
+def hex32(value):
+    """the hex of the 32 bits of `value` as a float32"""
+    return "%08x" % struct.unpack("<I", struct.pack("<f", np.float32(value)))[0]
+
+
+def from_hex32(text):
+    return np.float32(struct.unpack("<f", struct.pack("<I", int(text, 16)))[0])
+
+
+def operation_of(step):
+    """the script's name for a step of map_life"""
+    operation = step.facts["operation"]
+    if operation == "merge" and step.facts["posed"]:
+        return "merge_posed"
+    return {"register": "register_terms", "register_rays": "register_rays_terms"}.get(operation, operation)
+
+
+class _Writer:
+    def __init__(self, directory):
+        self.directory, self.written, self.poses = directory, {}, {}
+
+    def array(self, name, make, dtype=np.float32):
+        """`name`.bin with the array `make()` gives, once"""
+        if name not in self.written:
+            data = np.ascontiguousarray(make(), dtype=dtype)
+            with open(os.path.join(self.directory, name + ".bin"), "wb") as out:
+                out.write(data.tobytes())
+            self.written[name] = data.shape
+        return name + ".bin"
+
+    def pose(self, pose):
+        """the file of a T.Transform, "-" for none"""
+        if pose is None:
+            return "-"
+        key = bytes(pose)
+        if key not in self.poses:
+            self.poses[key] = "pose_%d" % len(self.poses)
+        return self.array(self.poses[key], lambda: np.frombuffer(key, dtype=np.uint8), np.uint8)
+
+
+def _rays(w, orc, quarter, units, stretch=1.0):
+    form = "v" if units else "m"
+    return [("rays", w.array(f"rays_{quarter}_{form}", lambda: ML.rays_of(orc, quarter, units, stretch)[0])),
+            ("ranges", w.array(f"ranges_{quarter}_{form}_x{stretch:g}", lambda: ML.rays_of(orc, quarter, units, stretch)[1])),
+            ("count", 4800)]
+
+
+def _ray_form(facts):
+    units, one = ML._form(facts["flags"])
+    return [("pose", None), ("voxel_units", int(units)), ("one_observation", int(one)), ("r_min", hex32(facts["r_min"])),
+            ("r_max", hex32(facts["r_max"])), ("cap", hex32(facts["cap"]))]
+
+
+def _frame(w, orc, yaw):
+    hf = R.frame_at(orc, yaw)
+    return [("width", R.W), ("height", R.H), ("yaw", hex32(yaw)),
+            ("projection", w.array("projection", lambda: np.frombuffer(bytes(hf.depth_projection), dtype=np.float32))),
+            ("pose", w.pose(hf.depth_to_world))], hf
+
+
+def tokens(w, orc, index, record):
+    """[(key, value)] of one step: the volumes, the scalars, the files"""
+    step, facts = record.step, record.step.facts
+    operation = operation_of(step)
+    if operation in ("integrate_rays", "color_rays", "carve_rays"):
+        units = bool(facts["flags"] & ML.IR.VOXEL_UNITS)
+        out = [("on", step.on)] + _rays(w, orc, facts["quarter"], units, facts.get("stretch", 1.0)) + _ray_form(facts)
+        out = [(k, w.pose(facts["pose"]) if k == "pose" else v) for k, v in out]
+        if operation == "color_rays":
+            out += [("colors", w.array(f"colors_{facts['quarter']}", lambda: ML.colors_of(facts["quarter"]))), ("band", hex32(facts["band"]))]
+        if operation == "carve_rays":
+            out += [("t_from", hex32(facts["t_from"]))]
+        return out
+    if operation == "release_blocks":
+        rule = RT.RULES[facts["rule"]]
+        lo, hi = rule.get("keep_box", ((0, 0, 0), (0, 0, 0)))
+        return [("on", step.on), ("unobserved", int(bool(rule.get("unobserved")))), ("no_surface", int("min_abs_distance" in rule)),
+                ("min_abs_distance", hex32(rule.get("min_abs_distance", 0.0))), ("outside_box", int("keep_box" in rule)),
+                ("keep_lo", ",".join(str(v) for v in lo)), ("keep_hi", ",".join(str(v) for v in hi))]
+    if operation in ("merge", "merge_posed"):
+        return [("on", step.on), ("source", facts["source"]), ("pose", w.pose(facts["pose"])), ("max_rounds", facts["max_rounds"])]
+    if operation == "frame":
+        out, hf = _frame(w, orc, facts["yaw"])
+        return [("on", step.on)] + out + [("depth", w.array(f"depth_{facts['yaw']:g}", lambda: hf.depth)), ("ran_dry", int(bool(record.want[1])))]
+    if operation == "raycast":
+        return [("on", step.reads[0])] + _frame(w, orc, facts["yaw"])[0]
+    if operation == "sample":
+        return [("on", step.reads[0]), ("points", w.array(f"points_{index}", lambda: record.want[0])), ("count", len(record.want[0]))]
+    if operation == "cast_rays":
+        return [("on", step.reads[0])] + _rays(w, orc, facts["quarter"], False)[::2] + [("t_max", hex32(CR.T_MAX)), ("max_steps", CR.MAX_STEPS)]
+    if operation == "extract":
+        return [("on", step.reads[0])]
+    flags, r_min, r_max = ML._rays_form()
+    if operation == "score_poses":
+        poses = SP.eight_poses()
+        return [("on", step.reads[0])] + _rays(w, orc, facts["quarter"], False) + [
+            ("poses", w.array("eight_poses", lambda: np.frombuffer(b"".join(bytes(p) for p in poses), dtype=np.uint8), np.uint8)),
+            ("pose_count", len(poses)), ("band", hex32(SP.BAND)), ("r_min", hex32(r_min)), ("r_max", hex32(r_max))]
+    if operation == "register_terms":
+        return [("on", step.reads[0]), ("source", facts["source"]), ("pose", w.pose(facts["pose"])), ("iterations", ML.LOOP_STEPS),
+                ("band", hex32(ML.BAND))]
+    if operation == "register_rays_terms":
+        return [("on", step.reads[0])] + _rays(w, orc, facts["quarter"], False) + [
+            ("pose", w.pose(facts["pose"])), ("iterations", ML.LOOP_STEPS), ("band", hex32(ML.RY.BAND)), ("r_min", hex32(r_min)),
+            ("r_max", hex32(r_max))]
+    raise KeyError(operation)
+
+
+def states_after(run):
+    """per step, the sorted names of the volumes whose state run_on_device compares behind it: behind every step that changes
+    a volume, and behind the last read of a checkpoint the volumes its reads read"""
+    out, read = [], set()
+    for index, record in enumerate(run.records):
+        step = record.step
+        read |= set(step.reads)
+        last_read = step.kind == ML.READ and (index + 1 == len(run.records) or run.records[index + 1].step.kind != ML.READ)
+        if step.kind != ML.READ or last_read:
+            out.append(sorted(read | ({step.on} if step.on else set())))
+            read = set()
+        else:
+            out.append([])
+    return out
+
+
+def last_checkpoint(run):
+    """the indices of the reads behind the last step that changes a volume"""
+    at = max(index for index, record in enumerate(run.records) if record.step.kind != ML.READ)
+    return list(range(at + 1, len(run.records)))
+
+
+def lines(w, run, again=None):
+    """the script's lines: [(index, operation, [(key, value)])]. `again`: the name of a volume — behind the chain a second
+    Volume object takes its place and the reads of the last checkpoint are made once more"""
+    orc = run.orc
+    states = states_after(run)
+    out = []
+    for index, record in enumerate(run.records):
+        out.append((index, operation_of(record.step), tokens(w, orc, index, record) + [("state", ",".join(states[index]) or "-")]))
+    if again is not None:
+        out.append((len(out), "second_volume", [("on", again), ("state", "-")]))
+        reads = last_checkpoint(run)
+        for k, index in enumerate(reads):
+            state = again if k + 1 == len(reads) else "-"
+            out.append((len(out), operation_of(run.records[index].step), tokens(w, orc, index, run.records[index]) + [("state", state), ("of", index)]))
+    return out
+
+
+def write(run, directory, fill, again=None):
+    """one Run of map_life.host_run as files (see the module's docstring)"""
+    assert fill in FILLS
+    os.makedirs(directory, exist_ok=True)
+    w = _Writer(directory)
+    with open(os.path.join(directory, "volumes.txt"), "w") as out:
+        for name in sorted(run.start):
+            state = run.start[name]
+            main, excess, voxel_length, truncation_length, depth_range = state.shape
+            out.write(" ".join([name, str(main), str(excess), hex32(voxel_length), hex32(truncation_length), hex32(depth_range[0]),
+                                hex32(depth_range[1])]) + "\n")
+            hv = state.restore(run.orc)
+            for buffer in BUFFERS:
+                with open(os.path.join(directory, f"{name}.{buffer}"), "wb") as raw:
+                    raw.write(np.ascontiguousarray(getattr(hv, buffer)).tobytes())
+    with open(os.path.join(directory, "script.txt"), "w") as out:
+        for index, operation, pairs in lines(w, run, again):
+            text = " ".join([str(index), operation] + [f"{key}={value}" for key, value in pairs])
+            assert all(len(token.split("=")) == 2 for token in text.split()[2:]), text
+            out.write(text + "\n")
+    with open(os.path.join(directory, "fill.txt"), "w") as out:
+        out.write(fill + "\n")
+
+
+def parse(directory):
+    """script.txt back: [(index, operation, {key: value as text})]"""
+    out = []
+    with open(os.path.join(directory, "script.txt")) as script:
+        for line in script:
+            fields = line.split()
+            out.append((int(fields[0]), fields[1], dict(field.split("=") for field in fields[2:])))
+    return out
+
+
+def start_volumes(directory, orc):
+    """{name: the HostVolume the files of a start volume restore}"""
+    out = {}
+    with open(os.path.join(directory, "volumes.txt")) as volumes:
+        for line in volumes:
+            name, main, excess, voxel_length, truncation_length, near, far = line.split()
+            hv = orc.HostVolume(int(main), int(excess), voxel_length=float(from_hex32(voxel_length)),
+                                truncation_length=float(from_hex32(truncation_length)),
+                                depth_range=(float(from_hex32(near)), float(from_hex32(far))))
+            for buffer in BUFFERS:
+                held = getattr(hv, buffer)
+                held[:] = np.fromfile(os.path.join(directory, f"{name}.{buffer}"), dtype=held.dtype).reshape(held.shape)
+            out[name] = hv
+    return out
+
+
+# ---- what the replay wrote ------------------------------------------------------------------------------------------------
+
+STATE_DTYPES = {"hash_entries": T.hash_entry_dtype, "free_voxel_blocks": np.int32, "allocation_types": np.uint8,
+                "allocation_blocks": T.block_dtype, "block_visibility": np.uint8, "visible_blocks": np.int32, "counters": np.int32}
+
+
+def _empty_block():
+    empty = np.zeros(512, dtype=T.voxel_dtype)
+    empty["distance"] = 1
+    return empty
+
+
+def read_state(out, index, name, blocks):
+    """the arrays of test_gpu_release.state_arrays from the files of one state, the voxels whole again (`blocks` of them), and
+    `visible_size`, Volume::GetVisibleBlocks().GetSize()"""
+    prefix = os.path.join(out, f"{index}.state.{name}.")
+    state = {buffer: np.fromfile(prefix + buffer, dtype=dtype) for buffer, dtype in STATE_DTYPES.items() if buffer != "counters"}
+    state["counters"] = np.fromfile(prefix + "public_counters", dtype=np.int32)             # Volume::GetCounters
+    state["counters_buffer"] = np.fromfile(prefix + "counters", dtype=np.int32)
+    written = np.fromfile(prefix + "written", dtype=np.int32)
+    voxels = np.tile(_empty_block(), blocks)
+    voxels.view(np.uint8).reshape(blocks, 512 * T.voxel_dtype.itemsize)[written] = np.fromfile(prefix + "blocks", dtype=np.uint8).reshape(len(written), 512 * T.voxel_dtype.itemsize)
+    state["voxels"] = voxels
+    state["visible_size"] = int(np.fromfile(prefix + "visible_size", dtype=np.int32)[0])
+    return state
+
+
+def read(directory):
+    """{index: {"counts": int32 array or None, "returns": tuple of arrays or None, "loop": dict or None,
+    "states": {name: read_state's arrays}}} of every line of the script"""
+    out = os.path.join(directory, "out")
+    sizes = {}
+    with open(os.path.join(directory, "volumes.txt")) as volumes:
+        for line in volumes:
+            fields = line.split()
+            sizes[fields[0]] = int(fields[1]) + int(fields[2])
+    result = {}
+    for index, operation, arguments in parse(directory):
+        step = result[index] = {"counts": None, "returns": None, "loop": None, "states": {}}
+        counts = os.path.join(out, f"{index}.counts")
+        if os.path.exists(counts):
+            step["counts"] = np.fromfile(counts, dtype=np.int32)
+        if operation in RETURNS:
+            arrays = []
+            for name, dtype, trailing in RETURNS[operation]:
+                array = np.fromfile(os.path.join(out, f"{index}.{name}"), dtype=dtype)
+                if operation in ("frame", "raycast"):
+                    array = array.reshape((int(arguments["height"]), int(arguments["width"])) + trailing)
+                else:
+                    array = array.reshape((-1,) + trailing)
+                arrays.append(array)
+            step["returns"] = tuple(arrays)
+        if operation in LOOPS:
+            ints = np.fromfile(os.path.join(out, f"{index}.loop"), dtype=np.int32)
+            step["loop"] = {"steps": int(ints[0]), "code": int(ints[1]), "counts": tuple(int(c) for c in ints[2:6]),
+                            "result": tuple(int(v) for v in ints[6:10]),        # Registration: steps, converged, overlap, residuals
+                            "pose": T.Transform.from_buffer_copy(open(os.path.join(out, f"{index}.pose"), "rb").read())}
+        if arguments["state"] != "-":
+            for name in arguments["state"].split(","):
+                step["states"][name] = read_state(out, index, name, sizes[name])
+    return result

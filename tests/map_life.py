@@ -8,6 +8,10 @@ to every step, bit for bit, with one upload at the start.
 The units and bounds of every call are converted where the per-operation GPU tests convert them (their keywords() helpers and
 integrate_rays_reference.bounds); a merge goes on with VK_MERGE_CONTINUE on the host exactly as Volume.merge does on the device.
 
+Two of the read steps compare the terms of a registration, which the C++ class layer does not expose: their class_host is the
+statement of the loop the class makes instead, for tests/test_gpu_chain_replay.py, which runs the same chains through that layer
+from the files tests/chain_files.py writes.
+
 The rays are integrate_rays_reference.pixel_hits: the 19 200 pixel rays with the ranges cast_rays gives them, taken in strided
 quarters of 4 800; the colours are color_rays_reference.colors_for, seeded by the quarter."""
 import numpy as np
@@ -19,9 +23,11 @@ import extract_attributes_reference as A
 import integrate_rays_reference as IR
 import merge_pose_reference as MP
 import merge_reference as M
+import register_rays_reference as RY
 import register_reference as RR
 import release_reference as R
 import sample_reference as S
+import score_poses_reference as SP
 import scenes
 import test_gpu_carve_rays as CVT
 import test_gpu_color_rays as COT
@@ -33,6 +39,7 @@ LONG, OTHER = (509, 4096), (4093, 2048)                   # long chains; the oth
 MUTATE, FRAME, READ = "mutate", "frame", "read"
 BEYOND = CV.BEYOND                                         # carving ranges: the hit's times this, through the surface
 BAND = 0.75                                                # register's band, in truncation lengths
+LOOP_STEPS = 3                                             # Gauss-Newton steps of the loops the class layer makes (class_host)
 _RAYS, _RUNS = {}, {}
 
 
@@ -103,11 +110,14 @@ class Step:
     """`host(orc, volumes)` applies the statement to the HostVolume objects and returns what the call returns; `device(orc,
     side, want)` makes the call on side.volumes and returns the same, as the statement gives it; `workspace(side)` makes sure
     the workspace the call will use is the volume's cached one. `on`: the volume a mutating step changes; `reads`: the volumes
-    it only reads. `work(want)`: did the step do anything"""
+    it only reads. `work(want)`: did the step do anything. `class_host(orc, volumes)`: a second statement, for the steps whose
+    call the C++ class layer does not expose (tests/chain_files.py) — what the call it makes instead returns on the same
+    state; host_run evaluates it only when asked"""
 
-    def __init__(self, name, kind, on, host, device, workspace=None, reads=(), work=None, **facts):
+    def __init__(self, name, kind, on, host, device, workspace=None, reads=(), work=None, class_host=None, **facts):
         self.name, self.kind, self.on, self.reads = name, kind, on, tuple(reads)
         self.host, self.device, self.work = host, device, work
+        self.class_host = class_host
         self.workspace = workspace or (lambda side: None)
         self.facts = facts
 
@@ -150,7 +160,8 @@ def integrate_rays(quarter, pose=None, flags=0, cap=16.0, on="map"):
         _workspace(side, on, "integrate_rays", (dv.main, dv.excess), "vk_volume_integrate_rays_workspace_bytes", 8)
 
     return Step(f"integrate_rays(quarter {quarter}{_tag(pose, flags, cap)})", MUTATE, on, host, device, workspace,
-                work=lambda counts: counts[6] > 0, operation="integrate_rays", allocates=True)
+                work=lambda counts: counts[6] > 0, operation="integrate_rays", allocates=True, quarter=quarter, pose=pose, flags=flags, cap=cap,
+                r_min=r_min, r_max=r_max)
 
 
 def color_rays(quarter, pose=None, flags=0, cap=16.0, band=None, on="map"):
@@ -174,7 +185,8 @@ def color_rays(quarter, pose=None, flags=0, cap=16.0, band=None, on="map"):
         _workspace(side, on, "color_rays", (dv.main, dv.excess), "vk_volume_color_rays_workspace_bytes", 8)
 
     name = f"color_rays(quarter {quarter}{_tag(pose, flags, cap)}{'' if band is None else ', band %g m' % band})"
-    return Step(name, MUTATE, on, host, device, workspace, work=lambda counts: counts[5] > 0, operation="color_rays")
+    return Step(name, MUTATE, on, host, device, workspace, work=lambda counts: counts[5] > 0, operation="color_rays", quarter=quarter, pose=pose,
+                flags=flags, cap=cap, r_min=r_min, r_max=r_max, band=kw["band"])
 
 
 def carve_rays(quarter, pose=None, flags=0, cap=16.0, stretch=BEYOND, on="map"):
@@ -195,7 +207,8 @@ def carve_rays(quarter, pose=None, flags=0, cap=16.0, stretch=BEYOND, on="map"):
         _workspace(side, on, "carve_rays", (dv.main, dv.excess), "vk_volume_carve_rays_workspace_bytes", 8)
 
     return Step(f"carve_rays(quarter {quarter}, ranges x {stretch:g}{_tag(pose, flags, cap)})", MUTATE, on, host, device, workspace,
-                work=lambda counts: counts[6] > 0, operation="carve_rays")
+                work=lambda counts: counts[6] > 0, operation="carve_rays", quarter=quarter, pose=pose, flags=flags, cap=cap, r_min=r_min, r_max=r_max,
+                t_from=kw["t_from"], stretch=stretch)
 
 
 def release_blocks(rule, on="map"):
@@ -216,9 +229,10 @@ def release_blocks(rule, on="map"):
                 operation="release_blocks", rule=rule)
 
 
-def merge_statement(dst, src, pose=None, max_rounds=8):
+def merge_statement(dst, src, pose=None, max_rounds=8, calls=None):
     """Volume.merge on the host: the statement's call, then its call that continues while a call posted requests in every
-    round, dropped none and still left blocks out — the later calls' counts added up as Volume._merge_rounds adds them"""
+    round, dropped none and still left blocks out — the later calls' counts added up as Volume._merge_rounds adds them.
+    `calls`: a list that takes the counts of every call made"""
     workspace = {}
     dropped = int(dst.counters[T.VK_CTR_DROPPED])
     if pose is None:
@@ -227,21 +241,28 @@ def merge_statement(dst, src, pose=None, max_rounds=8):
         call, left_out, rounds, summed = (lambda flags: MP.merge(dst, src, pose, flags, max_rounds, workspace=workspace)), 4, 5, (2, 3, 5, 7)
     counts = call(0)
     total = list(counts)
+    made = [] if calls is None else calls
+    made.append(tuple(counts))
     while counts[rounds] == max_rounds and counts[left_out] > 0 and int(dst.counters[T.VK_CTR_DROPPED]) == dropped:
         counts = call(M.CONTINUE)
+        made.append(tuple(counts))
         for i in summed:
             total[i] += counts[i]
         total[left_out] = counts[left_out]
     return tuple(total)
 
 
-def merge(on, source, pose=None):
-    """volume `on` takes volume `source`, through `pose` (T_on_source) or on the shared lattice"""
+def merge(on, source, pose=None, max_rounds=8):
+    """volume `on` takes volume `source`, through `pose` (T_on_source) or on the shared lattice, in calls of `max_rounds`
+    allocation rounds; the calls the statement made are the step's facts["calls"]"""
+    step = None
+
     def host(orc, volumes):
-        return merge_statement(volumes[on], volumes[source], pose)
+        step.facts["calls"] = []
+        return merge_statement(volumes[on], volumes[source], pose, max_rounds, step.facts["calls"])
 
     def device(orc, side, want):
-        return side.volumes[on].merge(side.volumes[source], pose=pose)
+        return side.volumes[on].merge(side.volumes[source], pose=pose, max_rounds=max_rounds)
 
     def workspace(side):
         dv, ds = side.volumes[on], side.volumes[source]
@@ -250,8 +271,11 @@ def merge(on, source, pose=None):
         else:
             _workspace(side, on, "merge_posed", (ds.main, ds.excess, dv.main, dv.excess), "vk_volume_merge_posed_workspace_bytes", 8)
 
-    return Step(f"merge({on} <- {source}{', posed' if pose is not None else ''})", MUTATE, on, host, device, workspace, reads=(source,),
-                work=lambda counts: counts[1 if pose is None else 2] > 0, operation="merge", posed=pose is not None, allocates=True)
+    name = f"merge({on} <- {source}{', posed' if pose is not None else ''}{'' if max_rounds == 8 else ', %d round(s) a call' % max_rounds})"
+    step = Step(name, MUTATE, on, host, device, workspace, reads=(source,),
+                work=lambda counts: counts[1 if pose is None else 2] > 0, operation="merge", posed=pose is not None, allocates=True, source=source, pose=pose,
+                max_rounds=max_rounds)
+    return step
 
 
 def frame(yaw_deg, on="map"):
@@ -284,7 +308,7 @@ def frame(yaw_deg, on="map"):
         return tuple(image.cpu().numpy() for image in (out.depth, out.color, out.normals)), want[1]
 
     return Step(f"frame(yaw {yaw_deg:g})", FRAME, on, host, device, work=lambda want: (want[0][0] > 0).sum() > 1000,
-                operation="frame", allocates=True)
+                operation="frame", allocates=True, yaw=yaw_deg)
 
 
 # ---- the steps that only read --------------------------------------------------------------------------------------------
@@ -315,7 +339,7 @@ def raycast(yaw_deg, on="map"):
         return tuple(image.cpu().numpy() for image in (out.depth, out.color, out.normals))
 
     return Step(f"raycast(yaw {yaw_deg:g}, {on})", READ, None, host, device, reads=(on,), work=lambda want: (want[0] > 0).sum() > 1000,
-                operation="raycast")
+                operation="raycast", yaw=yaw_deg)
 
 
 def sample(on="map", count=2000, seed=7):
@@ -355,7 +379,7 @@ def cast_rays(quarter, on="map"):
                 got.gradients.cpu().numpy())
 
     return Step(f"cast_rays(quarter {quarter}, {on})", READ, None, host, device, reads=(on,),
-                work=lambda want: (want[0] == CR.HIT).sum() > 100, operation="cast_rays")
+                work=lambda want: (want[0] == CR.HIT).sum() > 100, operation="cast_rays", quarter=quarter)
 
 
 def extract(on="map"):
@@ -396,8 +420,62 @@ def register_terms(on, source, pose):
         ds = side.volumes[source]
         side.volumes[on]._register_setup(ds, pose, 1, BAND)
 
+    def class_host(orc, volumes):
+        return RR.register(orc, volumes[on], volumes[source], pose, iterations=LOOP_STEPS, band=BAND)
+
     return Step(f"register_terms({on} <- {source})", READ, None, host, device, workspace, reads=(on, source),
-                work=lambda want: want[0].sum() > 1000, operation="register")
+                work=lambda want: want[0].sum() > 1000, class_host=class_host, operation="register", source=source, pose=pose)
+
+
+def _rays_form():
+    """(flags, r_min, r_max) of rays in metres, as test_gpu_register_rays.form gives them"""
+    return (0,) + IR.bounds(False)
+
+
+def score_poses(quarter, on="map"):
+    """vk_volume_score_poses of a quarter of the pixel rays at score_poses_reference.eight_poses() (the identity and
+    generic() among them), with the band and the bounds of tests/test_gpu_score_poses.py: the vk_pose_score array"""
+    _, r_min, r_max = _rays_form()
+
+    def host(orc, volumes):
+        rays, ranges = rays_of(orc, quarter)
+        return (SP.score(RY.Map(volumes[on]), rays, ranges, SP.eight_poses(), SP.BAND, r_min, r_max, False),)
+
+    def device(orc, side, want):
+        rays, ranges = side.rays(orc, quarter, False)
+        scored = side.volumes[on].score_poses(rays, ranges, SP.eight_poses(), max_abs_distance=SP.BAND, r_min=r_min, r_max=r_max)
+        return (scored.host(),)
+
+    def workspace(side):
+        _workspace(side, on, "score_poses", (4800, 8), "vk_volume_score_poses_workspace_bytes", 1)
+
+    return Step(f"score_poses(quarter {quarter}, {on})", READ, None, host, device, workspace, reads=(on,),
+                work=lambda want: want[0]["residuals"].max() > 100, operation="score_poses", quarter=quarter)
+
+
+def register_rays_terms(quarter, pose, on="map"):
+    """the per-ray terms of vk_volume_register_rays of a quarter of the pixel rays at `pose`: (valid, residuals, jacobians)"""
+    flags, r_min, r_max = _rays_form()
+
+    def host(orc, volumes):
+        rays, ranges = rays_of(orc, quarter)
+        want = RY.terms(RY.Map(volumes[on]), rays, ranges, pose, RY.BAND, r_min, r_max, False)
+        return want.valid, want.r, want.J
+
+    def device(orc, side, want):
+        rays, ranges = side.rays(orc, quarter, False)
+        valid, residuals, jacobians = side.volumes[on]._register_rays_terms_call(rays, ranges, pose, RY.BAND, flags, r_min, r_max)
+        return valid.cpu().numpy(), residuals.cpu().numpy(), jacobians.cpu().numpy()
+
+    def workspace(side):
+        side.volumes[on]._register_rays_setup(4800, pose, 1, RY.BAND, flags, r_min, r_max)
+
+    def class_host(orc, volumes):
+        rays, ranges = rays_of(orc, quarter)
+        return RY.register(orc, RY.Map(volumes[on]), rays, ranges, pose, iterations=LOOP_STEPS, band=RY.BAND, r_min=r_min, r_max=r_max)
+
+    return Step(f"register_rays_terms(quarter {quarter}, {on})", READ, None, host, device, workspace, reads=(on,),
+                work=lambda want: want[0].sum() > 1000, class_host=class_host, operation="register_rays", quarter=quarter, pose=pose)
 
 
 def same(got, want):
@@ -419,10 +497,14 @@ class Chain:
         self.name, self.start, self.steps = name, start, steps
 
 
-def checkpoint(on="map", register=None):
+def checkpoint(on="map", register=None, sweep=(0, None)):
     """the read-only operations: sample, cast_rays of quarter 2 (rays the map was not made from) and of quarter 0 (rays it was
-    made from), the mesh with colours and normals, and with `register` = (source, pose) the terms of vk_volume_register"""
-    reads =[sample(on), cast_rays(2, on), cast_rays(0, on), extract(on)]
+    made from), the mesh with colours and normals, the scores of quarter `sweep[0]` at the eight poses and the terms of
+    vk_volume_register_rays of that quarter at `sweep[1]` (the pose the chain fused it through; None: the identity), and with
+    `register` = (source, pose) the terms of vk_volume_register"""
+    quarter, pose = sweep
+    reads = [sample(on), cast_rays(2, on), cast_rays(0, on), extract(on), score_poses(quarter, on),
+             register_rays_terms(quarter, T.Transform.identity() if pose is None else pose, on)]
     if register is not None:
         reads.append(register_terms(on, *register))
     return reads
@@ -430,13 +512,18 @@ def checkpoint(on="map", register=None):
 
 def ray_map():
     """a map built from rays alone: fused, coloured, carved, released, fused again through a pose, merged both ways, continued
-    by a camera and repaired, with the read-only operations at four checkpoints"""
+    back in calls that continue, continued by a camera and repaired, with the read-only operations at four checkpoints"""
     generic = MP.generic()
-    steps = [integrate_rays(0), color_rays(0)] + checkpoint()
-    steps += [carve_rays(0), carve_rays(0), carve_rays(0), release_blocks("unobserved+no-surface"), integrate_rays(1, generic)] + checkpoint()
+    # (one quarter alone is too sparse for a trilinear sample: no endpoint finds all eight voxels observed, and the two sweep
+    # reads of the checkpoint would compare nothing. A second quarter on the same lattice gives them residuals.)
+    steps = [integrate_rays(0), color_rays(0), integrate_rays(3), color_rays(3)] + checkpoint()
+    steps += [carve_rays(0), carve_rays(0), carve_rays(0), carve_rays(3), carve_rays(3), carve_rays(3)]
+    steps += [release_blocks("unobserved+no-surface"), integrate_rays(1, generic)]
+    steps += checkpoint(sweep=(1, generic))
     steps += [color_rays(1, flags=IR.VOXEL_UNITS, band=CO.TWO_VOXELS), merge("other", "map"), merge("map", "other", generic)]
-    steps += checkpoint(register=("other", generic))
-    steps += [frame(12), release_blocks("repair"), raycast(12)] + checkpoint()
+    steps += checkpoint(register=("other", generic), sweep=(1, generic))
+    steps += [merge("other", "map", max_rounds=1)]                        # what the posed merge added, one round a call: it continues
+    steps += [frame(12), release_blocks("repair"), raycast(12)] + checkpoint(sweep=(1, generic))
     return Chain("ray_map", {"map": lambda orc: M.fresh(orc, *LONG), "other": lambda orc: M.fresh(orc, *OTHER)}, steps)
 
 
@@ -464,7 +551,7 @@ OPERATIONS = ("integrate_rays", "color_rays", "carve_rays", "release_blocks", "m
 
 def random_chain(seed):
     """eight mutating steps drawn from the seed, each followed by a frame step — and, between the two, by the raycast alone
-    at the frame step before — and two reads at the end: integrate_rays, color_rays, carve_rays,
+    at the frame step before — and three reads at the end (sample, cast_rays, score_poses): integrate_rays, color_rays, carve_rays,
     release_blocks by one of the five rule sets, and the merge of view "b" (through generic() at most once a chain). The ray
     quarter, pose or no pose, metres or voxels, one observation or not and a cap of 3 or 16 are drawn with the step; the chain
     starts from the fused state or from a fresh volume. Nothing a statement refuses can be drawn: every call is a valid one."""
@@ -498,7 +585,7 @@ def random_chain(seed):
             steps.append(raycast(previous))
         steps.append(frame(yaw_deg))
         previous = yaw_deg
-    steps += [sample(), cast_rays(2)]
+    steps += [sample(), cast_rays(2), score_poses(2)]
     return Chain(f"random_chain({seed})", start, steps)
 
 
@@ -547,12 +634,22 @@ class Run:
     """`start`: {name: Snapshot of the volumes the chain starts from}, `records`: a Record per step"""
 
 
-def host_run(orc, chain, keep=True):
-    """the chain on the host. `keep`: cached under the chain's name, for the tests that share it"""
-    if chain.name in _RUNS:
-        return _RUNS[chain.name]
+def host_run(orc, chain, keep=True, class_layer=False):
+    """the chain on the host. `keep`: cached under the chain's name, for the tests that share it. `class_layer`: every record
+    whose step has a class_host also gets `class_want`, that statement on the state the step found — evaluated here, once,
+    from the snapshots, so a run that was cached without them takes them later"""
+    run = _RUNS[chain.name] if chain.name in _RUNS else _host_run(orc, chain, keep)
+    if class_layer:
+        for index, record in enumerate(run.records):
+            if record.step.class_host is not None and not hasattr(record, "class_want"):
+                volumes = {name: before(run, index)[name].restore(orc) for name in record.step.reads}
+                record.class_want = record.step.class_host(orc, volumes)
+    return run
+
+
+def _host_run(orc, chain, keep):
     run = Run()
-    run.chain = chain
+    run.chain, run.orc = chain, orc
     volumes = {name: make(orc) for name, make in chain.start.items()}
     run.start = after = {name: Snapshot(orc, hv) for name, hv in volumes.items()}
     defined = {name: True for name in volumes}

@@ -15,7 +15,7 @@ import pytest
 
 import map_life as ML
 from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
-from test_gpu_release import assert_same_state, device_copy
+from test_gpu_release import assert_arrays_same_state, device_copy, state_arrays
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
@@ -35,8 +35,11 @@ def held_tensors(side):
             counts.append(count)
         if dv._sample_pose is not None:
             workspaces.append(dv._sample_pose)
-        if dv._register_buffers is not None:
-            workspaces += [dv._register_buffers[name] for name in ("pose", "system", "state", "update")]
+        # (the workspaces and counts of register_rays and score_poses are among dv._workspaces; the scores are a new tensor
+        # every call)
+        for buffers in (dv._register_buffers, dv._register_rays_buffers):
+            if buffers is not None:
+                workspaces += [buffers[name] for name in ("pose", "system", "state", "update")]
     for ex in side.extractors():
         workspaces.append(ex.workspace)
         counts.append(ex.counts)
@@ -56,16 +59,36 @@ def overwrite(side, how, generator):
         tensor.fill_(SENTINEL)
 
 
-def assert_state(dv, hv, defined):
-    """the device holds the host's state. `defined`: VK_CTR_BANDED is the statements' too — everything test_gpu_release's
-    assert_same_state compares; after a frame step it is the device's own, and the comparison is continue_both's: the
-    volume, and the free list up to VK_CTR_VOXEL_PTR"""
+def assert_arrays_volume_equal(got, hv):
+    """test_gpu_parity.assert_volume_equal on the arrays of test_gpu_release.state_arrays"""
+    ctr = got["counters"]
+    for i in (T.VK_CTR_VISIBLE, T.VK_CTR_VOXEL_PTR, T.VK_CTR_EXCESS_PTR, T.VK_CTR_DROPPED):
+        assert ctr[i] == hv.counters[i], (i, ctr, hv.counters)
+    assert np.array_equal(got["hash_entries"], hv.hash_entries)
+    assert np.array_equal(got["block_visibility"], hv.block_visibility)
+    assert np.array_equal(got["allocation_types"], hv.allocation_types)
+    assert np.array_equal(got["allocation_blocks"], hv.allocation_blocks)
+    n = int(ctr[T.VK_CTR_VISIBLE])
+    assert np.array_equal(np.sort(got["visible_blocks"][:n]), hv.visible())     # order is unspecified (volume.cu:80-83)
+    assert got["voxels"].tobytes() == hv.voxels.tobytes()
+
+
+def assert_arrays_state(got, hv, defined):
+    """the arrays of test_gpu_release.state_arrays hold the host's state. `defined`: VK_CTR_BANDED is the statements' too —
+    everything test_gpu_release's assert_same_state compares; after a frame step it is the device's own, and the comparison
+    is continue_both's: the volume, and the free list up to VK_CTR_VOXEL_PTR"""
     if defined:
-        assert_same_state(dv, hv, all_counters=False)
+        assert_arrays_same_state(got, hv, all_counters=False)
         return
-    assert_volume_equal(dv, hv)
+    assert_arrays_volume_equal(got, hv)
     free = max(int(hv.counters[T.VK_CTR_VOXEL_PTR]) + 1, 0)
-    assert np.array_equal(dv.free_voxel_blocks.cpu().numpy()[:free], hv.free_voxel_blocks[:free])
+    assert np.array_equal(got["free_voxel_blocks"][:free], hv.free_voxel_blocks[:free])
+
+
+def assert_state(dv, hv, defined):
+    """the device holds the host's state (assert_arrays_state)"""
+    sync()
+    assert_arrays_state(state_arrays(dv), hv, defined)
 
 
 def first_difference(got, want):

@@ -40,21 +40,35 @@ def device_copy(api, hv):
 DEFINED_COUNTERS = (T.VK_CTR_VISIBLE, T.VK_CTR_VOXEL_PTR, T.VK_CTR_EXCESS_PTR, T.VK_CTR_DROPPED, T.VK_CTR_BANDED)
 
 
+def state_arrays(dv):
+    """the state of an api.Volume as host arrays, with the dtypes of the oracle's HostVolume: what the comparisons below and
+    those of test_gpu_map_life take — from a device volume here, from the files of a replay in test_gpu_chain_replay"""
+    return {"hash_entries": dv.host_entries(), "block_visibility": dv.host_visibility(),
+            "free_voxel_blocks": dv.free_voxel_blocks.cpu().numpy(), "voxels": dv.host_voxels(), "counters": dv.read_counters(),
+            "allocation_types": dv.host_allocation_types(), "allocation_blocks": dv.host_allocation_blocks(),
+            "visible_blocks": dv.visible_blocks.cpu().numpy()}
+
+
+def assert_arrays_same_state(got, hv, all_counters=True):
+    """assert_same_state on the arrays of state_arrays"""
+    assert np.array_equal(got["hash_entries"], hv.hash_entries)
+    assert np.array_equal(got["block_visibility"], hv.block_visibility)
+    assert np.array_equal(got["free_voxel_blocks"], hv.free_voxel_blocks)
+    assert got["voxels"].tobytes() == hv.voxels.tobytes()
+    counters = got["counters"]
+    print("counters", counters, hv.counters[:T.VK_CTR_PUBLIC])
+    if all_counters:
+        assert np.array_equal(counters, hv.counters[:T.VK_CTR_PUBLIC])
+    for counter in DEFINED_COUNTERS:
+        assert counters[counter] == hv.counters[counter], counter
+    assert np.array_equal(got["allocation_types"], hv.allocation_types)
+
+
 def assert_same_state(dv, hv, all_counters=True):
     """everything the call defines, and the rest of the volume with it. `all_counters`: the device has run nothing but
     uploads and releases, so all its public counters are the host's (the oracle does not keep the SetView statistics)"""
     sync()
-    assert np.array_equal(dv.host_entries(), hv.hash_entries)
-    assert np.array_equal(dv.host_visibility(), hv.block_visibility)
-    assert np.array_equal(dv.free_voxel_blocks.cpu().numpy(), hv.free_voxel_blocks)
-    assert dv.host_voxels().tobytes() == hv.voxels.tobytes()
-    got = dv.read_counters()
-    print("counters", got, hv.counters[:T.VK_CTR_PUBLIC])
-    if all_counters:
-        assert np.array_equal(got, hv.counters[:T.VK_CTR_PUBLIC])
-    for counter in DEFINED_COUNTERS:
-        assert got[counter] == hv.counters[counter], counter
-    assert np.array_equal(dv.host_allocation_types(), hv.allocation_types)
+    assert_arrays_same_state(state_arrays(dv), hv, all_counters)
 
 
 def release_both(dv, hv, rule, all_counters=True):
