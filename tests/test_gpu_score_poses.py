@@ -121,6 +121,41 @@ def test_the_counts_are_register_rays_counts(api, orc):
         assert counts == (got[k]["measured"], got[k]["sampled"], got[k]["residuals"], got[k]["invalid"])
 
 
+def one_residual_test(orc):
+    """(rays, ranges, poses) for test_one_residual_test, checked on the CPU: 513 rays spread over the displaced sweep; its truth,
+    the identity and seven of the eight poses. Once."""
+    if "cut" not in _LOOP:
+        rays, ranges, truth = RY.displaced_sweep(orc)
+        rays, ranges = np.ascontiguousarray(rays[::37][:513]), np.ascontiguousarray(ranges[::37][:513])
+        poses = [truth, T.Transform.identity()] + SP.eight_poses()[1:]
+        assert len(ranges) == 513 and len(poses) == 9
+        # the equality below says something only if the test has residuals to sum and a sampled ray to refuse
+        assert RY.terms(RY.world(orc), rays, ranges, truth).counts[2] >= 257
+        assert any(RY.terms(RY.world(orc), rays, ranges, pose).branches["outside_band"] > 0 for pose in poses)
+        _LOOP["cut"] = (rays, ranges, poses)
+    return _LOOP["cut"]
+
+
+@pytest.mark.parametrize("count", [1, 63, 257, 513])
+def test_one_residual_test(api, orc, count):
+    """the two entry points share one residual test on the device: at every pose, score_poses' six numbers are what
+    vk_volume_register_rays_terms and vk_volume_register_rays_system give there for the same rays. 9 poses are one past a pose
+    tile; the counts are inside a wave, past score_poses' workgroup of 256 and past register_rays' of 512."""
+    rays, ranges, poses = one_residual_test(orc)
+    dv = device_copy(api, RY.world(orc).hv)
+    d_rays, d_ranges = on_device(rays[:count]), on_device(ranges[:count])
+    got, _ = device_scores(dv, d_rays, d_ranges, poses_on_device(poses), len(poses), False, count)
+    flags, r_min, r_max = form(False)
+    for k, pose in enumerate(poses):
+        valid, residuals, _ = dv._register_rays_terms_call(d_rays, d_ranges, pose, SP.BAND, flags, r_min, r_max, count)
+        _, counts = dv._register_rays_system_call(d_rays, d_ranges, pose, SP.BAND, flags, r_min, r_max, count)
+        valid, residuals = valid.cpu().numpy() != 0, residuals.cpu().numpy()
+        sum_abs, sum_squares = SP.quantised(residuals[valid])              # float32, then int64
+        want = (counts[0], counts[1], int(valid.sum()), counts[3], int(sum_abs.sum()), int(sum_squares.sum()))
+        print(count, k, tuple(got[k]), want)
+        assert tuple(int(x) for x in got[k]) == want and counts[2] == want[2]
+
+
 def test_permuted_rays_permuted_poses_and_a_second_call(api, orc):
     rays, ranges, want = statement(orc, SAME, False)
     shuffled = IR.permuted(rays, ranges)

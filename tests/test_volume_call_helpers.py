@@ -74,3 +74,43 @@ def test_tensor_check(last, message):
     with pytest.raises(api.VkError) as raised:
         api._float_tensor(good, last, message, rows=4)
     assert str(raised.value) == message
+
+
+@pytest.mark.parametrize("voxel_units", [False, True])
+@pytest.mark.parametrize("one_observation", [False, True])
+def test_range_ray_arguments(voxel_units, one_observation):
+    """The bounds an operation along range rays takes from the volume's depth range, and its flags. (0.25, 6.5) are float32
+    numbers, so without voxel units the bounds are the depth range itself; a depth range that is not (the default's 0.1) is
+    the same float32 the library reads from the parameter block."""
+    rays, ranges = torch.zeros((5, 6)), torch.zeros(5)
+    depth_range, voxel_length = (0.25, 6.5), 0.008
+    got = api._range_ray_arguments("carve_rays", rays, ranges, depth_range, voxel_length, None, None, voxel_units, one_observation)
+    assert got[0] is rays and got[1] is ranges
+    if voxel_units:
+        want = tuple(float(np.float32(depth_range[k]) / np.float32(voxel_length)) for k in range(2))
+    else:
+        want = depth_range
+    assert got[2:4] == want and all(type(bound) is float for bound in got[2:4])
+    assert got[4] == (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
+    default = api._range_ray_arguments("carve_rays", rays, ranges, (0.1, 5.0), voxel_length, None, None, voxel_units)
+    scale = np.float32(voxel_length) if voxel_units else np.float32(1)
+    assert default[2:4] == (float(np.float32(0.1) / scale), float(np.float32(5.0) / scale))
+    # given bounds pass through untouched, each on its own
+    given = api._range_ray_arguments("carve_rays", rays, ranges, depth_range, voxel_length, 0.3, 123.456, voxel_units)
+    assert given[2] == 0.3 and given[3] == 123.456
+    mixed = api._range_ray_arguments("carve_rays", rays, ranges, depth_range, voxel_length, None, 7, voxel_units)
+    assert mixed[2] == want[0] and mixed[3] == 7 and type(mixed[3]) is int
+    assert given[4] == mixed[4] == (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0)        # one_observation defaults to off
+
+
+@pytest.mark.parametrize("what", ["integrate_rays", "carve_rays", "color_rays", "register_rays", "score_poses", "localize_rays"])
+def test_range_ray_arguments_name_the_operation(what):
+    arguments = ((0.1, 5.0), 0.008, None, None, False)
+    with pytest.raises(api.VkError) as raised:
+        api._range_ray_arguments(what, torch.zeros((5, 6)), torch.zeros(4), *arguments)      # another row count
+    assert str(raised.value) == f"{what}: ranges is a float32 [N] device tensor, one range per ray"
+    with pytest.raises(api.VkError) as raised:
+        api._range_ray_arguments(what, torch.zeros((5, 5)), torch.zeros(5), *arguments)
+    assert str(raised.value) == f"{what}: rays is a float32 [N, 6] device tensor"
+    wide = torch.zeros((5, 12))[:, ::2]
+    assert api._range_ray_arguments(what, wide, torch.zeros(5), *arguments)[0].is_contiguous()

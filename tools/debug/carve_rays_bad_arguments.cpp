@@ -3,32 +3,9 @@
 // return VK_ERR_ARGUMENT (or 0 for count == 0) before anything is enqueued. Build it with the entry point's own source, the
 // rest of the library as it is:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//     -I include -I vulcan_amd/csrc vulcan_amd/csrc/vk_carve_rays.hip tools/debug/carve_rays_bad_arguments.cpp \
+//     -I include -I vulcan_amd/csrc -I tools/debug vulcan_amd/csrc/vk_carve_rays.hip tools/debug/carve_rays_bad_arguments.cpp \
 //     -L vulcan_amd/lib -lvk_hip -Wl,-rpath,$PWD/vulcan_amd/lib -o carve_rays_bad_arguments
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <limits>
-
-#include "vk.h"
-
-static int g_failed = 0;
-#define EXPECT(code, call) do { const int got__ = (call); if (got__ != (code)) { ++g_failed; \
-    std::printf("line %d: expected %d, got %d: %s\n", __LINE__, (code), got__, #call); } } while (0)
-
-static vk_volume Volume(uintptr_t base = uintptr_t(1) << 20)
-{
-  vk_volume v = {};
-  void** fields[8] = {reinterpret_cast<void**>(&v.voxels), reinterpret_cast<void**>(&v.hash_entries), reinterpret_cast<void**>(&v.free_voxel_blocks),
-      reinterpret_cast<void**>(&v.allocation_types), reinterpret_cast<void**>(&v.allocation_blocks), reinterpret_cast<void**>(&v.block_visibility),
-      reinterpret_cast<void**>(&v.visible_blocks), reinterpret_cast<void**>(&v.counters)};
-  for (int k = 0; k < 8; ++k) *fields[k] = reinterpret_cast<void*>(base + 4096 * uintptr_t(k));
-  v.main_block_count = 8;
-  v.excess_block_count = 8;
-  v.voxel_length = 0.008f;
-  v.truncation_length = 0.04f;
-  return v;
-}
+#include "bad_arguments.h"
 
 static vk_carve_rays_params Params(int flags = 0, int max_blocks = 1024, float r_min = 0.1f, float r_max = 5.0f, float t_from = 0.0f,
     float cap = 16.0f)
@@ -46,10 +23,9 @@ static vk_carve_rays_params Params(int flags = 0, int max_blocks = 1024, float r
 int main()
 {
   static_assert(sizeof(vk_carve_rays_params) == 24, "vk_carve_rays_params");
-  const float* rays = reinterpret_cast<const float*>(uintptr_t(4096));
-  int32_t* counts = reinterpret_cast<int32_t*>(uintptr_t(8192));
-  void* workspace = reinterpret_cast<void*>(uintptr_t(16384));
-  const float inf = std::numeric_limits<float>::infinity(), nan = std::nanf("");
+  const float* rays = kRays;
+  int32_t* counts = kInts;
+  void* workspace = kWorkspace;
   const vk_volume v = Volume();
   const vk_carve_rays_params p = Params();
   EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(nullptr, rays, rays, 8, nullptr, &p, counts, workspace, nullptr));
@@ -61,7 +37,8 @@ int main()
   EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, nullptr, 8, nullptr, &p, counts, workspace, nullptr));
   EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, -1, nullptr, &p, counts, workspace, nullptr));
   EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, (1 << 22) + 1, nullptr, &p, counts, workspace, nullptr));
-  EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, std::numeric_limits<int32_t>::max(), nullptr, &p, counts, workspace, nullptr));
+  EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, kMost, nullptr, &p, counts, workspace, nullptr));
+  EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, kLeast, nullptr, &p, counts, workspace, nullptr));
   {
     vk_volume broken = Volume();
     broken.hash_entries = nullptr;
@@ -73,41 +50,41 @@ int main()
     broken.main_block_count = 0;
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&broken, rays, rays, 8, nullptr, &p, counts, workspace, nullptr));
     broken = Volume();
-    broken.excess_block_count = std::numeric_limits<int32_t>::max();
+    broken.excess_block_count = kMost;
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&broken, rays, rays, 8, nullptr, &p, counts, workspace, nullptr));
     broken = Volume((uintptr_t(1) << 20) + 8);
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&broken, rays, rays, 8, nullptr, &p, counts, workspace, nullptr));
     broken = Volume();
     broken.truncation_length = 0.008f * 64.5f;
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&broken, rays, rays, 8, nullptr, &p, counts, workspace, nullptr));
-    broken.truncation_length = nan;
+    broken.truncation_length = kNan;
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&broken, rays, rays, 8, nullptr, &p, counts, workspace, nullptr));
   }
-  const int flags[] = {4, 7, 8, -1, 1 << 16, std::numeric_limits<int32_t>::min()};
+  const int flags[] = {4, 7, 8, -1, 1 << 16, kLeast};
   for (int f : flags)
   {
     const vk_carve_rays_params bad = Params(f);
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, 8, nullptr, &bad, counts, workspace, nullptr));
   }
-  const int blocks[] = {0, -1, 4097, 1 << 30, std::numeric_limits<int32_t>::min()};
+  const int blocks[] = {0, -1, 4097, 1 << 30, kLeast};
   for (int b : blocks)
   {
     const vk_carve_rays_params bad = Params(0, b);
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, 8, nullptr, &bad, counts, workspace, nullptr));
   }
-  const float caps[] = {0.5f, 0.0f, -1.0f, 32768.0f, inf, nan};
+  const float caps[] = {0.5f, 0.0f, -1.0f, 32768.0f, kInf, kNan};
   for (float c : caps)
   {
     const vk_carve_rays_params bad = Params(0, 1024, 0.1f, 5.0f, 0.0f, c);
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, 8, nullptr, &bad, counts, workspace, nullptr));
   }
-  const float bounds[][2] = {{-0.001f, 5.0f}, {1.0f, 1.0f}, {2.0f, 1.0f}, {0.0f, inf}, {0.0f, nan}, {nan, 5.0f}, {-inf, 5.0f}, {0.0f, 0.0f}};
+  const float bounds[][2] = {{-0.001f, 5.0f}, {1.0f, 1.0f}, {2.0f, 1.0f}, {0.0f, kInf}, {0.0f, kNan}, {kNan, 5.0f}, {-kInf, 5.0f}, {0.0f, 0.0f}};
   for (const auto& b : bounds)
   {
     const vk_carve_rays_params bad = Params(0, 1024, b[0], b[1]);
     EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, 8, nullptr, &bad, counts, workspace, nullptr));
   }
-  const float starts[] = {-0.001f, -inf, inf, nan};
+  const float starts[] = {-0.001f, -kInf, kInf, kNan};
   for (float t : starts)
   {
     const vk_carve_rays_params bad = Params(0, 1024, 0.1f, 5.0f, t);
@@ -123,8 +100,7 @@ int main()
   EXPECT(VK_ERR_ARGUMENT, vk_volume_carve_rays(&v, rays, rays, 0, nullptr, &p, nullptr, workspace, nullptr));
   EXPECT(0, vk_volume_carve_rays_workspace_bytes(0, 0) != 0);
   EXPECT(0, vk_volume_carve_rays_workspace_bytes(8, -1) != 0);
-  EXPECT(0, vk_volume_carve_rays_workspace_bytes(std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::max()) != 0);
+  EXPECT(0, vk_volume_carve_rays_workspace_bytes(kMost, kMost) != 0);
   EXPECT(1, vk_volume_carve_rays_workspace_bytes(509, 96) >= size_t(605) * (512 * 4 + 1));
-  std::printf("carve_rays_bad_arguments: %d failed\n", g_failed);
-  return g_failed ? 1 : 0;
+  return Finish("carve_rays_bad_arguments");
 }

@@ -3,32 +3,9 @@
 // sanitizer run of those checks. No GPU is needed or touched: each call has to return VK_ERR_ARGUMENT (or 0 for count == 0)
 // before anything is enqueued. Build it with the entry points' own source, the rest of the library as it is:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//     -I include -I vulcan_amd/csrc vulcan_amd/csrc/vk_register_rays.hip tools/debug/register_rays_bad_arguments.cpp \
+//     -I include -I vulcan_amd/csrc -I tools/debug vulcan_amd/csrc/vk_register_rays.hip tools/debug/register_rays_bad_arguments.cpp \
 //     -L vulcan_amd/lib -lvk_hip -Wl,-rpath,$PWD/vulcan_amd/lib -o register_rays_bad_arguments
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <limits>
-
-#include "vk.h"
-
-static int g_failed = 0;
-#define EXPECT(code, call) do { const int got__ = (call); if (got__ != (code)) { ++g_failed; \
-    std::printf("line %d: expected %d, got %d: %s\n", __LINE__, (code), got__, #call); } } while (0)
-
-static vk_volume Volume(uintptr_t base = uintptr_t(1) << 20)
-{
-  vk_volume v = {};
-  void** fields[8] = {reinterpret_cast<void**>(&v.voxels), reinterpret_cast<void**>(&v.hash_entries), reinterpret_cast<void**>(&v.free_voxel_blocks),
-      reinterpret_cast<void**>(&v.allocation_types), reinterpret_cast<void**>(&v.allocation_blocks), reinterpret_cast<void**>(&v.block_visibility),
-      reinterpret_cast<void**>(&v.visible_blocks), reinterpret_cast<void**>(&v.counters)};
-  for (int k = 0; k < 8; ++k) *fields[k] = reinterpret_cast<void*>(base + 4096 * uintptr_t(k));
-  v.main_block_count = 8;
-  v.excess_block_count = 8;
-  v.voxel_length = 0.008f;
-  v.truncation_length = 0.04f;
-  return v;
-}
+#include "bad_arguments.h"
 
 static vk_register_rays_params Params(int flags = 0, int iterations = 20, float r_min = 0.1f, float r_max = 5.0f, float band = 0.75f)
 {
@@ -40,13 +17,6 @@ static vk_register_rays_params Params(int flags = 0, int iterations = 20, float 
   p.max_abs_distance = band;
   return p;
 }
-
-static const float* const kRays = reinterpret_cast<const float*>(uintptr_t(4096));
-static float* const kFloats = reinterpret_cast<float*>(uintptr_t(8192));
-static int32_t* const kInts = reinterpret_cast<int32_t*>(uintptr_t(12288));
-static uint8_t* const kBytes = reinterpret_cast<uint8_t*>(uintptr_t(20480));
-static vk_transform* const kPose = reinterpret_cast<vk_transform*>(uintptr_t(24576));
-static void* const kWorkspace = reinterpret_cast<void*>(uintptr_t(16384));
 
 // the three entry points with the arguments they share: whatever one refuses for them, all three refuse
 static void All(int code, const vk_volume* v, const float* rays, const float* ranges, int32_t count, vk_transform* pose,
@@ -67,7 +37,6 @@ static void All(int code, const vk_volume* v, const float* rays, const float* ra
 int main()
 {
   static_assert(sizeof(vk_register_rays_params) == 24, "vk_register_rays_params");
-  const float inf = std::numeric_limits<float>::infinity(), nan = std::nanf("");
   const vk_volume v = Volume();
   const vk_register_rays_params p = Params();
   ALL(VK_ERR_ARGUMENT, nullptr, kRays, kRays, 8, kPose, &p, kWorkspace);
@@ -79,8 +48,8 @@ int main()
   ALL(VK_ERR_ARGUMENT, &v, kRays, nullptr, 8, kPose, &p, kWorkspace);
   ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, -1, kPose, &p, kWorkspace);
   ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, (1 << 22) + 1, kPose, &p, kWorkspace);
-  ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, std::numeric_limits<int32_t>::max(), kPose, &p, kWorkspace);
-  ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, std::numeric_limits<int32_t>::min(), kPose, &p, kWorkspace);
+  ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, kMost, kPose, &p, kWorkspace);
+  ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, kLeast, kPose, &p, kWorkspace);
   {
     vk_volume broken = Volume();
     broken.hash_entries = nullptr;
@@ -89,36 +58,36 @@ int main()
     broken.voxel_length = 0.0f;
     ALL(VK_ERR_ARGUMENT, &broken, kRays, kRays, 8, kPose, &p, kWorkspace);
     broken = Volume();
-    broken.truncation_length = nan;
+    broken.truncation_length = kNan;
     ALL(VK_ERR_ARGUMENT, &broken, kRays, kRays, 8, kPose, &p, kWorkspace);
     broken = Volume();
     broken.main_block_count = 0;
     ALL(VK_ERR_ARGUMENT, &broken, kRays, kRays, 8, kPose, &p, kWorkspace);
     broken = Volume();
-    broken.excess_block_count = std::numeric_limits<int32_t>::max();
+    broken.excess_block_count = kMost;
     ALL(VK_ERR_ARGUMENT, &broken, kRays, kRays, 8, kPose, &p, kWorkspace);
     broken = Volume((uintptr_t(1) << 20) + 8);
     ALL(VK_ERR_ARGUMENT, &broken, kRays, kRays, 8, kPose, &p, kWorkspace);
   }
-  const int flags[] = {2, 3, 4, 8, -1, 1 << 16, std::numeric_limits<int32_t>::min()};
+  const int flags[] = {2, 3, 4, 8, -1, 1 << 16, kLeast};
   for (int f : flags)
   {
     const vk_register_rays_params bad = Params(f);
     ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, 8, kPose, &bad, kWorkspace);
   }
-  const int steps[] = {0, -1, 65, std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::min()};
+  const int steps[] = {0, -1, 65, kMost, kLeast};
   for (int n : steps)
   {
     const vk_register_rays_params bad = Params(0, n);
     ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, 8, kPose, &bad, kWorkspace);
   }
-  const float bounds[][2] = {{-0.001f, 5.0f}, {1.0f, 1.0f}, {2.0f, 1.0f}, {0.0f, inf}, {0.0f, nan}, {nan, 5.0f}, {-inf, 5.0f}, {0.0f, 0.0f}};
+  const float bounds[][2] = {{-0.001f, 5.0f}, {1.0f, 1.0f}, {2.0f, 1.0f}, {0.0f, kInf}, {0.0f, kNan}, {kNan, 5.0f}, {-kInf, 5.0f}, {0.0f, 0.0f}};
   for (const auto& b : bounds)
   {
     const vk_register_rays_params bad = Params(0, 20, b[0], b[1]);
     ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, 8, kPose, &bad, kWorkspace);
   }
-  const float bands[] = {0.0f, -0.0f, -0.5f, 1.0000001f, 1.5f, inf, -inf, nan};
+  const float bands[] = {0.0f, -0.0f, -0.5f, 1.0000001f, 1.5f, kInf, -kInf, kNan};
   for (float b : bands)
   {
     const vk_register_rays_params bad = Params(0, 20, 0.1f, 5.0f, b);
@@ -146,13 +115,17 @@ int main()
     ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, 0, kPose, &bad, kWorkspace);
   }
   ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, 0, nullptr, &p, kWorkspace);
+  {
+    vk_volume wide = Volume();                      // nothing walks a band: the 64 voxels of the walks' truncation bound are none here
+    wide.truncation_length = 0.008f * 64.5f;
+    ALL(VK_OK, &wide, kRays, kRays, 0, kPose, &p, kWorkspace);
+  }
   ALL(VK_ERR_ARGUMENT, &v, kRays, kRays, 0, kPose, &p, nullptr);
   EXPECT(0, vk_volume_register_rays_workspace_bytes(-1) != 0);
   EXPECT(0, vk_volume_register_rays_workspace_bytes((1 << 22) + 1) != 0);
-  EXPECT(0, vk_volume_register_rays_workspace_bytes(std::numeric_limits<int32_t>::max()) != 0);
-  EXPECT(0, vk_volume_register_rays_workspace_bytes(std::numeric_limits<int32_t>::min()) != 0);
+  EXPECT(0, vk_volume_register_rays_workspace_bytes(kMost) != 0);
+  EXPECT(0, vk_volume_register_rays_workspace_bytes(kLeast) != 0);
   EXPECT(1, vk_volume_register_rays_workspace_bytes(0) >= 128);
   EXPECT(1, vk_volume_register_rays_workspace_bytes(1 << 22) >= size_t(4096) * 128);
-  std::printf("register_rays_bad_arguments: %d failed\n", g_failed);
-  return g_failed ? 1 : 0;
+  return Finish("register_rays_bad_arguments");
 }

@@ -3,32 +3,9 @@
 // sanitizer run of those checks. No GPU is needed or touched: each call has to return VK_ERR_ARGUMENT (or 0 for count == 0)
 // before anything is enqueued. Build it with the entry points' own source, the rest of the library as it is:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//     -I include -I vulcan_amd/csrc vulcan_amd/csrc/vk_score_poses.hip tools/debug/score_poses_bad_arguments.cpp \
+//     -I include -I vulcan_amd/csrc -I tools/debug vulcan_amd/csrc/vk_score_poses.hip tools/debug/score_poses_bad_arguments.cpp \
 //     -L vulcan_amd/lib -lvk_hip -Wl,-rpath,$PWD/vulcan_amd/lib -o score_poses_bad_arguments
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <limits>
-
-#include "vk.h"
-
-static int g_failed = 0;
-#define EXPECT(code, call) do { const int got__ = (call); if (got__ != (code)) { ++g_failed; \
-    std::printf("line %d: expected %d, got %d: %s\n", __LINE__, (code), got__, #call); } } while (0)
-
-static vk_volume Volume(uintptr_t base = uintptr_t(1) << 20)
-{
-  vk_volume v = {};
-  void** fields[8] = {reinterpret_cast<void**>(&v.voxels), reinterpret_cast<void**>(&v.hash_entries), reinterpret_cast<void**>(&v.free_voxel_blocks),
-      reinterpret_cast<void**>(&v.allocation_types), reinterpret_cast<void**>(&v.allocation_blocks), reinterpret_cast<void**>(&v.block_visibility),
-      reinterpret_cast<void**>(&v.visible_blocks), reinterpret_cast<void**>(&v.counters)};
-  for (int k = 0; k < 8; ++k) *fields[k] = reinterpret_cast<void*>(base + 4096 * uintptr_t(k));
-  v.main_block_count = 8;
-  v.excess_block_count = 8;
-  v.voxel_length = 0.008f;
-  v.truncation_length = 0.04f;
-  return v;
-}
+#include "bad_arguments.h"
 
 static vk_score_poses_params Params(int flags = 0, int min_residuals = 1, float r_min = 0.1f, float r_max = 5.0f, float band = 0.75f)
 {
@@ -41,11 +18,8 @@ static vk_score_poses_params Params(int flags = 0, int min_residuals = 1, float 
   return p;
 }
 
-static const float* const kRays = reinterpret_cast<const float*>(uintptr_t(4096));
-static int32_t* const kInts = reinterpret_cast<int32_t*>(uintptr_t(12288));
-static vk_pose_score* const kScores = reinterpret_cast<vk_pose_score*>(uintptr_t(20480));
-static vk_transform* const kPoses = reinterpret_cast<vk_transform*>(uintptr_t(24576));
-static void* const kWorkspace = reinterpret_cast<void*>(uintptr_t(16384));
+static vk_pose_score* const kScores = reinterpret_cast<vk_pose_score*>(uintptr_t(28672));
+static vk_transform* const kPoses = kPose;
 
 static int Score(const vk_volume* v, const float* rays, const float* ranges, int32_t count, const vk_transform* poses, int32_t pose_count,
     const vk_score_poses_params* p, vk_pose_score* scores = kScores, void* workspace = kWorkspace)
@@ -56,8 +30,6 @@ static int Score(const vk_volume* v, const float* rays, const float* ranges, int
 int main()
 {
   static_assert(sizeof(vk_score_poses_params) == 24 && sizeof(vk_pose_score) == 32, "the two structs");
-  const float inf = std::numeric_limits<float>::infinity(), nan = std::nanf("");
-  const int32_t most = std::numeric_limits<int32_t>::max(), least = std::numeric_limits<int32_t>::min();
   const vk_volume v = Volume();
   const vk_score_poses_params p = Params();
   EXPECT(VK_ERR_ARGUMENT, Score(nullptr, kRays, kRays, 8, kPoses, 8, &p));
@@ -68,9 +40,9 @@ int main()
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 8, kPoses, 8, &p, kScores, static_cast<char*>(kWorkspace) + 8));
   EXPECT(VK_ERR_ARGUMENT, Score(&v, nullptr, kRays, 8, kPoses, 8, &p));
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, nullptr, 8, kPoses, 8, &p));
-  const int32_t counts[] = {-1, (1 << 22) + 1, most, least};
+  const int32_t counts[] = {-1, (1 << 22) + 1, kMost, kLeast};
   for (int32_t n : counts) EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, n, kPoses, 1, &p));
-  const int32_t pose_counts[] = {0, -1, 65537, most, least};
+  const int32_t pose_counts[] = {0, -1, 65537, kMost, kLeast};
   for (int32_t n : pose_counts)
   {
     EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 8, kPoses, n, &p));
@@ -78,7 +50,7 @@ int main()
     EXPECT(VK_ERR_ARGUMENT, vk_volume_score_poses_best(kScores, kPoses, n, &p, kInts, kPoses, nullptr));
     EXPECT(0, vk_volume_score_poses_workspace_bytes(8, n) != 0);
   }
-  // the product: 1 << 28 pairs are the most
+  // the product: 1 << 28 pairs are the kMost
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 1 << 22, kPoses, 65, &p));
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, (1 << 12) + 1, kPoses, 65536, &p));
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, (1 << 14) + 1, kPoses, 1 << 14, &p));
@@ -91,25 +63,25 @@ int main()
     broken.voxel_length = 0.0f;
     EXPECT(VK_ERR_ARGUMENT, Score(&broken, kRays, kRays, 8, kPoses, 8, &p));
     broken = Volume();
-    broken.truncation_length = nan;
+    broken.truncation_length = kNan;
     EXPECT(VK_ERR_ARGUMENT, Score(&broken, kRays, kRays, 8, kPoses, 8, &p));
     broken = Volume();
     broken.main_block_count = 0;
     EXPECT(VK_ERR_ARGUMENT, Score(&broken, kRays, kRays, 8, kPoses, 8, &p));
     broken = Volume();
-    broken.excess_block_count = most;
+    broken.excess_block_count = kMost;
     EXPECT(VK_ERR_ARGUMENT, Score(&broken, kRays, kRays, 8, kPoses, 8, &p));
     broken = Volume((uintptr_t(1) << 20) + 8);
     EXPECT(VK_ERR_ARGUMENT, Score(&broken, kRays, kRays, 8, kPoses, 8, &p));
   }
-  const int flags[] = {2, 3, 4, 8, -1, 1 << 16, least};
+  const int flags[] = {2, 3, 4, 8, -1, 1 << 16, kLeast};
   for (int f : flags)
   {
     const vk_score_poses_params bad = Params(f);
     EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 8, kPoses, 8, &bad));
     EXPECT(VK_ERR_ARGUMENT, vk_volume_score_poses_best(kScores, kPoses, 8, &bad, kInts, kPoses, nullptr));
   }
-  const int fewest[] = {0, -1, least};
+  const int fewest[] = {0, -1, kLeast};
   for (int n : fewest)
   {
     const vk_score_poses_params bad = Params(0, n);
@@ -117,13 +89,13 @@ int main()
     EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 0, kPoses, 8, &bad));
     EXPECT(VK_ERR_ARGUMENT, vk_volume_score_poses_best(kScores, kPoses, 8, &bad, kInts, kPoses, nullptr));
   }
-  const float bounds[][2] = {{-0.001f, 5.0f}, {1.0f, 1.0f}, {2.0f, 1.0f}, {0.0f, inf}, {0.0f, nan}, {nan, 5.0f}, {-inf, 5.0f}, {0.0f, 0.0f}};
+  const float bounds[][2] = {{-0.001f, 5.0f}, {1.0f, 1.0f}, {2.0f, 1.0f}, {0.0f, kInf}, {0.0f, kNan}, {kNan, 5.0f}, {-kInf, 5.0f}, {0.0f, 0.0f}};
   for (const auto& b : bounds)
   {
     const vk_score_poses_params bad = Params(0, 1, b[0], b[1]);
     EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 8, kPoses, 8, &bad));
   }
-  const float bands[] = {0.0f, -0.0f, -0.5f, 1.0000001f, 1.5f, inf, -inf, nan};
+  const float bands[] = {0.0f, -0.0f, -0.5f, 1.0000001f, 1.5f, kInf, -kInf, kNan};
   for (float b : bands)
   {
     const vk_score_poses_params bad = Params(0, 1, 0.1f, 5.0f, b);
@@ -141,21 +113,25 @@ int main()
   EXPECT(VK_OK, Score(&v, kRays, kRays, 0, kPoses, 1, &p));
   EXPECT(VK_OK, Score(&v, kRays, kRays, 0, kPoses, 65536, &p));
   {
-    const vk_score_poses_params widest = Params(VK_RAYS_VOXEL_UNITS, most, 0.0f, 1e30f, 1.0f);
+    const vk_score_poses_params widest = Params(VK_RAYS_VOXEL_UNITS, kMost, 0.0f, 1e30f, 1.0f);
     EXPECT(VK_OK, Score(&v, kRays, kRays, 0, kPoses, 8, &widest));
     const vk_score_poses_params narrowest = Params(0, 1, 0.0f, 1e-30f, 1e-30f);
     EXPECT(VK_OK, Score(&v, kRays, kRays, 0, kPoses, 8, &narrowest));
   }
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 0, nullptr, 8, &p));
+  {
+    vk_volume wide = Volume();                      // nothing walks a band: the 64 voxels of the walks' truncation bound are none here
+    wide.truncation_length = 0.008f * 64.5f;
+    EXPECT(VK_OK, Score(&wide, kRays, kRays, 0, kPoses, 8, &p));
+  }
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 0, kPoses, 8, &p, nullptr));
   EXPECT(VK_ERR_ARGUMENT, Score(&v, kRays, kRays, 0, kPoses, 8, &p, kScores, nullptr));
   for (int32_t n : counts) EXPECT(0, vk_volume_score_poses_workspace_bytes(n, 1) != 0);
   EXPECT(0, vk_volume_score_poses_workspace_bytes(1 << 22, 65) != 0);
-  EXPECT(0, vk_volume_score_poses_workspace_bytes(most, most) != 0);
+  EXPECT(0, vk_volume_score_poses_workspace_bytes(kMost, kMost) != 0);
   EXPECT(1, vk_volume_score_poses_workspace_bytes(0, 1) >= 32);
   EXPECT(1, vk_volume_score_poses_workspace_bytes(1 << 22, 64) == (size_t(1) << 14) * 64 * 32);
   EXPECT(1, vk_volume_score_poses_workspace_bytes(1 << 12, 65536) == size_t(16) * 65536 * 32);
   EXPECT(1, vk_volume_score_poses_workspace_bytes(257, 3) >= size_t(2) * 3 * 32);
-  std::printf("score_poses_bad_arguments: %d failed\n", g_failed);
-  return g_failed ? 1 : 0;
+  return Finish("score_poses_bad_arguments");
 }

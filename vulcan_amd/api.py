@@ -265,6 +265,25 @@ def _float_tensor(x, last, message, rows=None):
     return x.contiguous()
 
 
+def _range_ray_arguments(what, rays, ranges, depth_range, voxel_length, r_min, r_max, voxel_units, one_observation=False):
+    """The arguments the operations along range rays share, for the operation `what`: (rays, ranges, r_min, r_max, flags).
+    `rays` [N, 6] and `ranges` [N] are checked (_float_tensor); a bound that is None is the volume's depth range, in float32
+    and divided by the voxel length with `voxel_units`; the flags are VK_RAYS_*."""
+    rays = _float_tensor(rays, 6, f"{what}: rays is a float32 [N, 6] device tensor")
+    ranges = _float_tensor(ranges, None, f"{what}: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+    scale = np.float32(voxel_length) if voxel_units else np.float32(1)
+    r_min = float(np.float32(depth_range[0]) / scale) if r_min is None else r_min
+    r_max = float(np.float32(depth_range[1]) / scale) if r_max is None else r_max
+    flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
+    return rays, ranges, r_min, r_max, flags
+
+
+def _registration(pose, state, counts, system, device_pose=None):
+    """the Registration of what a registration loop left: its pose, (steps, code), counts and system[48]"""
+    return Registration(pose, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
+                        float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0, device_pose)
+
+
 def _ints(counts):
     """a device tensor of counts as a tuple of int: one blocking read"""
     return tuple(int(c) for c in counts.cpu().numpy())
@@ -741,21 +760,32 @@ class Volume:
         return self._merge_rounds(lambda go_on: self._merge_posed_call(other, pose, flags | go_on, max_rounds, max_distance_weight,
                                                                        max_color_weight), max_rounds, 4, 5, (2, 3, 5, 7))
 
-    _register_buffers = None    # device buffers of vk_volume_register, per source size
+    _register_buffers = None         # device buffers of vk_volume_register, per source size
+    _register_rays_buffers = None    # device buffers of vk_volume_register_rays, per ray count
+
+    def _registration_buffers(self, held, operation, size, workspace_bytes, pose):
+        """the device buffers of a registration, `held` or — when _workspace handed out a new workspace — new ones, with
+        `pose` (a T.Transform) uploaded as the start"""
+        import torch
+        workspace, counts = self._workspace(operation, size, workspace_bytes, 4)
+        if held is None or held["workspace"] is not workspace:
+            held = {"workspace": workspace, "counts": counts, "pose": _dev_bytes(C.sizeof(T.Transform), self.device),
+                    "system": torch.zeros(48, dtype=torch.float32, device=self.device),
+                    "state": torch.zeros(2, dtype=torch.int32, device=self.device),
+                    "update": torch.zeros(6, dtype=torch.float32, device=self.device)}
+        check(lib().vk_transform_upload(_ptr(held["pose"]), _ref(pose), stream()), "vk_transform_upload")
+        return held
+
+    @staticmethod
+    def _registration_read(b):
+        """what a loop left in the buffers `b`: (pose, (steps, code), counts, system[48], update[6]), a blocking read each"""
+        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
+        return out, _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy(), b["update"].cpu().numpy()
 
     def _register_setup(self, other, pose, iterations, band):
         """the device buffers of a registration against `other`, the start pose uploaded: (buffers, vk_register_params)"""
-        import torch
-        size = (other.main, other.excess)
-        workspace, counts = self._workspace("register", size, lib().vk_volume_register_workspace_bytes, 4)
-        if self._register_buffers is None or self._register_buffers["workspace"] is not workspace:
-            self._register_buffers = {
-                "size": size, "workspace": workspace, "counts": counts, "pose": _dev_bytes(C.sizeof(T.Transform), self.device),
-                "system": torch.zeros(48, dtype=torch.float32, device=self.device),
-                "state": torch.zeros(2, dtype=torch.int32, device=self.device),
-                "update": torch.zeros(6, dtype=torch.float32, device=self.device)}
-        b = self._register_buffers
-        check(lib().vk_transform_upload(_ptr(b["pose"]), _ref(pose), stream()), "vk_transform_upload")
+        b = self._register_buffers = self._registration_buffers(self._register_buffers, "register", (other.main, other.excess),
+                                                                lib().vk_volume_register_workspace_bytes, pose)
         return b, T.RegisterParams(0, int(iterations), float(band), 0)
 
     def _register_terms_call(self, other, pose, band):
@@ -784,8 +814,7 @@ class Volume:
         check(lib().vk_volume_register(_ref(self.desc()), _ref(other.desc()), _ptr(b["pose"]), _ref(params), _ptr(b["system"]),
                                        _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]), _ptr(b["workspace"]), stream()),
               "vk_volume_register")
-        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
-        return out, _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy(), b["update"].cpu().numpy()
+        return self._registration_read(b)
 
     def register(self, other, pose=None, iterations=20, max_abs_distance=0.75):
         """vk_volume_register (not upstream): refine the rigid pose T_self_other between this volume and `other` — same
@@ -798,9 +827,7 @@ class Volume:
         Registration: `pose` (the result; merge(other, pose=result.pose) fuses through it), `steps`, `converged`,
         `overlap` (False: a step found no voxel to compare and the pose is the one it had then), `residuals` and `rms`
         (in truncation lengths) of the last evaluated step."""
-        out, state, counts, system, _ = self._register_call(other, _as_pose(pose, identity=True), iterations, max_abs_distance)
-        return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
-                            float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0)
+        return _registration(*self._register_call(other, _as_pose(pose, identity=True), iterations, max_abs_distance)[:4])
 
     def _sample_call(self, points, pose=None, flags=0, samples=True, gradients=True, count=None, out=None):
         """one vk_volume_sample at `points` (a float32 device tensor of 3 * count floats or more): the raw output buffers
@@ -894,13 +921,9 @@ class Volume:
         set_view rebuilds it) and what was prepared ahead for this volume is void. Returns (rays integrated, valid rays
         without a measurement, invalid rays, blocks allocated, rounds that posted a request, blocks updated, voxels updated,
         cell visits lost to a block that could not be allocated)."""
-        rays = _float_tensor(rays, 6, "integrate_rays: rays is a float32 [N, 6] device tensor")
-        ranges = _float_tensor(ranges, None, "integrate_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        rays, ranges, r_min, r_max, flags = _range_ray_arguments("integrate_rays", rays, ranges, self.depth_range, self.voxel_length, r_min,
+                                                                 r_max, voxel_units, one_observation)
         pose = _as_pose(pose, device=True)
-        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
-        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
-        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
-        flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
         if rays.shape[0] == 0:
             return (0,) * 8
         return self._integrate_rays_call(rays, ranges, pose, flags, max_rounds, r_min, r_max, max_distance_weight, rays.shape[0])
@@ -931,13 +954,9 @@ class Volume:
         bytes. Colours are left alone. The result does not depend on the order of the rays. Between SetView calls only:
         raises while a frame is announced. Returns (rays that carved, measured rays with nothing to carve, valid rays
         without a measurement, invalid rays, rays cut short by `max_blocks`, blocks updated, voxels updated, carves)."""
-        rays = _float_tensor(rays, 6, "carve_rays: rays is a float32 [N, 6] device tensor")
-        ranges = _float_tensor(ranges, None, "carve_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        rays, ranges, r_min, r_max, flags = _range_ray_arguments("carve_rays", rays, ranges, self.depth_range, self.voxel_length, r_min,
+                                                                 r_max, voxel_units, one_observation)
         pose = _as_pose(pose, device=True)
-        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
-        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
-        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
-        flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
         if rays.shape[0] == 0:
             return (0,) * 8
         return self._carve_rays_call(rays, ranges, pose, flags, max_blocks, r_min, r_max, t_from, max_distance_weight, rays.shape[0])
@@ -971,33 +990,20 @@ class Volume:
         frame is announced. Returns (rays coloured, measured rays without a colour, valid rays without a measurement,
         invalid rays, blocks updated, voxels updated, voxels visited but not near a surface, visits lost to an absent
         block)."""
-        rays = _float_tensor(rays, 6, "color_rays: rays is a float32 [N, 6] device tensor")
-        ranges = _float_tensor(ranges, None, "color_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        rays, ranges, r_min, r_max, flags = _range_ray_arguments("color_rays", rays, ranges, self.depth_range, self.voxel_length, r_min,
+                                                                 r_max, voxel_units, one_observation)
         colors = _float_tensor(colors, 3, "color_rays: colors is a float32 [N, 3] device tensor, one colour per ray", rays.shape[0])
         pose = _as_pose(pose, device=True)
-        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
-        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
-        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
-        band = float(np.float32(self.truncation_length) / scale) if band is None else band
-        flags = (T.VK_RAYS_VOXEL_UNITS if voxel_units else 0) | (T.VK_RAYS_ONE_OBSERVATION if one_observation else 0)
+        if band is None:
+            band = float(np.float32(self.truncation_length) / (np.float32(self.voxel_length) if voxel_units else np.float32(1)))
         if rays.shape[0] == 0:
             return (0,) * 8
         return self._color_rays_call(rays, ranges, colors, pose, flags, r_min, r_max, band, max_color_weight, rays.shape[0])
 
-    _register_rays_buffers = None    # device buffers of vk_volume_register_rays, per ray count
-
     def _register_rays_setup(self, count, pose, iterations, band, flags, r_min, r_max):
         """the device buffers of a registration of `count` rays, the start pose uploaded: (buffers, vk_register_rays_params)"""
-        import torch
-        workspace, counts = self._workspace("register_rays", (int(count),), lib().vk_volume_register_rays_workspace_bytes, 4)
-        if self._register_rays_buffers is None or self._register_rays_buffers["workspace"] is not workspace:
-            self._register_rays_buffers = {
-                "workspace": workspace, "counts": counts, "pose": _dev_bytes(C.sizeof(T.Transform), self.device),
-                "system": torch.zeros(48, dtype=torch.float32, device=self.device),
-                "state": torch.zeros(2, dtype=torch.int32, device=self.device),
-                "update": torch.zeros(6, dtype=torch.float32, device=self.device)}
-        b = self._register_rays_buffers
-        check(lib().vk_transform_upload(_ptr(b["pose"]), _ref(pose), stream()), "vk_transform_upload")
+        b = self._register_rays_buffers = self._registration_buffers(self._register_rays_buffers, "register_rays", (int(count),),
+                                                                     lib().vk_volume_register_rays_workspace_bytes, pose)
         return b, T.RegisterRaysParams(int(flags), int(iterations), float(r_min), float(r_max), float(band), 0)
 
     def _register_rays_terms_call(self, rays, ranges, pose, band, flags=0, r_min=0.1, r_max=5.0, count=None, out=None):
@@ -1023,17 +1029,20 @@ class Volume:
               "vk_volume_register_rays_system")
         return b["system"].cpu().numpy(), _ints(b["counts"])
 
+    def _register_rays_enqueue(self, rays, ranges, count, b, params):
+        """one vk_volume_register_rays from the pose in the buffers `b` (_register_rays_setup's): enqueued, nothing is read"""
+        b["state"].zero_()
+        check(lib().vk_volume_register_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
+                                            _ptr(b["system"]), _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]),
+                                            _ptr(b["workspace"]), stream()), "vk_volume_register_rays")
+
     def _register_rays_call(self, rays, ranges, pose, iterations, band, flags=0, r_min=0.1, r_max=5.0, count=None):
         """one vk_volume_register_rays from `pose` (a T.Transform): (pose, (steps, code), counts, system[48], update[6]); the
         result stays in the buffers' "pose" on the device"""
         count = ranges.numel() if count is None else int(count)
         b, params = self._register_rays_setup(count, pose, iterations, band, flags, r_min, r_max)
-        b["state"].zero_()
-        check(lib().vk_volume_register_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
-                                            _ptr(b["system"]), _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]),
-                                            _ptr(b["workspace"]), stream()), "vk_volume_register_rays")
-        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
-        return out, _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy(), b["update"].cpu().numpy()
+        self._register_rays_enqueue(rays, ranges, count, b, params)
+        return self._registration_read(b)
 
     def register_rays(self, rays, ranges, pose=None, iterations=20, max_abs_distance=0.75, r_min=None, r_max=None, voxel_units=False):
         """vk_volume_register_rays (not upstream): where the sensor is — refine the pose T_volume_rays of a sweep of range
@@ -1049,20 +1058,13 @@ class Volume:
         the same on the device for integrate_rays(pose=...); `steps`, `converged`, `overlap` (False: a step found no return
         to compare and the pose is the one it had then), `residuals` and `rms` (in truncation lengths) of the last evaluated
         step."""
-        rays = _float_tensor(rays, 6, "register_rays: rays is a float32 [N, 6] device tensor")
-        ranges = _float_tensor(ranges, None, "register_rays: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        rays, ranges, r_min, r_max, flags = _range_ray_arguments("register_rays", rays, ranges, self.depth_range, self.voxel_length,
+                                                                 r_min, r_max, voxel_units)
         start = _as_pose(pose, identity=True)
-        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
-        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
-        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
-        flags = T.VK_RAYS_VOXEL_UNITS if voxel_units else 0
         if rays.shape[0] == 0:
             return Registration(start, 0, False, False, 0, 0.0, self._pose_on_device(start).clone())
-        out, state, counts, system, _ = self._register_rays_call(rays, ranges, start, iterations, max_abs_distance, flags, r_min, r_max,
-                                                                 rays.shape[0])
-        return Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
-                            float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0,
-                            self._register_rays_buffers["pose"].clone())
+        result = self._register_rays_call(rays, ranges, start, iterations, max_abs_distance, flags, r_min, r_max, rays.shape[0])
+        return _registration(*result[:4], self._register_rays_buffers["pose"].clone())
 
     def _poses_on_device(self, poses, what):
         """(device buffer of vk_transforms, how many): `poses` a sequence of T.Transform (or 4x4 arrays), uploaded, or a device
@@ -1093,13 +1095,10 @@ class Volume:
         return scores
 
     def _score_poses_arguments(self, what, rays, ranges, poses, r_min, r_max, voxel_units):
-        rays = _float_tensor(rays, 6, f"{what}: rays is a float32 [N, 6] device tensor")
-        ranges = _float_tensor(ranges, None, f"{what}: ranges is a float32 [N] device tensor, one range per ray", rays.shape[0])
+        rays, ranges, r_min, r_max, flags = _range_ray_arguments(what, rays, ranges, self.depth_range, self.voxel_length, r_min, r_max,
+                                                                 voxel_units)
         poses, pose_count = self._poses_on_device(poses, what)
-        scale = np.float32(self.voxel_length) if voxel_units else np.float32(1)
-        r_min = float(np.float32(self.depth_range[0]) / scale) if r_min is None else r_min
-        r_max = float(np.float32(self.depth_range[1]) / scale) if r_max is None else r_max
-        return rays, ranges, poses, pose_count, r_min, r_max, T.VK_RAYS_VOXEL_UNITS if voxel_units else 0
+        return rays, ranges, poses, pose_count, r_min, r_max, flags
 
     def score_poses(self, rays, ranges, poses, max_abs_distance=0.75, r_min=None, r_max=None, voxel_units=False):
         """vk_volume_score_poses (not upstream): how well each of many candidate poses T_volume_rays explains a sweep of range
@@ -1136,21 +1135,15 @@ class Volume:
         if min_residuals is None:       # half the measured rays: the measurement test does not depend on the pose
             min_residuals = max(1, int(((ranges >= r_min) & (ranges <= r_max)).sum()) // 2)
         b, params = self._register_rays_setup(count, T.Transform.identity(), iterations, max_abs_distance, flags, r_min, r_max)
-        b["state"].zero_()
         best = torch.zeros(1, dtype=torch.int32, device=self.device)
         scored = PoseScores(self._score_poses_call(rays, ranges, poses, pose_count, max_abs_distance, flags, r_min, r_max, count), poses,
                             pose_count, self.device)
         scored._best_call(min_residuals, best, b["pose"])
-        check(lib().vk_volume_register_rays(_ref(self.desc()), _ptr(rays), _ptr(ranges), count, _ptr(b["pose"]), _ref(params),
-                                            _ptr(b["system"]), _ptr(b["state"]), _ptr(b["counts"]), _ptr(b["update"]),
-                                            _ptr(b["workspace"]), stream()), "vk_volume_register_rays")
+        self._register_rays_enqueue(rays, ranges, count, b, params)
         index = int(best.cpu()[0])
         if index < 0:
             raise VkError(f"localize_rays: none of the {pose_count} candidates has {min_residuals} residuals")
-        out = T.Transform.from_buffer_copy(b["pose"].cpu().numpy().tobytes())
-        state, counts, system = _ints(b["state"]), _ints(b["counts"]), b["system"].cpu().numpy()
-        result = Registration(out, state[0], state[1] == 1, state[1] != T.VK_REGISTER_NO_OVERLAP, counts[2],
-                              float(np.sqrt(float(system[42]) / counts[2])) if counts[2] else 0.0, b["pose"].clone())
+        result = _registration(*self._registration_read(b)[:4], b["pose"].clone())
         result.best_index, result.scores = index, scored
         return result
 

@@ -32,40 +32,17 @@ static_assert(kFoldSlots == 8, "a workgroup reads its slots' bytes as one 64-bit
 
 enum { cCarved = 0, cNothing, cNoMeasurement, cInvalid, cCut, cBlocks, cVoxels, cCarves, cWords = 8 };
 
-struct CarveParams
+struct CarveParams : RangeRays
 {
-  vk_volume v;
-  int total;                    // main + excess entries = pool slots
-  int count;
-  int voxel_units, one_observation;
+  int one_observation;
   int max_blocks;
-  float r_min, r_max, t_from, cap;
-  const float* rays;            // [6 * count]
-  const float* ranges;          // [count]
-  const vk_transform* pose;     // device, or null
+  float t_from, cap;
   // workspace
   uint32_t* visits;             // [512 * total]  N per pool voxel
   uint8_t* touched;             // [total]        1 for a pool slot that took a carve
   int32_t* ctl;                 // [cWords]
   int32_t* counts;              // [8] output
 };
-
-// the first crossing of a block face along one axis and the distance between crossings: axis_setup with a cell edge of 8
-__device__ __forceinline__ void block_axis_setup(float t0, float p, float n, int B, int& step, float& bmax, float& bdelta)
-{
-  step = n > 0.0f ? 1 : (n < 0.0f ? -1 : 0);
-  bmax = bdelta = INFINITY;
-  if (n > 0.0f)
-  {
-    bmax = t0 + ((float)(8 * (B + 1)) - p) / n;
-    bdelta = 8.0f / n;
-  }
-  else if (n < 0.0f)
-  {
-    bmax = t0 + ((float)(8 * B) - p) / n;
-    bdelta = 8.0f / fabsf(n);
-  }
-}
 
 // One lane per ray. (N, the touched bytes and the control words are zero: one memset in front of this launch.)
 __global__ __launch_bounds__(kThreads) void carve_add_kernel(CarveParams P)
@@ -74,7 +51,7 @@ __global__ __launch_bounds__(kThreads) void carve_add_kernel(CarveParams P)
   int what = -1, cut = 0, carves = 0;
   if (i < (size_t)P.count)
   {
-    const RangeRay ray = load_range_ray(P.rays, P.ranges, i, P.pose, P.v.voxel_length, P.voxel_units != 0, P.r_min, P.r_max);
+    const RangeRay ray = load_range_ray(P, i);
     const float tr = P.v.truncation_length / P.v.voxel_length;
     const float t0 = P.voxel_units ? P.t_from : P.t_from / P.v.voxel_length;
     const float te = ray.r - tr;
@@ -85,18 +62,15 @@ __global__ __launch_bounds__(kThreads) void carve_add_kernel(CarveParams P)
       int bx = cell_of(px) >> 3, by = cell_of(py) >> 3, bz = cell_of(pz) >> 3;
       int sx, sy, sz;
       float mx, my, mz, dx, dy, dz;
-      block_axis_setup(t0, px, ray.n.x, bx, sx, mx, dx);
-      block_axis_setup(t0, py, ray.n.y, by, sy, my, dy);
-      block_axis_setup(t0, pz, ray.n.z, bz, sz, mz, dz);
+      axis_setup<8>(t0, px, ray.n.x, bx, sx, mx, dx);
+      axis_setup<8>(t0, py, ray.n.y, by, sy, my, dy);
+      axis_setup<8>(t0, pz, ray.n.z, bz, sz, mz, dz);
       float t_in = t0;
       cut = 1;
       for (int turn = 0; turn < P.max_blocks; ++turn)
       {
-        // the axis of the smallest bmax, x before y before z on a tie (a NaN is never the smaller)
-        int axis = 0;
-        float least = mx;
-        if (my < least) { axis = 1;  least = my; }
-        if (mz < least) { axis = 2;  least = mz; }
+        float least;
+        const int axis = least_axis(mx, my, mz, least);       // of the block faces
         const float t_out = fminf(least, te);
         int slot = -1;
         Entry main_entry;
@@ -212,33 +186,19 @@ size_t vk_volume_carve_rays_workspace_bytes(int32_t main, int32_t excess)
 int vk_volume_carve_rays(const vk_volume* v, const float* rays, const float* ranges, int32_t count, const vk_transform* pose_dev,
     const vk_carve_rays_params* p, int32_t* counts_dev, void* workspace, void* stream)
 {
-  VK_REQUIRE(v && p && counts_dev && workspace);
-  VK_REQUIRE(volume_ok(v));
-  VK_REQUIRE((p->flags & ~(VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION)) == 0);
+  VK_REQUIRE(v && p && counts_dev);
   VK_REQUIRE(p->max_blocks >= 1 && p->max_blocks <= kMaxBlocks);
   VK_REQUIRE(p->max_distance_weight >= 1.0f && p->max_distance_weight <= 32767.0f);      // (false for a NaN)
-  VK_REQUIRE(__builtin_isfinite(p->r_min) && __builtin_isfinite(p->r_max) && p->r_min >= 0.0f && p->r_min < p->r_max);
   VK_REQUIRE(__builtin_isfinite(p->t_from) && p->t_from >= 0.0f);
-  VK_REQUIRE(count >= 0 && count <= kMaxCount);
-  VK_REQUIRE((rays && ranges) || count == 0);
-  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
-  VK_REQUIRE(v->truncation_length / v->voxel_length <= 64.0f);                           // (false for a NaN)
+  CarveParams P;
+  VK_REQUIRE(range_rays_arguments(v, rays, ranges, count, pose_dev, p->flags, p->r_min, p->r_max, workspace,
+      VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION, kMaxCount, true, true, P) == VK_OK);
   if (count == 0) return VK_OK;
   hipStream_t s = vk_s(stream);
-  CarveParams P;
-  P.v = *v;
-  P.total = v->main_block_count + v->excess_block_count;
-  P.count = count;
-  P.voxel_units = (p->flags & VK_RAYS_VOXEL_UNITS) ? 1 : 0;
   P.one_observation = (p->flags & VK_RAYS_ONE_OBSERVATION) ? 1 : 0;
   P.max_blocks = p->max_blocks;
-  P.r_min = p->r_min;
-  P.r_max = p->r_max;
   P.t_from = p->t_from;
   P.cap = p->max_distance_weight;
-  P.rays = rays;
-  P.ranges = ranges;
-  P.pose = pose_dev;
   const size_t total = (size_t)P.total;
   char* at = static_cast<char*>(workspace);
   P.visits = reinterpret_cast<uint32_t*>(at);           at += align_up(total * VK_BLOCK_VOXELS * 4);

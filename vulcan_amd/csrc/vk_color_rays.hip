@@ -38,17 +38,11 @@ static_assert(kFoldSlots == 8, "a workgroup reads its slots' marks as one 64-bit
 enum { kColoured = 0, kNoColour = 1, kUnmeasured = 2, kBad = 3 };
 enum { cColoured = 0, cNoColour, cNoMeasurement, cInvalid, cBlocks, cVoxels, cNotNear, cLost, cWords = 8 };
 
-struct ColorParams
+struct ColorParams : RangeRays
 {
-  vk_volume v;
-  int total;                    // main + excess entries = pool slots
-  int count;
-  int voxel_units, one_observation;
-  float r_min, r_max, band, cap;
-  const float* rays;            // [6 * count]
-  const float* ranges;          // [count]
+  int one_observation;
+  float band, cap;
   const float* colors;          // [3 * count]
-  const vk_transform* pose;     // device, or null
   // workspace
   unsigned long long* sums;     // [2 * 512 * total]  per pool voxel: R | G << 32, B | N << 32
   uint8_t* marks;               // [total]            1 for a pool slot a coloured ray visits
@@ -68,7 +62,7 @@ struct ColorRay
 __device__ __forceinline__ ColorRay load_color_ray(const ColorParams& P, size_t i)
 {
   ColorRay out;
-  out.ray = load_range_ray(P.rays, P.ranges, i, P.pose, P.v.voxel_length, P.voxel_units != 0, P.r_min, P.r_max);
+  out.ray = load_range_ray(P, i);
   const float c0 = P.colors[3 * i], c1 = P.colors[3 * i + 1], c2 = P.colors[3 * i + 2];
   const bool has_colour = 0.0f <= c0 && c0 <= 1.0f && 0.0f <= c1 && c1 <= 1.0f && 0.0f <= c2 && c2 <= 1.0f;      // false for a NaN
   out.what = out.ray.kind == kInvalid ? kBad : (out.ray.kind == kNoMeasurement ? kUnmeasured : (has_colour ? kColoured : kNoColour));
@@ -249,33 +243,20 @@ int vk_volume_color_rays(const vk_volume* v, const float* rays, const float* ran
   // the events are used up by this call, whether or not it gets as far as its launches (as vk_volume_integrate_rays_time_next's are)
   const bool timed = g_pass_armed;
   g_pass_armed = false;
-  VK_REQUIRE(v && p && counts_dev && workspace);
-  VK_REQUIRE(volume_ok(v));
-  VK_REQUIRE((p->flags & ~(VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION)) == 0);
+  VK_REQUIRE(v && p && counts_dev);
   VK_REQUIRE(p->max_color_weight >= 1.0f && p->max_color_weight <= 32767.0f);            // (false for a NaN)
-  VK_REQUIRE(__builtin_isfinite(p->r_min) && __builtin_isfinite(p->r_max) && p->r_min >= 0.0f && p->r_min < p->r_max);
   VK_REQUIRE(__builtin_isfinite(p->band) && p->band > 0.0f);
-  VK_REQUIRE(((p->flags & VK_RAYS_VOXEL_UNITS) ? p->band : p->band / v->voxel_length) <= kMaxBand);
-  VK_REQUIRE(count >= 0 && count <= kMaxCount);
-  VK_REQUIRE((rays && ranges && colors) || count == 0);
-  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0);                       // the accumulators are zeroed 16 bytes at a time
-  VK_REQUIRE(v->truncation_length / v->voxel_length <= 64.0f);                           // (false for a NaN)
+  VK_REQUIRE(colors || count == 0);
+  ColorParams P;
+  VK_REQUIRE(range_rays_arguments(v, rays, ranges, count, pose_dev, p->flags, p->r_min, p->r_max, workspace,
+      VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION, kMaxCount, true, true, P) == VK_OK);
+  VK_REQUIRE((P.voxel_units ? p->band : p->band / v->voxel_length) <= kMaxBand);
   if (count == 0) return VK_OK;
   hipStream_t s = vk_s(stream);
-  ColorParams P;
-  P.v = *v;
-  P.total = v->main_block_count + v->excess_block_count;
-  P.count = count;
-  P.voxel_units = (p->flags & VK_RAYS_VOXEL_UNITS) ? 1 : 0;
   P.one_observation = (p->flags & VK_RAYS_ONE_OBSERVATION) ? 1 : 0;
-  P.r_min = p->r_min;
-  P.r_max = p->r_max;
   P.band = p->band;
   P.cap = p->max_color_weight;
-  P.rays = rays;
-  P.ranges = ranges;
   P.colors = colors;
-  P.pose = pose_dev;
   const size_t total = (size_t)P.total;
   char* at = static_cast<char*>(workspace);
   P.sums = reinterpret_cast<unsigned long long*>(at);   at += align_up(total * VK_BLOCK_VOXELS * 16);

@@ -120,6 +120,27 @@ __device__ __forceinline__ int vmaxi(int a, int b) { return (b > a) ? b : a; }
 __device__ __forceinline__ float vclamp(float v, float lo, float hi) { return vmin(hi, vmax(lo, v)); }
 __device__ __forceinline__ int vclampi(int v, int lo, int hi) { return vmini(hi, vmaxi(lo, v)); }
 
+// Wave64 sum without LDS: four DPP steps fold each row of 16 lanes (two quad
+// permutes, half-mirror, mirror), row_bcast:15 / row_bcast:31 carry the row
+// totals upwards; the wave's sum ends in lane 63. Six adds with a DPP operand
+// per value, against six ds_bpermute round trips for __shfl_xor. T: float or int.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_lanes(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_lanes(float v) { return __int_as_float(dpp_lanes<CTRL, ROW_MASK>(__float_as_int(v))); }
+
+template <class T>
+__device__ __forceinline__ T wave_sum_lane63(T v)
+{
+  v += dpp_lanes<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
+  v += dpp_lanes<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
+  v += dpp_lanes<0x141, 0xf>(v);   // row_half_mirror
+  v += dpp_lanes<0x140, 0xf>(v);   // row_mirror
+  v += dpp_lanes<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+  v += dpp_lanes<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
 // float -> int / short: saturating, NaN -> 0 (what the reference gets from the
 // GPU's cvt instruction where C leaves the conversion undefined). v_cvt_i32_f32
 // has exactly these semantics; inline asm keeps the out-of-range case out of

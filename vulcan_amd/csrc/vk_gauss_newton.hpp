@@ -21,27 +21,6 @@ namespace vk
 
 constexpr int kSysStride = 32;     // floats per workgroup partial: 6 gradient + 21 hessian + pad
 
-// Wave64 sum without LDS: four DPP steps fold each row of 16 lanes (two quad
-// permutes, half-mirror, mirror), row_bcast:15 / row_bcast:31 carry the row
-// totals upwards; the wave's sum ends in lane 63. Six v_add_f32 with a DPP
-// operand per value, against six ds_bpermute round trips for __shfl_xor.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_term(float v)
-{
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-
-__device__ __forceinline__ float wave_sum_lane63(float v)
-{
-  v += dpp_term<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
-  v += dpp_term<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
-  v += dpp_term<0x141, 0xf>(v);   // row_half_mirror
-  v += dpp_term<0x140, 0xf>(v);   // row_mirror
-  v += dpp_term<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v += dpp_term<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-  return v;
-}
-
 // One pixel's contribution: slots [0,6) J^T r, [6,27) the packed lower triangle of
 // J^T J in (r, c<=r) row-major order (depth_tracker.cu:163-165,208-214).
 __device__ __forceinline__ void outer_products(const float (&J)[6], float r, float (&acc)[27])

@@ -38,16 +38,10 @@ constexpr int kBias = 1 << 20;
 enum : uint8_t { kHeldBefore = 1, kVisited = 2 };
 // the words that carry the sums, behind the ones that steer the rounds
 enum { cIntegrated = cRoundWords, cNoMeasurement, cInvalid, cAllocated, cBlocks, cVoxels, cLost, cWords = 16 };
-struct RaysParams
+struct RaysParams : RangeRays
 {
-  vk_volume v;
-  int total;                    // main + excess entries = pool slots
-  int count;
-  int voxel_units, one_observation;
-  float r_min, r_max, cap;
-  const float* rays;            // [6 * count]
-  const float* ranges;          // [count]
-  const vk_transform* pose;     // device, or null
+  int one_observation;
+  float cap;
   // workspace
   unsigned long long* sums;     // [512 * total]  two's complement sum of q per pool voxel; PACKED: N << 43 | sum of (q + 2^20)
   uint32_t* visits;             // [512 * total]  N per pool voxel (not PACKED)
@@ -55,12 +49,6 @@ struct RaysParams
   int32_t* ctl;                 // [cWords]
   int32_t* counts;              // [8] output
 };
-
-// ray i as the call carries it (load_range_ray, vk_range_rays.hpp)
-__device__ __forceinline__ RangeRay load_range_ray(const RaysParams& P, size_t i)
-{
-  return vk::load_range_ray(P.rays, P.ranges, i, P.pose, P.v.voxel_length, P.voxel_units != 0, P.r_min, P.r_max);
-}
 
 // the cells of the ray's band, between ta = max(r - tr, 0) and tb = r + tr: visit(cx, cy, cz) per cell
 template <class Visit>
@@ -282,30 +270,16 @@ int vk_volume_integrate_rays(const vk_volume* v, const float* rays, const float*
   // the events are used up by this call, whether or not it gets as far as its launches (as vk_integrate_time_next's are)
   const bool timed = g_pass_armed;
   g_pass_armed = false;
-  VK_REQUIRE(v && p && counts_dev && workspace);
-  VK_REQUIRE(volume_ok(v));
-  VK_REQUIRE((p->flags & ~(VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION)) == 0);
+  VK_REQUIRE(v && p && counts_dev);
   VK_REQUIRE(p->max_rounds >= 0 && p->max_rounds <= 64);
   VK_REQUIRE(p->max_distance_weight >= 1.0f && p->max_distance_weight <= 32767.0f);      // (false for a NaN)
-  VK_REQUIRE(__builtin_isfinite(p->r_min) && __builtin_isfinite(p->r_max) && p->r_min >= 0.0f && p->r_min < p->r_max);
-  VK_REQUIRE(count >= 0 && count <= kMaxCount);
-  VK_REQUIRE((rays && ranges) || count == 0);
-  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0);                       // the accumulators are zeroed 16 bytes at a time
-  VK_REQUIRE(v->truncation_length / v->voxel_length <= 64.0f);                           // (false for a NaN)
+  RaysParams P;
+  VK_REQUIRE(range_rays_arguments(v, rays, ranges, count, pose_dev, p->flags, p->r_min, p->r_max, workspace,
+      VK_RAYS_VOXEL_UNITS | VK_RAYS_ONE_OBSERVATION, kMaxCount, true, true, P) == VK_OK);
   if (count == 0) return VK_OK;
   hipStream_t s = vk_s(stream);
-  RaysParams P;
-  P.v = *v;
-  P.total = v->main_block_count + v->excess_block_count;
-  P.count = count;
-  P.voxel_units = (p->flags & VK_RAYS_VOXEL_UNITS) ? 1 : 0;
   P.one_observation = (p->flags & VK_RAYS_ONE_OBSERVATION) ? 1 : 0;
-  P.r_min = p->r_min;
-  P.r_max = p->r_max;
   P.cap = p->max_distance_weight;
-  P.rays = rays;
-  P.ranges = ranges;
-  P.pose = pose_dev;
   const size_t total = (size_t)P.total;
   char* at = static_cast<char*>(workspace);
   P.sums = reinterpret_cast<unsigned long long*>(at);   at += align_up(total * VK_BLOCK_VOXELS * 8);

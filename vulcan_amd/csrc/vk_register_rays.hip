@@ -35,16 +35,9 @@ constexpr int kMaxCount = 1 << 22;
 enum { kSumSquares = 27, kMeasured = 28, kSampled = 29, kResiduals = 30, kBad = 31 };      // a partial row behind the 27 sums (four are ints)
 static_assert(kBad < kSysStride, "a partial row");
 
-struct RegisterRaysParams
+struct RegisterRaysParams : RangeRays
 {
-  vk_volume v;
-  int total;                    // main + excess entries = pool slots
-  int count;
-  int voxel_units;
-  float r_min, r_max, band, inverse_voxel;
-  const float* rays;            // [6 * count]
-  const float* ranges;          // [count]
-  const vk_transform* pose;     // device
+  float band, inverse_voxel;
   const int32_t* state;         // device {steps, code}, or null: a pass that finds a code returns at once
   float* partials;              // workspace: [groups][kSysStride]
   // vk_volume_register_rays_terms
@@ -69,30 +62,25 @@ __global__ __launch_bounds__(kThreads) void register_rays_pass_kernel(RegisterRa
   int measured = 0, sampled = 0, residual = 0, bad = 0;
   if (i < (size_t)P.count)
   {
-    const RangeRay ray = load_range_ray(P.rays, P.ranges, i, P.pose, P.v.voxel_length, P.voxel_units != 0, P.r_min, P.r_max);
+    const RangeRay ray = load_range_ray(P, i);
     bad = ray.kind == kInvalid ? 1 : 0;
     measured = ray.kind == kIntegrated ? 1 : 0;
     float r = 0.0f;
     float J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (measured)
     {
-      const f3 e = f3{ray.o.x + ray.r * ray.n.x, ray.o.y + ray.r * ray.n.y, ray.o.z + ray.r * ray.n.z};
-      const Cell cell = read_cell<false, true>(P.v, P.total, e, finite3(e));
-      if (cell.all_d)
+      const Residual t = residual_test(P.v, P.total, ray, P.band);
+      sampled = t.sampled ? 1 : 0;
+      if (t.residual)
       {
-        sampled = 1;
-        float gx, gy, gz;
-        const float D = trilinear_gradient(cell.distance, cell.l.fx, cell.l.fy, cell.l.fz, gx, gy, gz);
-        if (fabsf(D) < P.band)
-        {
-          residual = 1;
-          r = D;
-          const float iv = P.inverse_voxel;
-          J[0] = e.y * gz - e.z * gy;  J[1] = e.z * gx - e.x * gz;  J[2] = e.x * gy - e.y * gx;
-          J[3] = gx * iv;  J[4] = gy * iv;  J[5] = gz * iv;
-          outer_products(J, r, acc);
-          squares = r * r;
-        }
+        residual = 1;
+        r = t.D;
+        const f3 e = t.e;
+        const float gx = t.gx, gy = t.gy, gz = t.gz, iv = P.inverse_voxel;
+        J[0] = e.y * gz - e.z * gy;  J[1] = e.z * gx - e.x * gz;  J[2] = e.x * gy - e.y * gx;
+        J[3] = gx * iv;  J[4] = gy * iv;  J[5] = gz * iv;
+        outer_products(J, r, acc);
+        squares = r * r;
       }
     }
     if (TERMS)
@@ -172,26 +160,13 @@ inline int groups_of(int count) { return (count + kThreads - 1) / kThreads; }
 int prepare(const vk_volume* v, const float* rays, const float* ranges, int32_t count, const vk_transform* pose_dev,
     const vk_register_rays_params* p, void* workspace, RegisterRaysParams& P)
 {
-  VK_REQUIRE(v && p && pose_dev && workspace);
-  VK_REQUIRE(volume_ok(v));
-  VK_REQUIRE((p->flags & ~VK_RAYS_VOXEL_UNITS) == 0);
+  VK_REQUIRE(v && p);
   VK_REQUIRE(p->iterations >= 1 && p->iterations <= 64);
   VK_REQUIRE(p->max_abs_distance > 0.0f && p->max_abs_distance <= 1.0f);        // (false for a NaN)
-  VK_REQUIRE(__builtin_isfinite(p->r_min) && __builtin_isfinite(p->r_max) && p->r_min >= 0.0f && p->r_min < p->r_max);
-  VK_REQUIRE(count >= 0 && count <= kMaxCount);
-  VK_REQUIRE((rays && ranges) || count == 0);
-  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
-  P.v = *v;
-  P.total = v->main_block_count + v->excess_block_count;
-  P.count = count;
-  P.voxel_units = (p->flags & VK_RAYS_VOXEL_UNITS) ? 1 : 0;
-  P.r_min = p->r_min;
-  P.r_max = p->r_max;
+  VK_REQUIRE(range_rays_arguments(v, rays, ranges, count, pose_dev, p->flags, p->r_min, p->r_max, workspace, VK_RAYS_VOXEL_UNITS,
+      kMaxCount, false, false, P) == VK_OK);
   P.band = p->max_abs_distance;
   P.inverse_voxel = 1.0f / v->voxel_length;
-  P.rays = rays;
-  P.ranges = ranges;
-  P.pose = pose_dev;
   P.state = nullptr;
   P.partials = static_cast<float*>(workspace);
   P.residuals = P.jacobians = nullptr;

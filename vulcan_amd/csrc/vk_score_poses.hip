@@ -39,33 +39,12 @@ constexpr float kUnit = 1048576.0f;            // 2^20: the sums' unit
 static_assert(sizeof(vk_pose_score) == 32 && sizeof(vk_score_poses_params) == 24, "ABI");
 static_assert(kPoseTile <= kWave && kSumPoses * kSumSlices == kThreads, "shapes");
 
-struct ScorePosesParams
+struct ScorePosesParams : RangeRays   // (pose: the first of the candidates, device [pose_count])
 {
-  vk_volume v;
-  int total;                    // main + excess entries = pool slots
-  int count, pose_count;
-  int voxel_units;
-  float r_min, r_max, band;
-  const float* rays;            // [6 * count]
-  const float* ranges;          // [count]
-  const vk_transform* poses;    // device [pose_count]
+  int pose_count;
+  float band;
   vk_pose_score* partials;      // workspace: [ray tiles][pose_count]
 };
-
-// the six DPP steps of wave_sum_lane63 (vk_gauss_newton.hpp) on an int: the wave's sum ends in lane 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_int(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
-
-__device__ __forceinline__ int wave_sum_int_lane63(int v)
-{
-  v += dpp_int<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
-  v += dpp_int<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
-  v += dpp_int<0x141, 0xf>(v);   // row_half_mirror
-  v += dpp_int<0x140, 0xf>(v);   // row_mirror
-  v += dpp_int<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v += dpp_int<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-  return v;
-}
 
 // One lane per ray, a loop over the workgroup's poses: blockIdx.x the ray tile, blockIdx.y the pose tile.
 __global__ __launch_bounds__(kThreads) void score_poses_pass_kernel(ScorePosesParams P)
@@ -79,33 +58,27 @@ __global__ __launch_bounds__(kThreads) void score_poses_pass_kernel(ScorePosesPa
   const int wave = (int)(threadIdx.x >> 6);
   for (int k = 0; k < poses_here; ++k)
   {
-    const RangeRay ray = load_range_ray(P.rays, P.ranges, at, P.poses + (first + k), P.v.voxel_length, P.voxel_units != 0, P.r_min, P.r_max);
+    const RangeRay ray = load_range_ray(P, at, P.pose + (first + k));
     const bool bad = live && ray.kind == kInvalid;
     const bool measured = live && ray.kind == kIntegrated;
     bool sampled = false, residual = false;
     int term_abs = 0, term_square = 0;
     if (measured)
     {
-      const f3 e = f3{ray.o.x + ray.r * ray.n.x, ray.o.y + ray.r * ray.n.y, ray.o.z + ray.r * ray.n.z};
-      const Cell cell = read_cell<false, true>(P.v, P.total, e, finite3(e));
-      if (cell.all_d)
+      const Residual t = residual_test(P.v, P.total, ray, P.band);       // (its gradient is dead code here)
+      sampled = t.sampled;
+      residual = t.residual;
+      if (residual)
       {
-        sampled = true;
-        float gx, gy, gz;
-        const float D = trilinear_gradient(cell.distance, cell.l.fx, cell.l.fy, cell.l.fz, gx, gy, gz);    // (the gradient is dead code)
-        if (fabsf(D) < P.band)
-        {
-          residual = true;
-          term_abs = (int)rintf(fabsf(D) * kUnit);           // < 2^20: band <= 1
-          term_square = (int)rintf((D * D) * kUnit);
-        }
+        term_abs = (int)rintf(fabsf(t.D) * kUnit);           // < 2^20: band <= 1
+        term_square = (int)rintf((t.D * t.D) * kUnit);
       }
     }
     // the four counts are of flags: a ballot and a population count each; the two sums fit 32 bits inside a wave
     const int measured_here = __popcll(__ballot(measured)), sampled_here = __popcll(__ballot(sampled));
     const int residuals_here = __popcll(__ballot(residual)), bad_here = __popcll(__ballot(bad));
-    term_abs = wave_sum_int_lane63(term_abs);
-    term_square = wave_sum_int_lane63(term_square);
+    term_abs = wave_sum_lane63(term_abs);
+    term_square = wave_sum_lane63(term_square);
     if (lane_id() == 63)
     {
       int32_t* row = found[wave][k];
@@ -227,28 +200,16 @@ size_t vk_volume_score_poses_workspace_bytes(int32_t count, int32_t pose_count)
 int vk_volume_score_poses(const vk_volume* v, const float* rays, const float* ranges, int32_t count, const vk_transform* poses_dev,
     int32_t pose_count, const vk_score_poses_params* p, vk_pose_score* scores_dev, void* workspace, void* stream)
 {
-  VK_REQUIRE(v && p && poses_dev && scores_dev && workspace);
-  VK_REQUIRE(volume_ok(v));
-  VK_REQUIRE((p->flags & ~VK_RAYS_VOXEL_UNITS) == 0);
+  VK_REQUIRE(v && p && scores_dev);
   VK_REQUIRE(p->min_residuals >= 1);
   VK_REQUIRE(p->max_abs_distance > 0.0f && p->max_abs_distance <= 1.0f);        // (false for a NaN)
-  VK_REQUIRE(__builtin_isfinite(p->r_min) && __builtin_isfinite(p->r_max) && p->r_min >= 0.0f && p->r_min < p->r_max);
   VK_REQUIRE(shape_ok(count, pose_count));
-  VK_REQUIRE((rays && ranges) || count == 0);
-  VK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
-  if (count == 0) return VK_OK;
   ScorePosesParams P;
-  P.v = *v;
-  P.total = v->main_block_count + v->excess_block_count;
-  P.count = count;
+  VK_REQUIRE(range_rays_arguments(v, rays, ranges, count, poses_dev, p->flags, p->r_min, p->r_max, workspace, VK_RAYS_VOXEL_UNITS,
+      kMaxCount, false, false, P) == VK_OK);
+  if (count == 0) return VK_OK;
   P.pose_count = pose_count;
-  P.voxel_units = (p->flags & VK_RAYS_VOXEL_UNITS) ? 1 : 0;
-  P.r_min = p->r_min;
-  P.r_max = p->r_max;
   P.band = p->max_abs_distance;
-  P.rays = rays;
-  P.ranges = ranges;
-  P.poses = poses_dev;
   P.partials = static_cast<vk_pose_score*>(workspace);
   hipStream_t s = vk_s(stream);
   const int tiles = tiles_of(count);

@@ -14,6 +14,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <array>
 #include <vector>
 #include <vk.h>
 #include <vulcan/buffer.h>
@@ -463,9 +464,21 @@ class Volume
     Buffer<int> merge_counts_;
     Buffer<unsigned char> merge_pose_workspace_;   // Merge through a pose: again for another pair of sizes
     Buffer<int> merge_pose_counts_;
+    // a registration's device buffers, and what is done with them before and after the loop
+    struct RegistrationBuffers
+    {
+      Buffer<float> floats;                        // the pose (32), the system (48), the update (6)
+      Buffer<int> ints;                            // the state (2), the counts (4)
+      vk_transform* pose = nullptr;
+      float* system = nullptr;
+      float* update = nullptr;
+      int* state = nullptr;
+      int* counts = nullptr;
+      void Begin(const Transform* seed);           // allocated by the first call; a seed is uploaded and the state zeroed
+      Registration Read() const;                   // one blocking read of each buffer
+    };
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
-    Buffer<float> register_floats_;                // the pose (32), the system (48), the update (6)
-    Buffer<int> register_ints_;                    // the state (2), the counts (4)
+    RegistrationBuffers register_;
     mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays, CarveRays, ColorRays: the pose on the device (32)
     Buffer<unsigned char> rays_workspace_;         // IntegrateRays: allocated by the first call
     Buffer<int> rays_counts_;
@@ -474,8 +487,7 @@ class Volume
     Buffer<unsigned char> color_rays_workspace_;   // ColorRays: allocated by the first call
     Buffer<int> color_rays_counts_;
     mutable Buffer<unsigned char> register_rays_workspace_;   // RegisterRays: again for another number of rays
-    mutable Buffer<float> register_rays_floats_;              // the pose (32), the system (48), the update (6)
-    mutable Buffer<int> register_rays_ints_;                  // the state (2), the counts (4)
+    mutable RegistrationBuffers register_rays_;               // RegisterRays and LocalizeRays
     mutable Buffer<unsigned char> score_poses_workspace_;     // ScorePoses: again for another number of rays or poses
     mutable Buffer<unsigned char> score_poses_scores_;        // [poses] vk_pose_score
     mutable Buffer<float> score_poses_poses_;                 // [poses] vk_transform
@@ -499,11 +511,15 @@ class Volume
     mutable bool pool_exhaustion_noted_ = false;
     void NotePoolExhaustion(int32_t dropped) const;
     mutable int32_t* normals_late_;     // pinned: vk_view_bounds.late_host of the attached tracer's record
+    // a call's workspace of `bytes` (again for another size; 0: no call follows) and its `count` counts, allocated by the first
+    static void Sized(Buffer<unsigned char>& workspace, size_t bytes, Buffer<int>& counts, size_t count = 8);
 
   private:
     // what the volume operations above share on the caller's side
     void AssertNoFrameAnnounced() const;                               // between SetView calls only
     const vk_transform* PoseOnDevice(const Transform* pose) const;     // uploaded into sample_pose_; null stays null
+    static int RayFlags(bool voxel_units, bool one_observation = false);           // VK_RAYS_*
+    static std::array<int32_t, 8> EightCounts(const Buffer<int>& counts_dev);      // one blocking read
     int ScorePosesBuffers(int count, const std::vector<Transform>& poses) const;    // the candidates uploaded: how many
     void VoidMadeAhead() const;                 // the raycast bounds and the light preparation made for the old table
     void EmptyVisibleList() const;              // VK_CTR_VISIBLE is 0 until the next SetView

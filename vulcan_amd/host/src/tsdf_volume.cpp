@@ -349,6 +349,58 @@ void Volume::EmptyVisibleList() const
   visible_count_stale_ = false;
 }
 
+int Volume::RayFlags(bool voxel_units, bool one_observation)
+{
+  return (voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+}
+
+void Volume::Sized(Buffer<unsigned char>& workspace, size_t bytes, Buffer<int>& counts, size_t count)
+{
+  if (bytes != 0 && workspace.GetSize() != bytes) workspace.Resize(bytes);
+  if (counts.GetSize() == 0) counts.Resize(count);
+}
+
+std::array<int32_t, 8> Volume::EightCounts(const Buffer<int>& counts_dev)
+{
+  std::array<int32_t, 8> counts;
+  counts_dev.CopyToHost(counts.data());
+  return counts;
+}
+
+void Volume::RegistrationBuffers::Begin(const Transform* seed)
+{
+  static_assert(sizeof(vk_transform) == 32 * sizeof(float), "vk_transform layout");
+  if (floats.GetSize() == 0) floats.Resize(32 + 48 + 8);
+  if (ints.GetSize() == 0) ints.Resize(2 + 4);
+  pose = reinterpret_cast<vk_transform*>(floats.GetData());
+  system = floats.GetData() + 32;
+  update = system + 48;
+  state = ints.GetData();
+  counts = state + 2;
+  if (!seed) return;
+  const vk_transform start = seed->ToVk();
+  VK_ASSERT(vk_transform_upload(pose, &start, Device::GetStream()));
+  VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
+}
+
+Registration Volume::RegistrationBuffers::Read() const
+{
+  std::vector<float> host_floats(floats.GetSize());
+  std::vector<int> host_ints(ints.GetSize());
+  floats.CopyToHost(host_floats.data());
+  ints.CopyToHost(host_ints.data());
+  vk_transform result;
+  std::memcpy(&result, host_floats.data(), sizeof(result));
+  Registration out;
+  out.pose = Transform::FromVk(result);
+  out.steps = host_ints[0];
+  out.converged = host_ints[1] == 1;
+  out.overlap = host_ints[1] != VK_REGISTER_NO_OVERLAP;
+  out.residuals = host_ints[4];
+  out.rms = host_ints[4] > 0 ? std::sqrt(host_floats[32 + 42] / float(host_ints[4])) : 0.0f;
+  return out;
+}
+
 ReleaseCounts Volume::ReleaseBlocks(const ReleaseRule& rule)
 {
   AssertNoFrameAnnounced();
@@ -398,8 +450,7 @@ void Volume::MergeRounds(const Volume& other, vk_merge_params& merge, Buffer<uns
   AssertNoFrameAnnounced();
   other.AssertNoFrameAnnounced();
   VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
-  if (workspace.GetSize() != bytes) workspace.Resize(bytes);
-  if (counts_dev.GetSize() == 0) counts_dev.Resize(count);
+  Sized(workspace, bytes, counts_dev, size_t(count));
   VoidMadeAhead();
   const vk_volume dst = ToVk(), src = other.ToVk();
   int32_t counters[VK_CTR_PUBLIC];
@@ -480,38 +531,17 @@ Registration Volume::Register(const Volume& other, const Transform& start, int i
   p.pad = 0;
   const size_t bytes = vk_volume_register_workspace_bytes(other.main_block_count_, other.excess_block_count_);
   if (register_workspace_.GetSize() != bytes) register_workspace_.Resize(bytes);
-  if (register_floats_.GetSize() == 0) register_floats_.Resize(32 + 48 + 8);
-  if (register_ints_.GetSize() == 0) register_ints_.Resize(2 + 4);
-  vk_transform* pose = reinterpret_cast<vk_transform*>(register_floats_.GetData());
-  float* system = register_floats_.GetData() + 32;
-  float* update = system + 48;
-  int* state = register_ints_.GetData();
-  int* counts = state + 2;
-  const vk_transform seed = start.ToVk();
+  RegistrationBuffers& b = register_;
+  b.Begin(&start);
   const vk_volume dst = ToVk(), src = other.ToVk();
-  VK_ASSERT(vk_transform_upload(pose, &seed, Device::GetStream()));
-  VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
-  VK_ASSERT(vk_volume_register(&dst, &src, pose, &p, system, state, counts, update, register_workspace_.GetData(), Device::GetStream()));
-  std::vector<float> floats(register_floats_.GetSize());
-  std::vector<int> ints(register_ints_.GetSize());
-  register_floats_.CopyToHost(floats.data());
-  register_ints_.CopyToHost(ints.data());
-  vk_transform result;
-  std::memcpy(&result, floats.data(), sizeof(result));
-  Registration out;
-  out.pose = Transform::FromVk(result);
-  out.steps = ints[0];
-  out.converged = ints[1] == 1;
-  out.overlap = ints[1] != VK_REGISTER_NO_OVERLAP;
-  out.residuals = ints[4];
-  out.rms = ints[4] > 0 ? std::sqrt(floats[32 + 42] / float(ints[4])) : 0.0f;
-  return out;
+  VK_ASSERT(vk_volume_register(&dst, &src, b.pose, &p, b.system, b.state, b.counts, b.update, register_workspace_.GetData(),
+      Device::GetStream()));
+  return b.Read();
 }
 
 // the candidates on the device, and the scores and the workspace sized for them: how many poses there are
 int Volume::ScorePosesBuffers(int count, const std::vector<Transform>& poses) const
 {
-  static_assert(sizeof(vk_transform) == 32 * sizeof(float), "vk_transform layout");
   const int pose_count = int(poses.size());
   const size_t bytes = vk_volume_score_poses_workspace_bytes(count, pose_count);
   if (bytes != 0 && score_poses_workspace_.GetSize() != bytes) score_poses_workspace_.Resize(bytes);
@@ -535,7 +565,7 @@ std::vector<PoseScore> Volume::ScorePoses(const Ray* rays_dev, const float* rang
   static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
   // the volume is only read: allowed while a frame is announced, like Sample and RegisterRays
   vk_score_poses_params p;
-  p.flags = options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0;
+  p.flags = RayFlags(options.voxel_units);
   p.min_residuals = 1;
   p.r_min = options.r_min;
   p.r_max = options.r_max;
@@ -560,7 +590,7 @@ Localization Volume::LocalizeRays(const Ray* rays_dev, const float* ranges_dev, 
     int min_residuals, const RegisterRaysOptions& options) const
 {
   vk_score_poses_params sp;
-  sp.flags = options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0;
+  sp.flags = RayFlags(options.voxel_units);
   sp.min_residuals = min_residuals;
   sp.r_min = options.r_min;
   sp.r_max = options.r_max;
@@ -576,47 +606,26 @@ Localization Volume::LocalizeRays(const Ray* rays_dev, const float* ranges_dev, 
   const int pose_count = ScorePosesBuffers(count, poses);
   const size_t bytes = vk_volume_register_rays_workspace_bytes(count);
   if (bytes != 0 && register_rays_workspace_.GetSize() != bytes) register_rays_workspace_.Resize(bytes);
-  if (register_rays_floats_.GetSize() == 0) register_rays_floats_.Resize(32 + 48 + 8);
-  if (register_rays_ints_.GetSize() == 0) register_rays_ints_.Resize(2 + 4);
   if (score_poses_best_.GetSize() == 0) score_poses_best_.Resize(1);
-  vk_transform* pose = reinterpret_cast<vk_transform*>(register_rays_floats_.GetData());
-  float* system = register_rays_floats_.GetData() + 32;
-  float* update = system + 48;
-  int* state = register_rays_ints_.GetData();
-  int* counts = state + 2;
+  RegistrationBuffers& b = register_rays_;
   Localization out = {};
   out.best_index = -1;
   const float* rays = reinterpret_cast<const float*>(rays_dev);
   const vk_transform* candidates = reinterpret_cast<const vk_transform*>(score_poses_poses_.GetData());
   vk_pose_score* scores = reinterpret_cast<vk_pose_score*>(score_poses_scores_.GetData());
-  const vk_transform seed = Transform().ToVk();
+  const Transform identity;
   const vk_volume v = ToVk();
   // score, choose, refine: one enqueue. The identity stands in the pose buffer for the case that nothing is chosen
-  if (count > 0)
-  {
-    VK_ASSERT(vk_transform_upload(pose, &seed, Device::GetStream()));
-    VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
-  }
+  b.Begin(count > 0 ? &identity : nullptr);        // no rays: no upload
   VK_ASSERT(vk_volume_score_poses(&v, rays, ranges_dev, count, candidates, pose_count, &sp, scores, score_poses_workspace_.GetData(),
       Device::GetStream()));
   if (count == 0) return out;                      // nothing was launched and nothing was written
-  VK_ASSERT(vk_volume_score_poses_best(scores, candidates, pose_count, &sp, score_poses_best_.GetData(), pose, Device::GetStream()));
-  VK_ASSERT(vk_volume_register_rays(&v, rays, ranges_dev, count, pose, &p, system, state, counts, update,
+  VK_ASSERT(vk_volume_score_poses_best(scores, candidates, pose_count, &sp, score_poses_best_.GetData(), b.pose, Device::GetStream()));
+  VK_ASSERT(vk_volume_register_rays(&v, rays, ranges_dev, count, b.pose, &p, b.system, b.state, b.counts, b.update,
       register_rays_workspace_.GetData(), Device::GetStream()));
   score_poses_best_.CopyToHost(&out.best_index);
   if (out.best_index < 0) return out;              // what the loop refined from the identity is not a result
-  std::vector<float> floats(register_rays_floats_.GetSize());
-  std::vector<int> ints(register_rays_ints_.GetSize());
-  register_rays_floats_.CopyToHost(floats.data());
-  register_rays_ints_.CopyToHost(ints.data());
-  vk_transform result;
-  std::memcpy(&result, floats.data(), sizeof(result));
-  out.pose = Transform::FromVk(result);
-  out.steps = ints[0];
-  out.converged = ints[1] == 1;
-  out.overlap = ints[1] != VK_REGISTER_NO_OVERLAP;
-  out.residuals = ints[4];
-  out.rms = ints[4] > 0 ? std::sqrt(floats[32 + 42] / float(ints[4])) : 0.0f;
+  static_cast<Registration&>(out) = b.Read();
   return out;
 }
 
@@ -654,23 +663,20 @@ IntegrateRaysCounts Volume::IntegrateRays(const Ray* rays_dev, const float* rang
   AssertNoFrameAnnounced();
   IntegrateRaysCounts out = {};
   vk_integrate_rays_params p;
-  p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+  p.flags = RayFlags(options.voxel_units, options.one_observation);
   p.max_rounds = options.max_rounds;
   p.r_min = options.r_min;
   p.r_max = options.r_max;
   p.max_distance_weight = options.max_distance_weight;
   p.pad = 0;
-  const size_t bytes = vk_volume_integrate_rays_workspace_bytes(main_block_count_, excess_block_count_);
-  if (rays_workspace_.GetSize() != bytes) rays_workspace_.Resize(bytes);
-  if (rays_counts_.GetSize() == 0) rays_counts_.Resize(8);
+  Sized(rays_workspace_, vk_volume_integrate_rays_workspace_bytes(main_block_count_, excess_block_count_), rays_counts_);
   const vk_transform* pose_dev = PoseOnDevice(count > 0 ? pose : nullptr);      // no rays: no upload
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_integrate_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose_dev, &p, rays_counts_.GetData(),
       rays_workspace_.GetData(), Device::GetStream()));
   if (count == 0) return out;                      // nothing was launched and the counts were not written
   VoidMadeAhead();
-  int32_t counts[8];
-  rays_counts_.CopyToHost(counts);
+  const std::array<int32_t, 8> counts = EightCounts(rays_counts_);
   out.integrated = counts[0];
   out.unmeasured = counts[1];
   out.invalid = counts[2];
@@ -693,23 +699,20 @@ CarveRaysCounts Volume::CarveRays(const Ray* rays_dev, const float* ranges_dev, 
   AssertNoFrameAnnounced();
   CarveRaysCounts out = {};
   vk_carve_rays_params p;
-  p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+  p.flags = RayFlags(options.voxel_units, options.one_observation);
   p.max_blocks = options.max_blocks;
   p.r_min = options.r_min;
   p.r_max = options.r_max;
   p.t_from = options.t_from;
   p.max_distance_weight = options.max_distance_weight;
-  const size_t bytes = vk_volume_carve_rays_workspace_bytes(main_block_count_, excess_block_count_);
-  if (carve_workspace_.GetSize() != bytes) carve_workspace_.Resize(bytes);
-  if (carve_counts_.GetSize() == 0) carve_counts_.Resize(8);
+  Sized(carve_workspace_, vk_volume_carve_rays_workspace_bytes(main_block_count_, excess_block_count_), carve_counts_);
   const vk_transform* pose_dev = PoseOnDevice(count > 0 ? pose : nullptr);      // no rays: no upload
   const vk_volume v = ToVk();
   VK_ASSERT(vk_volume_carve_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose_dev, &p, carve_counts_.GetData(),
       carve_workspace_.GetData(), Device::GetStream()));
   if (count == 0) return out;                      // nothing was launched and the counts were not written
   // the table and the visible list are as they were: nothing made ahead is void
-  int32_t counts[8];
-  carve_counts_.CopyToHost(counts);
+  const std::array<int32_t, 8> counts = EightCounts(carve_counts_);
   out.carved = counts[0];
   out.nothing = counts[1];
   out.unmeasured = counts[2];
@@ -729,22 +732,19 @@ ColorRaysCounts Volume::ColorRays(const Ray* rays_dev, const float* ranges_dev, 
   ColorRaysCounts out = {};
   const vk_volume v = ToVk();
   vk_color_rays_params p;
-  p.flags = (options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0) | (options.one_observation ? VK_RAYS_ONE_OBSERVATION : 0);
+  p.flags = RayFlags(options.voxel_units, options.one_observation);
   p.r_min = options.r_min;
   p.r_max = options.r_max;
   p.band = options.band != 0.0f ? options.band : (options.voxel_units ? v.truncation_length / v.voxel_length : v.truncation_length);
   p.max_color_weight = options.max_color_weight;
   p.pad = 0;
-  const size_t bytes = vk_volume_color_rays_workspace_bytes(main_block_count_, excess_block_count_);
-  if (color_rays_workspace_.GetSize() != bytes) color_rays_workspace_.Resize(bytes);
-  if (color_rays_counts_.GetSize() == 0) color_rays_counts_.Resize(8);
+  Sized(color_rays_workspace_, vk_volume_color_rays_workspace_bytes(main_block_count_, excess_block_count_), color_rays_counts_);
   const vk_transform* pose_dev = PoseOnDevice(count > 0 ? pose : nullptr);      // no rays: no upload
   VK_ASSERT(vk_volume_color_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, reinterpret_cast<const float*>(colors_dev),
       count, pose_dev, &p, color_rays_counts_.GetData(), color_rays_workspace_.GetData(), Device::GetStream()));
   if (count == 0) return out;                      // nothing was launched and the counts were not written
   // the table and the visible list are as they were: nothing made ahead is void
-  int32_t counts[8];
-  color_rays_counts_.CopyToHost(counts);
+  const std::array<int32_t, 8> counts = EightCounts(color_rays_counts_);
   out.coloured = counts[0];
   out.colourless = counts[1];
   out.unmeasured = counts[2];
@@ -762,7 +762,7 @@ Registration Volume::RegisterRays(const Ray* rays_dev, const float* ranges_dev, 
   static_assert(sizeof(Ray) == 6 * sizeof(float), "Ray layout");
   // the volume is only read: allowed while a frame is announced, like Sample and CastRays
   vk_register_rays_params p;
-  p.flags = options.voxel_units ? VK_RAYS_VOXEL_UNITS : 0;
+  p.flags = RayFlags(options.voxel_units);
   p.iterations = options.iterations;
   p.r_min = options.r_min;
   p.r_max = options.r_max;
@@ -770,37 +770,14 @@ Registration Volume::RegisterRays(const Ray* rays_dev, const float* ranges_dev, 
   p.pad = 0;
   const size_t bytes = vk_volume_register_rays_workspace_bytes(count);
   if (bytes != 0 && register_rays_workspace_.GetSize() != bytes) register_rays_workspace_.Resize(bytes);
-  if (register_rays_floats_.GetSize() == 0) register_rays_floats_.Resize(32 + 48 + 8);
-  if (register_rays_ints_.GetSize() == 0) register_rays_ints_.Resize(2 + 4);
-  vk_transform* pose = reinterpret_cast<vk_transform*>(register_rays_floats_.GetData());
-  float* system = register_rays_floats_.GetData() + 32;
-  float* update = system + 48;
-  int* state = register_rays_ints_.GetData();
-  int* counts = state + 2;
-  Registration out = {};
-  out.pose = start;
-  const vk_transform seed = start.ToVk();
+  RegistrationBuffers& b = register_rays_;
+  b.Begin(count > 0 ? &start : nullptr);           // no rays: no upload
   const vk_volume v = ToVk();
-  if (count > 0)                                   // no rays: no upload
-  {
-    VK_ASSERT(vk_transform_upload(pose, &seed, Device::GetStream()));
-    VK_ASSERT(vk_memset(state, 0, 2 * sizeof(int), Device::GetStream()));
-  }
-  VK_ASSERT(vk_volume_register_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, pose, &p, system, state, counts, update,
-      register_rays_workspace_.GetData(), Device::GetStream()));
-  if (count == 0) return out;                      // nothing was launched and nothing was written
-  std::vector<float> floats(register_rays_floats_.GetSize());
-  std::vector<int> ints(register_rays_ints_.GetSize());
-  register_rays_floats_.CopyToHost(floats.data());
-  register_rays_ints_.CopyToHost(ints.data());
-  vk_transform result;
-  std::memcpy(&result, floats.data(), sizeof(result));
-  out.pose = Transform::FromVk(result);
-  out.steps = ints[0];
-  out.converged = ints[1] == 1;
-  out.overlap = ints[1] != VK_REGISTER_NO_OVERLAP;
-  out.residuals = ints[4];
-  out.rms = ints[4] > 0 ? std::sqrt(floats[32 + 42] / float(ints[4])) : 0.0f;
+  VK_ASSERT(vk_volume_register_rays(&v, reinterpret_cast<const float*>(rays_dev), ranges_dev, count, b.pose, &p, b.system, b.state,
+      b.counts, b.update, register_rays_workspace_.GetData(), Device::GetStream()));
+  if (count > 0) return b.Read();
+  Registration out = {};                           // nothing was launched and nothing was written
+  out.pose = start;
   return out;
 }
 

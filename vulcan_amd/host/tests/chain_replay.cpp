@@ -116,14 +116,15 @@ class ReplayVolume : public Volume
             main, excess), merge_pose_counts_, 8);
       else if (op == "register_terms")
       {
-        Sized(register_workspace_, vk_volume_register_workspace_bytes(other->GetMainBlockCount(), other->GetExcessBlockCount()),
-            register_ints_, 2 + 4);
-        if (register_floats_.GetSize() == 0) register_floats_.Resize(32 + 48 + 8);
+        const size_t bytes = vk_volume_register_workspace_bytes(other->GetMainBlockCount(), other->GetExcessBlockCount());
+        if (register_workspace_.GetSize() != bytes) register_workspace_.Resize(bytes);
+        register_.Begin(nullptr);
       }
       else if (op == "register_rays_terms")
       {
-        Sized(register_rays_workspace_, vk_volume_register_rays_workspace_bytes(step.Int("count")), register_rays_ints_, 2 + 4);
-        if (register_rays_floats_.GetSize() == 0) register_rays_floats_.Resize(32 + 48 + 8);
+        const size_t bytes = vk_volume_register_rays_workspace_bytes(step.Int("count"));
+        if (bytes != 0 && register_rays_workspace_.GetSize() != bytes) register_rays_workspace_.Resize(bytes);
+        register_rays_.Begin(nullptr);
       }
       else if (op == "score_poses")
       {
@@ -146,40 +147,33 @@ class ReplayVolume : public Volume
       Soil(dirt, merge_workspace_);
       Soil(dirt, merge_pose_workspace_);
       Soil(dirt, register_workspace_);
-      Soil(dirt, register_floats_);
+      Soil(dirt, register_.floats);
       Soil(dirt, sample_pose_);
       Soil(dirt, rays_workspace_);
       Soil(dirt, carve_workspace_);
       Soil(dirt, color_rays_workspace_);
       Soil(dirt, register_rays_workspace_);
-      Soil(dirt, register_rays_floats_);
+      Soil(dirt, register_rays_.floats);
       Soil(dirt, score_poses_workspace_);
       Soil(dirt, score_poses_scores_);
       Soil(dirt, score_poses_poses_);
       SoilCounts(dirt, release_counts_);
       SoilCounts(dirt, merge_counts_);
       SoilCounts(dirt, merge_pose_counts_);
-      SoilCounts(dirt, register_ints_);
+      SoilCounts(dirt, register_.ints);
       SoilCounts(dirt, rays_counts_);
       SoilCounts(dirt, carve_counts_);
       SoilCounts(dirt, color_rays_counts_);
-      SoilCounts(dirt, register_rays_ints_);
+      SoilCounts(dirt, register_rays_.ints);
       SoilCounts(dirt, score_poses_best_);
     }
 
     // the state (2) and the counts (4) a loop left in the class's own buffer
     void LoopInts(bool rays, int32_t* out) const
     {
-      const Buffer<int>& ints = rays ? register_rays_ints_ : register_ints_;
+      const Buffer<int>& ints = rays ? register_rays_.ints : register_.ints;
       VULCAN_ASSERT_MSG(ints.GetSize() == 6, "the loop left no state");
       ints.CopyToHost(out);
-    }
-
-  private:
-    static void Sized(Buffer<unsigned char>& workspace, size_t bytes, Buffer<int>& counts, size_t count)
-    {
-      if (bytes != 0 && workspace.GetSize() != bytes) workspace.Resize(bytes);
-      if (counts.GetSize() == 0) counts.Resize(count);
     }
 };
 
