@@ -1334,7 +1334,8 @@ typedef struct vk_merge_params {
  * vk_volume_merge_workspace_bytes(src main, src excess) bytes (0 for sizes that are not a volume's), need not be
  * initialised: the one thing a workspace carries from call to call is what a CONTINUE call takes over. 5 + 4 * max_rounds
  * short launches on `stream` and one pass of one wave per source block over the two voxel pools. Moving a replica
- * between devices is the caller's: both volumes' buffers are on the stream's device. */
+ * between devices is the caller's: both volumes' buffers are on the stream's device (vk_volume_pack below makes the replica
+ * two compact arrays to copy, and vk_volume_merge_packed merges them). */
 VK_API size_t vk_volume_merge_workspace_bytes(int32_t src_main, int32_t src_excess);
 VK_API int vk_volume_merge(const vk_volume* dst, const vk_volume* src, const vk_merge_params* p,
     int32_t* counts_dev /* [6] */, void* workspace, void* stream);
@@ -1392,6 +1393,75 @@ typedef struct vk_merge_pose_params {
 VK_API size_t vk_volume_merge_posed_workspace_bytes(int32_t src_main, int32_t src_excess, int32_t dst_main, int32_t dst_excess);
 VK_API int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_merge_pose_params* p,
     int32_t* counts_dev /* [8] */, void* workspace, void* stream);
+
+/* --------------------------------------------------------------- pack the blocks -- */
+
+typedef struct vk_block_pack {
+  int32_t   capacity;   /* blocks the two arrays can hold */
+  int32_t   pad;
+  int16_t*  origins;    /* device [4 * capacity], 8-byte aligned: block x, y, z, 0 */
+  vk_voxel* voxels;     /* device [512 * capacity], 16-byte aligned; NULL: count only */
+} vk_block_pack;
+
+enum { VK_PACK_SKIP_UNOBSERVED = 1, VK_PACK_BOX = 2 };
+
+typedef struct vk_pack_rule {
+  int32_t flags;        /* VK_PACK_* or'ed */
+  int16_t lo[3], hi[3]; /* BOX: block coordinates, inclusive */
+} vk_pack_rule;
+
+/* The blocks of a volume, compact and in a defined order: what a caller writes to a file, hands to another device or
+ * process, and merges there (the receiving side follows below) — at the cost of the blocks that exist, not of the pool. No
+ * upstream counterpart (its Volume is a process-wide singleton that never leaves its buffers, ref: src/volume.cu:17-21;
+ * the chain walk is that of src/volume.cu:183-190). The definition is this comment; tests/pack_reference.py states it on
+ * the CPU and the device is held to it byte for byte.
+ * The call only READS the volume: it is allowed while a frame is announced (vk_requests_ahead), and no counter changes.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): v, pack, counts_dev or workspace null, a volume that vk_volume_merge
+ * would refuse for a null buffer, its sizes or its alignment, rule->flags with an unknown bit, BOX with lo[a] > hi[a] on an
+ * axis, capacity < 0, and with voxels != NULL: origins null or not 8-byte aligned, voxels not 16-byte aligned. rule == NULL:
+ * every block.
+ * (source blocks) vk_volume_merge's: an entry that is reachable from a main bucket along `next` and has data >= 0.
+ * (selection) a source block is SELECTED unless BOX is set and origin[a] < lo[a] or origin[a] > hi[a] for some a, or — of
+ * the blocks the box leaves — SKIP_UNOBSERVED is set and all 512 voxels have distance_weight == 0 and color_weight == 0
+ * (vk_volume_merge's test; one extra read of those blocks). Only stored values are compared.
+ * (order) the selected blocks in ascending order of their table entry index: main entries first, then excess entries. The
+ * positions come from an ordered scan (vk_compact_offsets); no atomic decides one, the pack is the same every time.
+ * (the pack) with written = min(selected, capacity): block k < written is that entry's origin in origins[4k .. 4k+2],
+ * origins[4k+3] = 0, and the 10 240 bytes of pool slot `data` in voxels[512k ..], byte for byte. Nothing is written at or
+ * behind block `written`. With voxels == NULL nothing is written at all and written = 0: the call only counts, so that
+ * the caller can size the pack. Origins within a pack are distinct.
+ * counts_dev: device int32[4] = {source blocks, selected, written, blocks the box left that were skipped as unobserved}.
+ * workspace: device, vk_volume_pack_workspace_bytes(main, excess) bytes (0 for sizes that are not a volume's), need not be
+ * initialised. Six short launches on `stream` (seven with SKIP_UNOBSERVED) and, with voxels, one pass of one wave per
+ * packed block: ten 16-byte loads and stores per lane. Nothing is read back. Moving a pack to another device is two plain
+ * copies, of origins and of voxels. */
+VK_API size_t vk_volume_pack_workspace_bytes(int32_t main_block_count, int32_t excess_block_count);
+VK_API int vk_volume_pack(const vk_volume* v, const vk_pack_rule* rule /* NULL: every block */,
+    const vk_block_pack* pack, int32_t* counts_dev /* [4] */, void* workspace, void* stream);
+
+/* vk_volume_merge with "the considered source blocks" replaced by blocks 0 .. block_count-1 of a pack; no new arithmetic
+ * (ref: src/volume.cu:304-368 for the allocation, src/depth_integrator.cu:55-59 and src/color_integrator.cu:109-118 for
+ * the running average, as at vk_volume_merge, whose comment is the definition; tests/pack_reference.py states the
+ * replacement on the CPU). Presence, the allocation rounds, the handle pass, the fusion arithmetic and the caps are
+ * merge's own — one source compiles both — and so are SKIP_UNOBSERVED (classified from the packed voxels), CONTINUE, the
+ * six counts and "afterwards". In one sentence: for a pack made without a rule from a volume src, with block_count =
+ * written = selected, the call leaves dst and counts_dev bit for bit as vk_volume_merge(dst, src, p) leaves them — entries,
+ * visibility, free list, voxels and counters.
+ * PRECONDITIONS: vk_volume_merge's for dst (between SetView calls, no frame announced: the class layers enforce it). The
+ * pack is only read. The origins of blocks 0 .. block_count-1 are DISTINCT and their fourth component is 0: the caller's
+ * duty — vk_volume_pack guarantees it, the file loaders of the class layers check it on the host. With duplicates the call
+ * stays inside its buffers and ends; which duplicate's voxels arrive in dst, or which mixture, is undefined.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): dst, pack, p, counts_dev or workspace null, origins or voxels null,
+ * origins not 8-byte or voxels not 16-byte aligned, pack->voxels == dst->voxels, a dst or a p that vk_volume_merge would
+ * refuse, voxel_length or truncation_length not bitwise equal to dst's, block_count outside 0 .. capacity.
+ * block_count == 0: VK_OK after the checks, six zero counts, "afterwards" as merge leaves it for a source without blocks.
+ * workspace: device, vk_volume_merge_packed_workspace_bytes(block_count) bytes (0 for a negative count), need not be
+ * initialised — what a CONTINUE call takes over excepted, as for vk_volume_merge. 4 + 4 * max_rounds short launches on
+ * `stream` and one pass of one wave per packed block. */
+VK_API size_t vk_volume_merge_packed_workspace_bytes(int32_t block_count);
+VK_API int vk_volume_merge_packed(const vk_volume* dst, const vk_block_pack* pack, int32_t block_count,
+    float voxel_length, float truncation_length, const vk_merge_params* p,
+    int32_t* counts_dev /* [6], vk_volume_merge's */, void* workspace, void* stream);
 
 /* ------------------------------------------------------- register volume to volume -- */
 

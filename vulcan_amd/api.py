@@ -123,6 +123,10 @@ _SIGNATURES = {
     "vk_volume_merge": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_volume_merge_posed_workspace_bytes": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32], _SZ),
     "vk_volume_merge_posed": ([_P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_pack_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
+    "vk_volume_pack": ([_P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_merge_packed_workspace_bytes": ([C.c_int32], _SZ),
+    "vk_volume_merge_packed": ([_P, _P, C.c_int32, _F, _F, _P, _P, _P, _P], _I),
     "vk_volume_register_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_volume_register_terms": ([_P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_volume_register_system": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
@@ -496,6 +500,54 @@ class RayHits:
         self.gradient, self.gradient_valid = at.gradient, at.gradient_valid
 
 
+class PackedVolume:
+    """The blocks of a volume, compact and in a defined order (vk_block_pack, vk.h): what Volume.pack returns and
+    Volume.merge takes in a volume's place. `origins`: int16 [count, 4] (x, y, z, 0), `voxels`: uint8 [count * 10240],
+    both on one device; `voxel_length`, `truncation_length`: the lattice the voxels belong to. Not upstream."""
+    BLOCK_BYTES = T.BLOCK_VOXELS * 20
+
+    def __init__(self, origins, voxels, voxel_length, truncation_length):
+        self.origins, self.voxels = origins, voxels
+        self.count = int(origins.shape[0])
+        if self.voxels.numel() != self.count * self.BLOCK_BYTES:
+            raise VkError(f"PackedVolume: {self.count} origins and {self.voxels.numel()} bytes of voxels")
+        self.voxel_length, self.truncation_length = float(voxel_length), float(truncation_length)
+
+    def __len__(self):
+        return self.count
+
+    @property
+    def device(self):
+        return self.voxels.device
+
+    def desc(self):
+        d = T.BlockPack()
+        d.capacity = self.count
+        d.origins, d.voxels = self.origins.data_ptr(), self.voxels.data_ptr()
+        return d
+
+    def host(self):
+        """(origins [count, 4] int16, voxels [512 * count] of vk_types.voxel_dtype): one blocking read each"""
+        return self.origins.cpu().numpy(), to_numpy(self.voxels, T.voxel_dtype)
+
+    def to(self, device):
+        """the pack on `device`: two plain copies (the pack itself when it is there already)"""
+        return PackedVolume(self.origins.to(device), self.voxels.to(device), self.voxel_length, self.truncation_length)
+
+    def save(self, path):
+        """io.write_map: the pack as one file, at the size of its blocks"""
+        from . import io
+        io.write_map(path, self.origins.cpu().numpy(), self.voxels.cpu().numpy(), self.voxel_length, self.truncation_length)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """io.read_map, which refuses a malformed file (ValueError) before anything reaches a device"""
+        import torch
+        from . import io
+        origins, voxels, voxel_length, truncation_length = io.read_map(path)
+        return cls(torch.from_numpy(origins).to(device), torch.from_numpy(voxels).to(device), voxel_length, truncation_length)
+
+
 class Volume:
     """vulcan::Volume (volume.h:16-117): owns the device buffers, forwards to vk_volume_*."""
 
@@ -720,6 +772,67 @@ class Volume:
                                           stream()), "vk_volume_merge_posed")
         return _ints(counts)
 
+    def _merge_packed_call(self, pack, flags, max_rounds, max_distance_weight, max_color_weight):
+        """one vk_volume_merge_packed(self <- pack): the six counts from one blocking read"""
+        self._no_requests_pending("merge")
+        workspace, counts = self._workspace("merge_packed", (pack.count,), lib().vk_volume_merge_packed_workspace_bytes, 6, flags)
+        params = T.MergeParams(int(flags), int(max_rounds), float(max_distance_weight), float(max_color_weight))
+        self._table_changes()
+        check(lib().vk_volume_merge_packed(_ref(self.desc()), _ref(pack.desc()), pack.count, pack.voxel_length, pack.truncation_length,
+                                           _ref(params), _ptr(counts), _ptr(workspace), stream()), "vk_volume_merge_packed")
+        return _ints(counts)
+
+    def _pack_call(self, rule, origins, voxels, capacity):
+        """one vk_volume_pack: (source blocks, selected, written, skipped as unobserved) from one blocking read"""
+        workspace, counts = self._workspace("pack", (self.main, self.excess), lib().vk_volume_pack_workspace_bytes, 4)
+        pack = T.BlockPack()
+        pack.capacity = int(capacity)
+        pack.origins = origins.data_ptr() if origins is not None else None
+        pack.voxels = voxels.data_ptr() if voxels is not None else None
+        check(lib().vk_volume_pack(_ref(self.desc()), _ref(rule) if rule is not None else None, _ref(pack), _ptr(counts),
+                                   _ptr(workspace), stream()), "vk_volume_pack")
+        return _ints(counts)
+
+    def pack(self, box=None, skip_unobserved=False):
+        """vk_volume_pack (not upstream): this volume's blocks as a PackedVolume — the origin and the 10 240 bytes of
+        every block, in ascending order of the blocks' table entries, at the cost of the blocks that exist and not of
+        the pool. `box` = ((lo x, y, z), (hi x, y, z)) in block coordinates, inclusive: only the blocks inside;
+        `skip_unobserved`: without the blocks no voxel was ever integrated into. A call that counts, one blocking read
+        of the count, an allocation of exactly that size, the call that packs. The volume is only read: allowed while
+        a frame is announced. What to do with the pack: save(path), to(another device), other_volume.merge(pack)."""
+        import torch
+        rule = None
+        if box is not None or skip_unobserved:
+            rule = T.PackRule()
+            if skip_unobserved:
+                rule.flags |= T.VK_PACK_SKIP_UNOBSERVED
+            if box is not None:
+                rule.flags |= T.VK_PACK_BOX
+                rule.lo[:] = [int(c) for c in box[0]]
+                rule.hi[:] = [int(c) for c in box[1]]
+        selected = self._pack_call(rule, None, None, 0)[1]
+        origins = torch.empty((selected, 4), dtype=torch.int16, device=self.device)
+        voxels = _dev_bytes(selected * PackedVolume.BLOCK_BYTES, self.device)
+        if selected:
+            written = self._pack_call(rule, origins, voxels, selected)[2]
+            if written != selected:
+                raise VkError(f"pack: {selected} blocks counted, {written} written: the volume changed between the two calls")
+        return PackedVolume(origins, voxels, self.voxel_length, self.truncation_length)
+
+    @classmethod
+    def load(cls, path, main_block_count, excess_block_count, depth_range=(0.1, 5.0), device="cuda", max_rounds=8):
+        """A map file (PackedVolume.save, io.write_map) as a fresh volume of the given table sizes, which need not be
+        those of the volume that was saved: a new Volume with the file's voxel and truncation length, and merge(pack)
+        with both caps 32767, which into empty blocks is a copy. Raises when the blocks do not fit the sizes."""
+        pack = PackedVolume.load(path, device=device)
+        volume = cls(main_block_count, excess_block_count, voxel_length=pack.voxel_length,
+                     truncation_length=pack.truncation_length, depth_range=depth_range, device=device)
+        counts = volume.merge(pack, max_distance_weight=32767, max_color_weight=32767, max_rounds=max_rounds)
+        if counts[3]:
+            raise VkError(f"Volume.load: {counts[3]} of {len(pack)} blocks did not fit ({main_block_count} main, "
+                          f"{excess_block_count} excess entries)")
+        return volume
+
     def _merge_rounds(self, call, max_rounds, left_out, rounds, summed):
         """`call(0)`, then `call(VK_MERGE_CONTINUE)` while a call posted requests in every round, dropped none and still left
         blocks out. Of the later calls' counts those at `summed` add up and the one at `left_out` replaces; the rest are
@@ -749,8 +862,23 @@ class Volume:
         vk_volume_merge_posed: every voxel of the blocks of this volume that `other`'s blocks reach takes a trilinear
         sample of `other`. Returns (source blocks considered, candidate blocks, candidates fused, blocks allocated,
         candidates left out, rounds that posted, source blocks skipped as unobserved, voxels that took a distance
-        sample); a candidate no sample reaches stays allocated and empty (release_blocks(unobserved=True) frees those)."""
+        sample); a candidate no sample reaches stays allocated and empty (release_blocks(unobserved=True) frees those).
+        `other` may be a PackedVolume (Volume.pack, PackedVolume.load) in a volume's place — vk_volume_merge_packed: the
+        same options and the same six counts, and for a pack made without a rule the state merge(that volume) leaves.
+        A pack has no table to sample through a pose: `pose` with a pack raises TypeError."""
         flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
+        if isinstance(other, PackedVolume):
+            if pose is not None:
+                raise TypeError("merge: a PackedVolume is merged block into block; pose= takes a Volume")
+            self._no_requests_pending("merge")
+            if (np.float32(other.voxel_length) != np.float32(self.voxel_length) or
+                    np.float32(other.truncation_length) != np.float32(self.truncation_length)):
+                raise VkError(f"merge: the pack's voxel / truncation length ({other.voxel_length}, {other.truncation_length}) "
+                              f"is not the volume's ({self.voxel_length}, {self.truncation_length})")
+            if len(other) == 0:
+                return (0, 0, 0, 0, 0, 0)                  # no blocks: no call
+            return self._merge_rounds(lambda go_on: self._merge_packed_call(other, flags | go_on, max_rounds, max_distance_weight,
+                                                                            max_color_weight), max_rounds, 3, 4, (1, 2, 4))
         if pose is None:
             # (considered, fused, allocated, left out, rounds, skipped)
             return self._merge_rounds(lambda go_on: self._merge_call(other, flags | go_on, max_rounds, max_distance_weight,

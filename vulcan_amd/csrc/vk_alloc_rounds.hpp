@@ -72,11 +72,16 @@ int run_rounds(const vk_volume* v, int max_rounds, int32_t* ctl, void* stream, R
 }
 
 // what vk_volume_merge and vk_volume_merge_posed ask of their arguments
+inline bool merge_params_ok(const vk_merge_params& m)
+{
+  return (m.flags & ~(VK_MERGE_SKIP_UNOBSERVED | VK_MERGE_CONTINUE)) == 0 && m.max_rounds >= 1 &&
+         m.max_distance_weight >= 1.0f && m.max_distance_weight <= 32767.0f &&        // (false for a NaN)
+         m.max_color_weight >= 1.0f && m.max_color_weight <= 32767.0f;
+}
+
 inline bool merge_ok(const vk_volume* dst, const vk_volume* src, const vk_merge_params& m)
 {
-  return volumes_match(dst, src) && dst->voxels != src->voxels && (m.flags & ~(VK_MERGE_SKIP_UNOBSERVED | VK_MERGE_CONTINUE)) == 0 &&
-         m.max_rounds >= 1 && m.max_distance_weight >= 1.0f && m.max_distance_weight <= 32767.0f &&        // (false for a NaN)
-         m.max_color_weight >= 1.0f && m.max_color_weight <= 32767.0f;
+  return volumes_match(dst, src) && dst->voxels != src->voxels && merge_params_ok(m);
 }
 
 }  // namespace vk

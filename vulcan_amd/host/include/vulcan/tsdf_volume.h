@@ -15,6 +15,8 @@
 #include <cmath>
 #include <cstdint>
 #include <array>
+#include <memory>
+#include <string>
 #include <vector>
 #include <vk.h>
 #include <vulcan/buffer.h>
@@ -77,6 +79,45 @@ struct MergeCounts
   int left_out;         // blocks that found no room: the pool or the excess list ran out
   int rounds;           // allocation rounds that posted a request
   int skipped;          // blocks of the other volume skipped as unobserved
+};
+
+// Not upstream: which blocks Volume::Pack leaves out (vk_pack_rule). Default-constructed: every block.
+struct PackOptions
+{
+  bool skip_unobserved = false;       // without the blocks no voxel of which was ever integrated
+  bool box = false;                   // only the blocks whose origin lies in [lo, hi], block coordinates, inclusive
+  int16_t lo[3] = {0, 0, 0};
+  int16_t hi[3] = {0, 0, 0};
+};
+
+// Not upstream (its Volume never leaves the device buffers it was allocated in, src/volume.cu:17-21): the blocks of a
+// volume, compact and in a defined order (vk_block_pack) — per block its origin (x, y, z, 0) and its 10 240 bytes of
+// voxels, in ascending order of the blocks' table entries. What Volume::Pack returns and Volume::Merge takes in a volume's
+// place; Save and Load move it through a file, at the size of its blocks. Copies share the two device buffers.
+class PackedVolume
+{
+  public:
+    PackedVolume();                                 // no blocks
+    int Count() const { return count_; }
+    float VoxelLength() const { return voxel_length_; }
+    float TruncationLength() const { return truncation_length_; }
+    const Buffer<int16_t>& GetOrigins() const { return *origins_; }           // device [4 * Count()]
+    const Buffer<unsigned char>& GetVoxels() const { return *voxels_; }       // device [10240 * Count()]
+    vk_block_pack ToVk() const;                     // device view for the C ABI
+    // The file of vulcan_amd/io.py write_map / read_map, little-endian: the magic "VULCANMP", int32 version 1, int32 block
+    // count, float voxel length, float truncation length, 8 reserved bytes (zero), the origins, the voxels. Blocking.
+    void Save(const std::string& path) const;
+    // Throws for a file that is not one — a wrong magic or version, a negative count, a length that does not match the
+    // count, a fourth origin component that is not 0, two blocks with one origin — before anything reaches the device.
+    static PackedVolume Load(const std::string& path);
+
+  private:
+    friend class Volume;
+    PackedVolume(int count, float voxel_length, float truncation_length);     // device buffers for `count` blocks
+    std::shared_ptr<Buffer<int16_t>> origins_;
+    std::shared_ptr<Buffer<unsigned char>> voxels_;
+    int count_;
+    float voxel_length_, truncation_length_;
 };
 
 // Volume::Merge through a pose (vk_volume_merge_posed's eight counts, summed over the calls the rounds take)
@@ -307,6 +348,18 @@ class Volume
     // The visible list is empty afterwards (the next SetView rebuilds it); the raycast bounds and the light preparation
     // made ahead are void. Blocking readbacks (the six counts, VK_CTR_DROPPED).
     MergeCounts Merge(const Volume& other, const MergeOptions& options = MergeOptions());
+    // ... with the blocks of a pack in the other volume's place (vk_volume_merge_packed): for a pack made without options
+    // from a volume, the state and the counts Merge(that volume) leaves. The pack's voxel and truncation length must be
+    // this volume's. A pack without blocks: no call. Otherwise as Merge(other).
+    MergeCounts Merge(const PackedVolume& pack, const MergeOptions& options = MergeOptions());
+    // Not upstream: this volume's blocks as a PackedVolume (vk_volume_pack) — a call that counts, one blocking read of the
+    // count, an allocation of exactly that size, the call that packs. The volume is only read: like Sample it is allowed
+    // while a frame announced by Tracer::Trace(keyframe, next_frame) is outstanding.
+    PackedVolume Pack(const PackOptions& options = PackOptions()) const;
+    // Not upstream: a map file (PackedVolume::Save) as a fresh volume of the given table sizes, which need not be those
+    // of the volume that was saved: the file's voxel and truncation length, and Merge(pack) with both caps 32767, which
+    // into empty blocks is a copy. Throws when the blocks do not fit.
+    static std::shared_ptr<Volume> Load(const std::string& path, int main_block_count, int excess_block_count);
     // ... through the rigid pose Tdst_src (x in this volume's frame = Tdst_src * x in `other`'s, metres): the two need not
     // share a world frame or a voxel lattice (vk_volume_merge_posed). Every voxel of the blocks of this volume that `other`'s
     // blocks reach takes a trilinear sample of `other` at its own centre carried back; a reached block no sample falls into
@@ -462,6 +515,10 @@ class Volume
     Buffer<int> release_counts_;
     Buffer<unsigned char> merge_workspace_;     // Merge: allocated by the first call, again for a source of another size
     Buffer<int> merge_counts_;
+    Buffer<unsigned char> merge_packed_workspace_;   // Merge of a pack: again for a pack of another size
+    Buffer<int> merge_packed_counts_;
+    mutable Buffer<unsigned char> pack_workspace_;   // Pack: allocated by the first call
+    mutable Buffer<int> pack_counts_;
     Buffer<unsigned char> merge_pose_workspace_;   // Merge through a pose: again for another pair of sizes
     Buffer<int> merge_pose_counts_;
     // a registration's device buffers, and what is done with them before and after the loop
@@ -523,10 +580,11 @@ class Volume
     int ScorePosesBuffers(int count, const std::vector<Transform>& poses) const;    // the candidates uploaded: how many
     void VoidMadeAhead() const;                 // the raycast bounds and the light preparation made for the old table
     void EmptyVisibleList() const;              // VK_CTR_VISIBLE is 0 until the next SetView
-    // both Merge overloads: `call(dst, src, counts_dev, workspace)` is the library call with `merge` among its parameters,
-    // made again with VK_MERGE_CONTINUE until every block had its turn; `total` takes the `count` (6 or 8) summed counts
+    // the Merge overloads: `call(dst, src, counts_dev, workspace)` is the library call with `merge` among its parameters,
+    // made again with VK_MERGE_CONTINUE until every block had its turn; `total` takes the `count` (6 or 8) summed counts.
+    // `other` null: the source is a pack, and `src` of the call is null
     template <typename Call>
-    void MergeRounds(const Volume& other, vk_merge_params& merge, Buffer<unsigned char>& workspace, size_t bytes,
+    void MergeRounds(const Volume* other, vk_merge_params& merge, Buffer<unsigned char>& workspace, size_t bytes,
         Buffer<int>& counts_dev, int count, int32_t* total, Call call);
     void Initialize();
     Volume(const Volume&);              // not copyable

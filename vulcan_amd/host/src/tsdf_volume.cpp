@@ -1,5 +1,6 @@
 // tsdf_volume.cpp — Volume host class over vk_volume_* (ref: src/volume.cu:370-627).
 #include <vulcan/tsdf_volume.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -444,15 +445,16 @@ static vk_merge_params ToVkMergeParams(const MergeOptions& options)
 }
 
 template <typename Call>
-void Volume::MergeRounds(const Volume& other, vk_merge_params& merge, Buffer<unsigned char>& workspace, size_t bytes,
+void Volume::MergeRounds(const Volume* other, vk_merge_params& merge, Buffer<unsigned char>& workspace, size_t bytes,
     Buffer<int>& counts_dev, int count, int32_t* total, Call call)
 {
   AssertNoFrameAnnounced();
-  other.AssertNoFrameAnnounced();
-  VULCAN_ASSERT_MSG(&other != this, "a volume cannot be merged into itself");
+  if (other) other->AssertNoFrameAnnounced();
+  VULCAN_ASSERT_MSG(other != this, "a volume cannot be merged into itself");
   Sized(workspace, bytes, counts_dev, size_t(count));
   VoidMadeAhead();
-  const vk_volume dst = ToVk(), src = other.ToVk();
+  const vk_volume dst = ToVk(), source = other ? other->ToVk() : dst;
+  const vk_volume* src = other ? &source : nullptr;
   int32_t counters[VK_CTR_PUBLIC];
   GetCounters(counters);
   const int32_t dropped = counters[VK_CTR_DROPPED];
@@ -460,7 +462,7 @@ void Volume::MergeRounds(const Volume& other, vk_merge_params& merge, Buffer<uns
   const int k = count == 8 ? 1 : 0, fused = 1 + k, allocated = 2 + k, left_out = 3 + k, rounds = 4 + k;
   for (bool first = true;; first = false)
   {
-    VK_ASSERT(call(&dst, &src, counts_dev.GetData(), workspace.GetData()));
+    VK_ASSERT(call(&dst, src, counts_dev.GetData(), workspace.GetData()));
     int32_t counts[8];
     counts_dev.CopyToHost(counts);
     if (first)
@@ -487,7 +489,7 @@ MergeCounts Volume::Merge(const Volume& other, const MergeOptions& options)
 {
   vk_merge_params p = ToVkMergeParams(options);
   int32_t counts[6];
-  MergeRounds(other, p, merge_workspace_, vk_volume_merge_workspace_bytes(other.main_block_count_, other.excess_block_count_),
+  MergeRounds(&other, p, merge_workspace_, vk_volume_merge_workspace_bytes(other.main_block_count_, other.excess_block_count_),
       merge_counts_, 6, counts, [&p](const vk_volume* dst, const vk_volume* src, int32_t* counts_dev, void* workspace)
       { return vk_volume_merge(dst, src, &p, counts_dev, workspace, Device::GetStream()); });
   MergeCounts out;
@@ -506,7 +508,7 @@ MergePoseCounts Volume::Merge(const Volume& other, const Transform& Tdst_src, co
   p.merge = ToVkMergeParams(options);
   p.pose = Tdst_src.ToVk();                       // the matrix and its inverse, from the one Transform
   int32_t counts[8];
-  MergeRounds(other, p.merge, merge_pose_workspace_, vk_volume_merge_posed_workspace_bytes(other.main_block_count_,
+  MergeRounds(&other, p.merge, merge_pose_workspace_, vk_volume_merge_posed_workspace_bytes(other.main_block_count_,
       other.excess_block_count_, main_block_count_, excess_block_count_), merge_pose_counts_, 8, counts,
       [&p](const vk_volume* dst, const vk_volume* src, int32_t* counts_dev, void* workspace)
       { return vk_volume_merge_posed(dst, src, &p, counts_dev, workspace, Device::GetStream()); });
@@ -520,6 +522,165 @@ MergePoseCounts Volume::Merge(const Volume& other, const Transform& Tdst_src, co
   out.skipped = counts[6];
   out.sampled = counts[7];
   return out;
+}
+
+// ---- PackedVolume: a volume's blocks, compact (vk_block_pack) ----
+
+static const char kMapMagic[8] = {'V', 'U', 'L', 'C', 'A', 'N', 'M', 'P'};
+static const int32_t kMapVersion = 1;
+static const size_t kMapHeaderBytes = 32, kMapBlockBytes = sizeof(vk_voxel) * VK_BLOCK_VOXELS;
+
+PackedVolume::PackedVolume() : PackedVolume(0, 0.008f, 0.04f) {}
+
+PackedVolume::PackedVolume(int count, float voxel_length, float truncation_length) :
+  origins_(std::make_shared<Buffer<int16_t>>(size_t(count) * 4)),
+  voxels_(std::make_shared<Buffer<unsigned char>>(size_t(count) * kMapBlockBytes)),
+  count_(count),
+  voxel_length_(voxel_length),
+  truncation_length_(truncation_length)
+{
+}
+
+vk_block_pack PackedVolume::ToVk() const
+{
+  vk_block_pack pack;
+  pack.capacity = count_;
+  pack.pad = 0;
+  pack.origins = const_cast<int16_t*>(origins_->GetData());
+  pack.voxels = reinterpret_cast<vk_voxel*>(const_cast<unsigned char*>(voxels_->GetData()));
+  return pack;
+}
+
+void PackedVolume::Save(const std::string& path) const
+{
+  static_assert(sizeof(float) == 4 && sizeof(int32_t) == 4, "the map file's fields");
+  std::vector<int16_t> origins(size_t(count_) * 4);
+  std::vector<unsigned char> voxels(size_t(count_) * kMapBlockBytes);
+  if (count_ > 0)
+  {
+    origins_->CopyToHost(origins.data());
+    voxels_->CopyToHost(voxels.data());
+    Device::Synchronize();
+  }
+  unsigned char header[kMapHeaderBytes] = {0};                 // (the file is little-endian, as every host this builds for)
+  std::memcpy(header, kMapMagic, 8);
+  std::memcpy(header + 8, &kMapVersion, 4);
+  const int32_t count = count_;
+  std::memcpy(header + 12, &count, 4);
+  std::memcpy(header + 16, &voxel_length_, 4);
+  std::memcpy(header + 20, &truncation_length_, 4);
+  std::FILE* file = std::fopen(path.c_str(), "wb");
+  VULCAN_ASSERT_MSG(file != nullptr, "cannot write the map file " + path);
+  bool good = std::fwrite(header, 1, kMapHeaderBytes, file) == kMapHeaderBytes;
+  good = good && std::fwrite(origins.data(), sizeof(int16_t), origins.size(), file) == origins.size();
+  good = good && std::fwrite(voxels.data(), 1, voxels.size(), file) == voxels.size();
+  good = (std::fclose(file) == 0) && good;
+  VULCAN_ASSERT_MSG(good, "the map file " + path + " could not be written in full");
+}
+
+PackedVolume PackedVolume::Load(const std::string& path)
+{
+  std::FILE* file = std::fopen(path.c_str(), "rb");
+  VULCAN_ASSERT_MSG(file != nullptr, "cannot read the map file " + path);
+  std::vector<unsigned char> data;
+  unsigned char chunk[1 << 16];
+  for (size_t got; (got = std::fread(chunk, 1, sizeof(chunk), file)) > 0;) data.insert(data.end(), chunk, chunk + got);
+  std::fclose(file);
+  VULCAN_ASSERT_MSG(data.size() >= kMapHeaderBytes && std::memcmp(data.data(), kMapMagic, 8) == 0, path + " is not a map file (magic)");
+  int32_t version, count;
+  float voxel_length, truncation_length;
+  std::memcpy(&version, data.data() + 8, 4);
+  std::memcpy(&count, data.data() + 12, 4);
+  std::memcpy(&voxel_length, data.data() + 16, 4);
+  std::memcpy(&truncation_length, data.data() + 20, 4);
+  VULCAN_ASSERT_MSG(version == kMapVersion, path + ": a map file of another version");
+  VULCAN_ASSERT_MSG(count >= 0, path + ": a negative block count");
+  VULCAN_ASSERT_MSG(data.size() == kMapHeaderBytes + size_t(count) * (8 + kMapBlockBytes), path + ": the file's length does not match its block count");
+  std::vector<int16_t> origins(size_t(count) * 4);
+  if (count > 0) std::memcpy(origins.data(), data.data() + kMapHeaderBytes, origins.size() * sizeof(int16_t));
+  std::vector<std::array<int16_t, 3>> seen(static_cast<size_t>(count));
+  for (int k = 0; k < count; ++k)
+  {
+    VULCAN_ASSERT_MSG(origins[size_t(k) * 4 + 3] == 0, path + ": an origin's fourth component is not 0");
+    seen[size_t(k)] = {{origins[size_t(k) * 4], origins[size_t(k) * 4 + 1], origins[size_t(k) * 4 + 2]}};
+  }
+  std::sort(seen.begin(), seen.end());
+  VULCAN_ASSERT_MSG(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), path + ": two blocks have the same origin");
+  PackedVolume pack(count, voxel_length, truncation_length);
+  if (count > 0)
+  {
+    pack.origins_->CopyFromHost(origins.data());
+    pack.voxels_->CopyFromHost(data.data() + kMapHeaderBytes + size_t(count) * 8);
+    Device::Synchronize();                                     // the host vectors go away
+  }
+  return pack;
+}
+
+PackedVolume Volume::Pack(const PackOptions& options) const
+{
+  vk_pack_rule rule;
+  std::memset(&rule, 0, sizeof(rule));
+  rule.flags = (options.skip_unobserved ? VK_PACK_SKIP_UNOBSERVED : 0) | (options.box ? VK_PACK_BOX : 0);
+  for (int a = 0; a < 3; ++a)
+  {
+    rule.lo[a] = options.lo[a];
+    rule.hi[a] = options.hi[a];
+  }
+  if (pack_counts_.GetSize() == 0)
+  {
+    pack_workspace_.Resize(vk_volume_pack_workspace_bytes(main_block_count_, excess_block_count_));
+    pack_counts_.Resize(4);
+  }
+  const vk_volume v = ToVk();
+  vk_block_pack none;
+  std::memset(&none, 0, sizeof(none));                          // voxels null: the call only counts
+  VK_ASSERT(vk_volume_pack(&v, &rule, &none, pack_counts_.GetData(), pack_workspace_.GetData(), Device::GetStream()));
+  int32_t counts[4];
+  pack_counts_.CopyToHost(counts);
+  PackedVolume pack(counts[1], voxel_length_, truncation_length_);
+  if (counts[1] == 0) return pack;
+  const vk_block_pack into = pack.ToVk();
+  VK_ASSERT(vk_volume_pack(&v, &rule, &into, pack_counts_.GetData(), pack_workspace_.GetData(), Device::GetStream()));
+  pack_counts_.CopyToHost(counts);
+  VULCAN_ASSERT_MSG(counts[2] == pack.Count(), "the volume changed between the call that counted its blocks and the call that packed them");
+  return pack;
+}
+
+MergeCounts Volume::Merge(const PackedVolume& pack, const MergeOptions& options)
+{
+  AssertNoFrameAnnounced();
+  const float voxel_length = pack.VoxelLength(), truncation_length = pack.TruncationLength();
+  VULCAN_ASSERT_MSG(std::memcmp(&voxel_length, &voxel_length_, sizeof(float)) == 0 &&
+      std::memcmp(&truncation_length, &truncation_length_, sizeof(float)) == 0,
+      "the pack's voxel or truncation length is not the volume's");
+  MergeCounts out = {0, 0, 0, 0, 0, 0};
+  if (pack.Count() == 0) return out;                            // no blocks: no call
+  vk_merge_params p = ToVkMergeParams(options);
+  const vk_block_pack from = pack.ToVk();
+  int32_t counts[6];
+  MergeRounds(nullptr, p, merge_packed_workspace_, vk_volume_merge_packed_workspace_bytes(pack.Count()), merge_packed_counts_, 6, counts,
+      [&](const vk_volume* dst, const vk_volume*, int32_t* counts_dev, void* workspace)
+      { return vk_volume_merge_packed(dst, &from, pack.Count(), voxel_length, truncation_length, &p, counts_dev, workspace, Device::GetStream()); });
+  out.considered = counts[0];
+  out.fused = counts[1];
+  out.allocated = counts[2];
+  out.left_out = counts[3];
+  out.rounds = counts[4];
+  out.skipped = counts[5];
+  return out;
+}
+
+std::shared_ptr<Volume> Volume::Load(const std::string& path, int main_block_count, int excess_block_count)
+{
+  const PackedVolume pack = PackedVolume::Load(path);
+  auto volume = std::make_shared<Volume>(main_block_count, excess_block_count);
+  volume->SetVoxelLength(pack.VoxelLength());
+  volume->SetTruncationLength(pack.TruncationLength());
+  MergeOptions options;
+  options.max_distance_weight = options.max_color_weight = 32767.0f;
+  const MergeCounts counts = volume->Merge(pack, options);
+  VULCAN_ASSERT_MSG(counts.left_out == 0, "the map's blocks do not fit the volume's table sizes");
+  return volume;
 }
 
 Registration Volume::Register(const Volume& other, const Transform& start, int iterations, float max_abs_distance)

@@ -18,6 +18,9 @@ SequenceWriter / SequenceReader
               a directory of depth_%06d.pgm / color_%06d.ppm plus sequence.txt (size,
               intrinsics, depth scale, one depth_to_world matrix + inverse per frame): what stands in for the
               HAL camera the upstream app reads from (apps/vulcan/vulcan.cu:181-232).
+write_map / read_map
+              the packed blocks of a volume (Volume.pack, vk_volume_pack) as one binary file: what PackedVolume.save /
+              load and the C++ layer's PackedVolume::Save / Load read and write.
 """
 import os
 
@@ -252,3 +255,52 @@ class SequenceReader:
         path = os.path.join(self.directory, "color_%06d.ppm" % i)
         color = load_color(path, 1.0 / 255.0) if os.path.exists(path) else None
         return depth, color, self.poses.get(i, np.eye(4, dtype=np.float32))
+
+
+# ---- maps ---------------------------------------------------------------------------
+
+MAP_MAGIC, MAP_VERSION = b"VULCANMP", 1
+MAP_HEADER_BYTES, MAP_BLOCK_BYTES = 32, 512 * 20
+
+
+def write_map(path, origins, voxels, voxel_length, truncation_length):
+    """The packed blocks of a volume (vk_volume_pack, vk.h) as a file, little-endian: the 8-byte magic, int32 version,
+    int32 block count, float32 voxel length, float32 truncation length, 8 reserved bytes (zero), then the origins
+    (int16 x, y, z, 0 per block) and the voxels (10 240 bytes per block) as the pack holds them. `origins` [n, 4] int16,
+    `voxels` any array of n * 10 240 bytes. Not upstream: its Volume never leaves the device (src/volume.cu:17-21)."""
+    origins = np.ascontiguousarray(np.asarray(origins, dtype="<i2").reshape(-1, 4))
+    body = np.ascontiguousarray(voxels).tobytes()
+    if len(body) != len(origins) * MAP_BLOCK_BYTES:
+        raise ValueError(f"write_map: {len(origins)} origins and {len(body)} bytes of voxels")
+    header = (MAP_MAGIC + np.array([MAP_VERSION, len(origins)], dtype="<i4").tobytes() +
+              np.array([voxel_length, truncation_length], dtype="<f4").tobytes() + bytes(8))
+    with open(path, "wb") as fh:
+        fh.write(header)
+        fh.write(origins.tobytes())
+        fh.write(body)
+
+
+def read_map(path):
+    """A file of write_map: (origins [n, 4] int16, voxels [n * 10 240] uint8, voxel length, truncation length — both
+    np.float32). ValueError for a file that is not one: a wrong magic or version, a negative count, a length that does
+    not match the count, a fourth origin component that is not 0, two blocks with one origin (vk_volume_merge_packed
+    leaves duplicates undefined) — all on the host, before anything is given to a device."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if len(data) < MAP_HEADER_BYTES or data[:8] != MAP_MAGIC:
+        raise ValueError(f"{path}: not a map file (magic)")
+    version, count = (int(x) for x in np.frombuffer(data, dtype="<i4", count=2, offset=8))
+    if version != MAP_VERSION:
+        raise ValueError(f"{path}: map file version {version}, this reader knows {MAP_VERSION}")
+    if count < 0:
+        raise ValueError(f"{path}: block count {count}")
+    if len(data) != MAP_HEADER_BYTES + count * (8 + MAP_BLOCK_BYTES):
+        raise ValueError(f"{path}: {len(data)} bytes do not hold {count} blocks")
+    voxel_length, truncation_length = np.frombuffer(data, dtype="<f4", count=2, offset=16)
+    origins = np.frombuffer(data, dtype="<i2", count=4 * count, offset=MAP_HEADER_BYTES).reshape(count, 4).astype(np.int16)
+    if (origins[:, 3] != 0).any():
+        raise ValueError(f"{path}: an origin's fourth component is not 0")
+    if count and len(np.unique(origins, axis=0)) != count:
+        raise ValueError(f"{path}: two blocks have the same origin")
+    voxels = np.frombuffer(data, dtype=np.uint8, count=count * MAP_BLOCK_BYTES, offset=MAP_HEADER_BYTES + 8 * count).copy()
+    return origins, voxels, np.float32(voxel_length), np.float32(truncation_length)

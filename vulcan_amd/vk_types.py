@@ -25,6 +25,7 @@ ALLOC_NONE, ALLOC_MAIN, ALLOC_EXCESS = 0, 1, 2
 BLOCK_RESOLUTION, BLOCK_VOXELS, PATCH_MAX_SIZE = 8, 512, 16
 VK_RELEASE_UNOBSERVED, VK_RELEASE_NO_SURFACE, VK_RELEASE_OUTSIDE_BOX = 1, 2, 4   # vk_release_rule.flags
 VK_MERGE_SKIP_UNOBSERVED, VK_MERGE_CONTINUE = 1, 2                               # vk_merge_params.flags
+VK_PACK_SKIP_UNOBSERVED, VK_PACK_BOX = 1, 2                                      # vk_pack_rule.flags
 VK_REGISTER_NO_OVERLAP = 2                                                       # vk_volume_register: state_dev[1]
 VK_SAMPLE_VOXEL_UNITS, VK_SAMPLE_DISTANCE_ONLY = 1, 2                            # vk_sample_params.flags
 VK_CAST_VOXEL_UNITS, VK_CAST_DISTANCE_ONLY = 1, 2                                # vk_cast_params.flags
@@ -213,6 +214,16 @@ class ReleaseRule(C.Structure):
 class MergeParams(C.Structure):
     """vk_merge_params (vk.h): how vk_volume_merge fuses one volume into another"""
     _fields_ = [("flags", C.c_int32), ("max_rounds", C.c_int32), ("max_distance_weight", C.c_float), ("max_color_weight", C.c_float)]
+
+
+class BlockPack(C.Structure):
+    """vk_block_pack (vk.h): the two device arrays of a volume's packed blocks; voxels None: vk_volume_pack only counts"""
+    _fields_ = [("capacity", C.c_int32), ("pad", C.c_int32), ("origins", C.c_void_p), ("voxels", C.c_void_p)]
+
+
+class PackRule(C.Structure):
+    """vk_pack_rule (vk.h): which blocks vk_volume_pack leaves out; flags 0 = none"""
+    _fields_ = [("flags", C.c_int32), ("lo", C.c_int16 * 3), ("hi", C.c_int16 * 3)]
 
 
 class MergePoseParams(C.Structure):
