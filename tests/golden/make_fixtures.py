@@ -102,7 +102,9 @@ def step_cap_oracle():
 # ---- the soak run's parity leg (round 6; tools/soak.py): 2 000 frames of fusion + raycast at GIVEN poses on the room
 # sequence, looped (240 distinct frames), at the bench's size — Volume(65024, 8192), 640x480, 5 mm. The file holds SHA-256
 # digests of the hash table, the voxel pool and the raycast images at a few frame counts: long enough for the free list,
-# the visibility churn of revisited blocks and the saturated weights to matter, and still a parity statement.
+# the visibility churn of revisited blocks and the saturated weights to matter, and still a parity statement. The device is
+# held to the checkpoints up to frame 480 by tests/test_gpu_long_run.py (the same code as the tool's leg: tests/long_run.py),
+# to frame 2 000 by the tool.
 SOAK_FILE = os.path.join(HERE, "soak_room_640x480.json")
 SOAK_CHECKPOINTS = (20, 240, 480, 2000)
 SOAK_CYCLE = 240          # tests/scenes.py room_pose: frames per swing

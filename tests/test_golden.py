@@ -60,7 +60,8 @@ def test_oracle_reproduces_the_step_cap_vectors(orc):
 
 
 def test_oracle_reproduces_the_soak_fixtures_first_checkpoint(orc):
-    """tests/golden/soak_room_640x480.json (make_fixtures.py --soak; tools/soak.py holds the device to it over 2 000 frames):
+    """tests/golden/soak_room_640x480.json (make_fixtures.py --soak; tests/test_gpu_long_run.py holds the device to its checkpoints at
+    frames 20 / 240 / 480 in every run of the suite, tools/soak.py to all four over 2 000 frames):
     the oracle's first 20 frames of the looped room sequence at the bench's size still give the digests on file — the
     2 000-frame file and the oracle cannot drift apart unnoticed (the whole run takes the oracle five minutes: made once)."""
     import json

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import scenes
+from closed_loop_oracle import oracle_loop
 from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
@@ -46,25 +47,13 @@ def closed_loop(api, orc, size, count, stride, tracking, free_running_atol=2e-5)
     params = T.Integrator(0.1, 5.0, 100.0, 16.0) if photometric else T.Integrator.default()
 
     # ---- the oracle's closed loop
-    hv = orc.HostVolume(main, excess, voxel_length=voxel, truncation_length=trunc)
-    pose, hkey, oracle = truth[0], None, []
-    for i, (depth, color) in enumerate(inputs):
-        hf = orc.HostFrame(depth, k, pose, color=color)
-        hf.compute_normals()
-        if i > 0:
-            if photometric:
-                pose, _ = orc.light_track(hkey, hf, light, tracking[1])
-            else:
-                pose, _ = orc.pyramid_track(hkey, hf)
-        hf.depth_to_world = pose
-        for _ in range(3):
-            hv.set_view(hf, orc.POLICY_MAXKEY)
-        orc.integrate_depth(hv, hf, params)
-        orc.integrate_light_color(hv, hf, light, orc.light_frame_mask(hf, 0.2), params)
-        odepth, ocolor, onormals, obounds = orc.trace(hv, hf)
-        hkey = orc.HostFrame(odepth, k, pose, color=ocolor, normals=onormals)
-        oracle.append(dict(pose=pose, depth=odepth, color=ocolor, normals=onormals, bounds=obounds,
-                           visible=hv.visible_count))
+    if photometric:
+        def track(hkey, hf):
+            return orc.light_track(hkey, hf, light, tracking[1])[0]
+    else:
+        def track(hkey, hf):
+            return orc.pyramid_track(hkey, hf)[0]
+    hv, oracle = oracle_loop(orc, k, inputs, light, truth[0], track=track, params=params, volume=(main, excess, voxel, trunc))
 
     def device_loop(follow_oracle):
         dv = api.Volume(main, excess, voxel_length=voxel, truncation_length=trunc)

@@ -299,9 +299,10 @@ def test_tracked_loop_with_set_view_at_the_device_pose_equals_the_loop_without(a
     """bench.FrameLoop('rgbd-icp') with SetView(i) enqueued behind Track(i) at the pose the tracker leaves on the device — the
     whole call (vk_volume_set_view_at_device_pose, bench.py's default) or its request pass only
     (vk_volume_requests_at_device_pose) — and with the host's round trip in front of SetView
-    (VK_BENCH_SET_VIEW_AT_DEVICE_POSE=0, the form the oracle's closed loop is held against in tests/test_gpu_closed_loop.py):
-    six frames, every tracked pose, the volume, the table, the visibility bytes, the visible list's size and the raycast and
-    light-preparation images, bit for bit."""
+    (VK_BENCH_SET_VIEW_AT_DEVICE_POSE=0): six frames, every tracked pose, the volume, the table, the visibility bytes, the visible
+    list's size and the raycast and light-preparation images, bit for bit. The three forms are held to EACH OTHER here; the
+    default form is held to the oracle by tests/test_gpu_tracked_bench_step.py, and with it, through this test, the other two
+    (tests/test_gpu_closed_loop.py holds the api.* wrapper calls to the oracle's closed loop, not FrameLoop)."""
     import torch
     import bench
     frames = 6

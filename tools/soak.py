@@ -30,19 +30,6 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 
-class Looped:
-    """a list that repeats: frame i of the soak is frame i mod 240 of the room sequence"""
-
-    def __init__(self, items, length):
-        self.items, self.length = items, length
-
-    def __len__(self):
-        return self.length
-
-    def __getitem__(self, i):
-        return self.items[i % len(self.items)]
-
-
 def sha(t):
     return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
 
@@ -59,6 +46,7 @@ def main():
 
     import torch
     import bench
+    import long_run
     import make_fixtures as mf
     import scenes
     from vulcan_amd import api, vk_types as T
@@ -69,16 +57,10 @@ def main():
     doc = {"tool": "tools/soak.py", "device": torch.cuda.get_device_name(0), "cycle_frames": mf.SOAK_CYCLE}
 
     k, inputs = mf.soak_inputs(mf.SOAK_CYCLE)
-    room = bench.RoomSequence.__new__(bench.RoomSequence)
-    room.truth = [p for _, _, p in inputs]
-    room.depth = [torch.from_numpy(d).cuda() for d, _, _ in inputs]
-    room.color = [torch.from_numpy(c).cuda() for _, c, _ in inputs]
-    torch.cuda.synchronize()
+    room = long_run.resident_room(inputs)
 
     def looped(n):
-        seq = bench.RoomSequence.__new__(bench.RoomSequence)
-        seq.truth, seq.depth, seq.color = Looped(room.truth, n), Looped(room.depth, n), Looped(room.color, n)
-        return seq
+        return long_run.looped(room, n)
 
     # ---------------------------------------------------------------- leg 1: parity ----
     golden = json.load(open(mf.SOAK_FILE))["checkpoints"]
@@ -95,12 +77,7 @@ def main():
     for i in range(n):
         loop.step(i)
         if str(i + 1) in golden:
-            torch.cuda.synchronize()
-            ctr = vol.read_counters()
-            got = {"entries_sha256": sha(vol.hash_entries), "voxels_sha256": sha(vol.voxels), "depth_sha256": sha(loop.key.depth),
-                   "color_sha256": sha(loop.key.color), "normals_sha256": sha(loop.key.normals),
-                   "visible": int(ctr[T.VK_CTR_VISIBLE]), "voxel_pointer": int(ctr[T.VK_CTR_VOXEL_PTR]),
-                   "dropped": int(ctr[T.VK_CTR_DROPPED])}
+            got = long_run.digests(loop)              # (tests/long_run.py: what tests/test_gpu_long_run.py compares as well)
             want = golden[str(i + 1)]
             differs = sorted(key for key in want if got[key] != want[key])
             parity["checkpoints"][str(i + 1)] = {"equal_to_the_oracle": not differs, "differs": differs, "visible": got["visible"],
