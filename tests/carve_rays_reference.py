@@ -229,6 +229,22 @@ def all_rays(orc, voxel_units):
 bounds, permuted = IR.bounds, IR.permuted
 
 
+def keywords(flags, kw):
+    """the statement's and the device call's keywords for one case: t_from is given in metres and converted like the bounds"""
+    units = bool(flags & VOXEL_UNITS)
+    r_min, r_max = bounds(units)
+    kw = dict(kw)
+    t_from = kw.pop("t_from", 0.0)
+    kw["t_from"] = float(np.float32(t_from) / np.float32(R.VOXEL)) if units else float(np.float32(t_from))
+    return r_min, r_max, kw
+
+
+def state_but_voxels(hv):
+    """everything of a HostVolume the call must leave as it found it, as bytes"""
+    return (hv.hash_entries.tobytes(), hv.free_voxel_blocks.tobytes(), hv.block_visibility.tobytes(), hv.allocation_types.tobytes(),
+            hv.allocation_blocks.tobytes(), hv.visible_blocks.tobytes(), hv.counters.tobytes())
+
+
 # ---- the scenario the call exists for: a wall that is no longer there ---------------------------------------------------
 
 FRONT, BACK = 1.0, 1.4                      # two fronto-parallel planes in metres: ten truncation lengths apart

@@ -25,7 +25,6 @@ import cast_reference as CR
 import map_life as ML
 import release_reference as R
 import score_poses_reference as SP
-import test_gpu_release as RT
 from vulcan_amd import vk_types as T
 
 CALLS = {
@@ -135,7 +134,7 @@ def tokens(w, orc, index, record):
             out += [("t_from", hex32(facts["t_from"]))]
         return out
     if operation == "release_blocks":
-        rule = RT.RULES[facts["rule"]]
+        rule = R.RULES[facts["rule"]]
         lo, hi = rule.get("keep_box", ((0, 0, 0), (0, 0, 0)))
         return [("on", step.on), ("unobserved", int(bool(rule.get("unobserved")))), ("no_surface", int("min_abs_distance" in rule)),
                 ("min_abs_distance", hex32(rule.get("min_abs_distance", 0.0))), ("outside_box", int("keep_box" in rule)),
@@ -271,7 +270,7 @@ def _empty_block():
 
 
 def read_state(out, index, name, blocks):
-    """the arrays of test_gpu_release.state_arrays from the files of one state, the voxels whole again (`blocks` of them), and
+    """the arrays of gpu_support.state_arrays from the files of one state, the voxels whole again (`blocks` of them), and
     `visible_size`, Volume::GetVisibleBlocks().GetSize()"""
     prefix = os.path.join(out, f"{index}.state.{name}.")
     state = {buffer: np.fromfile(prefix + buffer, dtype=dtype) for buffer, dtype in STATE_DTYPES.items() if buffer != "counters"}

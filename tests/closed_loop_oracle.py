@@ -5,6 +5,7 @@ Trace at the frame's pose. No GPU, nothing of the device in here."""
 from vulcan_amd import vk_types as T
 
 VOLUME = (65024, 8192, 0.005, 0.04)          # apps/vulcan/vulcan.cu:12-13: main, excess, voxel length, truncation length
+POSE_ATOL = 2e-5                             # per entry, matrix and inverse: the project's bound for a tracked pose against the oracle's
 
 
 def oracle_loop(orc, k, inputs, light, first_pose, track=None, poses=None, params=None, volume=VOLUME):

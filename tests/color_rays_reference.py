@@ -141,6 +141,23 @@ def colors_for(count, seed=83):
     return colors
 
 
+def all_rays(orc, voxel_units):
+    """(rays, ranges, colours): integrate_rays' seven sets, one after the other, with the seeded colours"""
+    rays, ranges = IR.all_rays(orc, voxel_units)
+    return rays, ranges, colors_for(len(ranges))
+
+
+def keywords(flags, kw):
+    """the statement's and the device call's keywords for one case: the band is given in metres (None: the truncation length)
+    and converted like the bounds"""
+    units = bool(flags & VOXEL_UNITS)
+    r_min, r_max = IR.bounds(units)
+    kw = dict(kw)
+    band = np.float32(R.TRUNCATION if kw.get("band") is None else kw["band"])
+    kw["band"] = float(band / np.float32(R.VOXEL)) if units else float(band)
+    return r_min, r_max, kw
+
+
 def permuted(rays, ranges, colors, seed=5):
     order = np.random.default_rng(seed).permutation(len(ranges))
     return np.ascontiguousarray(rays[order]), np.ascontiguousarray(ranges[order]), np.ascontiguousarray(colors[order])

@@ -62,6 +62,19 @@ def run_scene(backend, name):
     return backend(depth, color, k, pose)
 
 
+def compare(got, golden, name):
+    """what a backend computed for scene `name` against the stored vectors: strings as text, floats bit for bit, the rest equal"""
+    for key, value in got.items():
+        want = golden[f"{name}/{key}"]
+        value = np.asarray(value)
+        if value.dtype.kind in "US":
+            assert str(value) == str(want), (name, key)
+        elif value.dtype.kind == "f":
+            assert np.array_equal(value.view(np.uint32), want.view(np.uint32)), (name, key)     # bit for bit, NaN included
+        else:
+            assert np.array_equal(value, want), (name, key)
+
+
 def oracle_backend(depth, color, k, pose):
     from oracle import oracle as orc
     from vulcan_amd import vk_types as T

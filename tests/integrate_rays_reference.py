@@ -313,6 +313,12 @@ def bounds(voxel_units, voxel_length=R.VOXEL):
     return float(f32(R_MIN) / f32(voxel_length)), float(f32(R_MAX) / f32(voxel_length))
 
 
+def keywords(flags, kw):
+    """the statement's and the device call's keywords for one case: (r_min, r_max, kw) — only the bounds follow the form"""
+    r_min, r_max = bounds(bool(flags & VOXEL_UNITS))
+    return r_min, r_max, dict(kw)
+
+
 def permuted(rays, ranges, seed=5):
     order = np.random.default_rng(seed).permutation(len(ranges))
     return np.ascontiguousarray(rays[order]), np.ascontiguousarray(ranges[order])

@@ -5,8 +5,8 @@ from and its steps. tests/test_map_life.py shows on the statements alone that th
 release has rebuilt, colour no camera wrote, carved voxels, an exhausted pool — and tests/test_gpu_map_life.py holds the device
 to every step, bit for bit, with one upload at the start.
 
-The units and bounds of every call are converted where the per-operation GPU tests convert them (their keywords() helpers and
-integrate_rays_reference.bounds); a merge goes on with VK_MERGE_CONTINUE on the host exactly as Volume.merge does on the device.
+The units and bounds of every call are converted where the per-operation GPU tests convert them (the statements' keywords()
+helpers and integrate_rays_reference.bounds); a merge goes on with VK_MERGE_CONTINUE on the host exactly as Volume.merge does on the device.
 
 Two of the read steps compare the terms of a registration, which the C++ class layer does not expose: their class_host is the
 statement of the loop the class makes instead, for tests/test_gpu_chain_replay.py, which runs the same chains through that layer
@@ -29,9 +29,6 @@ import release_reference as R
 import sample_reference as S
 import score_poses_reference as SP
 import scenes
-import test_gpu_carve_rays as CVT
-import test_gpu_color_rays as COT
-import test_gpu_release as RT
 from vulcan_amd import vk_types as T
 
 f32 = np.float32
@@ -165,9 +162,9 @@ def integrate_rays(quarter, pose=None, flags=0, cap=16.0, on="map"):
 
 
 def color_rays(quarter, pose=None, flags=0, cap=16.0, band=None, on="map"):
-    """`band` in metres (None: the truncation length), converted like the bounds by test_gpu_color_rays.keywords"""
+    """`band` in metres (None: the truncation length), converted like the bounds by color_rays_reference.keywords"""
     units, one = _form(flags)
-    r_min, r_max, kw = COT.keywords(flags, {"band": band})
+    r_min, r_max, kw = CO.keywords(flags, {"band": band})
 
     def host(orc, volumes):
         rays, ranges = rays_of(orc, quarter, units)
@@ -191,7 +188,7 @@ def color_rays(quarter, pose=None, flags=0, cap=16.0, band=None, on="map"):
 
 def carve_rays(quarter, pose=None, flags=0, cap=16.0, stretch=BEYOND, on="map"):
     units, one = _form(flags)
-    r_min, r_max, kw = CVT.keywords(flags, {})
+    r_min, r_max, kw = CV.keywords(flags, {})
 
     def host(orc, volumes):
         rays, ranges = rays_of(orc, quarter, units, stretch)
@@ -212,11 +209,11 @@ def carve_rays(quarter, pose=None, flags=0, cap=16.0, stretch=BEYOND, on="map"):
 
 
 def release_blocks(rule, on="map"):
-    """`rule`: a key of test_gpu_release.RULES"""
-    keywords = RT.RULES[rule]
+    """`rule`: a key of release_reference.RULES"""
+    keywords = R.RULES[rule]
 
     def host(orc, volumes):
-        return R.release_blocks(volumes[on], *RT.helper_arguments(keywords))
+        return R.release_blocks(volumes[on], *R.helper_arguments(keywords))
 
     def device(orc, side, want):
         return side.volumes[on].release_blocks(**keywords)
@@ -279,7 +276,7 @@ def merge(on, source, pose=None, max_rounds=8):
 
 
 def frame(yaw_deg, on="map"):
-    """three SetView rounds, a depth integration and a raycast at `yaw_deg`, as test_gpu_release.continue_both makes them —
+    """three SetView rounds, a depth integration and a raycast at `yaw_deg`, as gpu_support.continue_both makes them —
     but with the volume's one Tracer, attached before the integration, so that the integrate launch prepares the raycast's
     bounds ahead as in the frame loop: ((depth, colour, normals) of the raycast, whether a SetView round dropped a request)"""
     def host(orc, volumes):
@@ -428,7 +425,7 @@ def register_terms(on, source, pose):
 
 
 def _rays_form():
-    """(flags, r_min, r_max) of rays in metres, as test_gpu_register_rays.form gives them"""
+    """(flags, r_min, r_max) of rays in metres, as gpu_support.form gives them"""
     return (0,) + IR.bounds(False)
 
 
@@ -488,6 +485,23 @@ def same(got, want):
     return got == want
 
 
+def first_difference(got, want):
+    """which part of what a step returned is not the statement's, for the message of a failing step"""
+    if isinstance(want, (tuple, list)) and not all(isinstance(w, (int, np.integer)) for w in want):
+        for k, (g, w) in enumerate(zip(got, want)):
+            if not same(g, w):
+                return f"[{k}] {first_difference(g, w)}"
+    if isinstance(want, np.ndarray):
+        got = np.ascontiguousarray(got)
+        if got.shape != want.shape or got.dtype != want.dtype:
+            return f"{got.dtype}{got.shape} for {want.dtype}{want.shape}"
+        if got.size == 0:
+            return "nothing"
+        rows = np.flatnonzero(got.reshape(len(got), -1).view(np.uint8) != np.ascontiguousarray(want).reshape(len(want), -1).view(np.uint8))
+        return f"{len(rows)} bytes differ"
+    return f"{got} for {want}"
+
+
 # ---- the chains ----------------------------------------------------------------------------------------------------------
 
 class Chain:
@@ -545,7 +559,7 @@ def pose_buffer():
 # no block by definition, so a chain that draws it cannot pass that test and its seed is not among these: the repair alone is
 # a step of ray_map and of exhausted.
 SEEDS = (1, 8, 9, 12, 15, 17)
-RULES = list(RT.RULES)
+RULES = list(R.RULES)
 OPERATIONS = ("integrate_rays", "color_rays", "carve_rays", "release_blocks", "merge")
 
 
@@ -626,7 +640,7 @@ class Snapshot:
 class Record:
     """one step on the host: `want` (what the statement returned), `after` ({name: a Snapshot of every volume after the step;
     a volume the step did not change shares the one before}), `defined` ({name: does every counter of
-    test_gpu_release.DEFINED_COUNTERS hold the statement's value}: a frame step leaves VK_CTR_BANDED to the device alone, the
+    gpu_support.DEFINED_COUNTERS hold the statement's value}: a frame step leaves VK_CTR_BANDED to the device alone, the
     next operation that ends on VK_CTR_BANDED = -1 defines it again)"""
 
 

@@ -10,6 +10,24 @@ from vulcan_amd import vk_types as T
 
 UNOBSERVED, NO_SURFACE, OUTSIDE_BOX = 1, 2, 4
 
+# the rule sets the tests and the chains (tests/map_life.py) release by, as the keywords of api.Volume.release_blocks
+BOX = ((-10, -8, 14), (2, 7, 16))
+RULES = {
+    "repair": {},
+    "unobserved": {"unobserved": True},
+    "no-surface": {"min_abs_distance": 0.75},
+    "unobserved+no-surface": {"unobserved": True, "min_abs_distance": 0.75},
+    "all-three": {"unobserved": True, "min_abs_distance": 0.75, "keep_box": BOX},
+}
+
+
+def helper_arguments(rule):
+    """release_blocks' arguments behind `hv` for a rule set of RULES"""
+    flags = ((UNOBSERVED if rule.get("unobserved") else 0) | (NO_SURFACE if "min_abs_distance" in rule else 0) |
+             (OUTSIDE_BOX if "keep_box" in rule else 0))
+    lo, hi = rule.get("keep_box", ((0, 0, 0), (0, 0, 0)))
+    return flags, rule.get("min_abs_distance", 0.0), lo, hi
+
 
 def chain(entries, bucket, limit):
     """entry indices of main bucket `bucket`'s chain, entry `bucket` first (a `next` outside the table ends it)"""

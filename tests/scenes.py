@@ -61,6 +61,12 @@ def checker_color(w, h, lo=0.0, hi=1.0):
     return c
 
 
+def cloud(n, seed, centre=(0.3, -0.2, 1.0), sigma=0.05):
+    """a seeded Gaussian point cloud [n, 3] for the detector tests"""
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0.0, sigma, size=(n, 3)) + np.asarray(centre)).astype(np.float32)
+
+
 def tracer_test_pose():
     """Tcw of tracer_test.cu:267-271; returns Twc = Tcw.Inverse()."""
     tcw = T.Transform.translate(0.3, -1.3, 3.7) * T.Transform.rotate(0.7474, 0.3438, -0.3884, 0.4152)

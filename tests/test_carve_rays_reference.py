@@ -10,6 +10,7 @@ import pytest
 
 from abi_support import fake_volume
 import carve_rays_reference as CV
+from carve_rays_reference import state_but_voxels
 import cast_reference as CR
 import integrate_rays_reference as IR
 import register_reference as RR
@@ -22,11 +23,6 @@ SMALL, LARGE = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
 # percentile 4.19e-3 m, 5.14e-3 m at worst, measured on this statement. Asserted: twice the measured maximum, the margin for
 # nothing more than another host libm or numpy build (as test_integrate_rays_reference.py does).
 SCENARIO_BOUND = 2 * 5.14e-3
-
-
-def state_but_voxels(hv):
-    return (hv.hash_entries.tobytes(), hv.free_voxel_blocks.tobytes(), hv.block_visibility.tobytes(), hv.allocation_types.tobytes(),
-            hv.allocation_blocks.tobytes(), hv.visible_blocks.tobytes(), hv.counters.tobytes())
 
 
 def test_the_statements_walk_is_integrate_rays_walk(orc):

@@ -23,7 +23,7 @@ import extract_attributes_reference as A
 import integrate_rays_reference as IR
 import register_reference as RR
 import release_reference as R
-from test_carve_rays_reference import state_but_voxels
+from carve_rays_reference import state_but_voxels
 from vulcan_amd import vk_types as T
 
 f32 = np.float32

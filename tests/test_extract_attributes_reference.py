@@ -12,8 +12,7 @@ import numpy as np
 import pytest
 
 import extract_attributes_reference as A
-
-ANGLE_P99_DEGREES = 62.71       # measured by test_normals_follow_the_analytic_surface (62.702), rounded up
+from extract_attributes_reference import ANGLE_P99_DEGREES
 
 
 @pytest.fixture(scope="module")

@@ -18,22 +18,10 @@ def golden():
     return np.load(mf.FILE)
 
 
-def compare(got, golden, name):
-    for key, value in got.items():
-        want = golden[f"{name}/{key}"]
-        value = np.asarray(value)
-        if value.dtype.kind in "US":
-            assert str(value) == str(want), (name, key)
-        elif value.dtype.kind == "f":
-            assert np.array_equal(value.view(np.uint32), want.view(np.uint32)), (name, key)     # bit for bit, NaN included
-        else:
-            assert np.array_equal(value, want), (name, key)
-
-
 @pytest.mark.parametrize("name", mf.SCENES)
 def test_oracle_reproduces_the_golden_vectors(orc, golden, name):
     orc.set_threads(8)
-    compare(mf.run_scene(mf.oracle_backend, name), golden, name)
+    mf.compare(mf.run_scene(mf.oracle_backend, name), golden, name)
     orc.set_threads(1)
 
 
@@ -51,7 +39,7 @@ def test_oracle_reproduces_the_step_cap_vectors(orc):
     assert os.path.exists(mf.STEP_CAP_FILE), "run python tests/golden/make_fixtures.py --step-cap-only"
     golden = np.load(mf.STEP_CAP_FILE)
     orc.set_threads(8)
-    compare(mf.step_cap_oracle(), golden, "step_cap")
+    mf.compare(mf.step_cap_oracle(), golden, "step_cap")
     orc.set_threads(1)
     color, depth = golden["step_cap/color"], golden["step_cap/depth"]
     capped = (color[..., 0] == 1) & (color[..., 1] == 0) & (color[..., 2] == 0)

@@ -12,13 +12,11 @@ import pytest
 import cast_reference as CR
 import merge_pose_reference as MP
 import sample_reference as S
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_release import device_copy
+from gpu_support import OTHER, SAME, api, device_copy, on_device, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
 
-SAME, OTHER = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
 FORMS = [0, CR.VOXEL_UNITS, CR.DISTANCE_ONLY, CR.VOXEL_UNITS | CR.DISTANCE_ONLY]
 _HOST, _DEVICE, _STATE = {}, {}, {}
 
@@ -30,11 +28,6 @@ def volumes(api, orc, sizes=SAME):
         _HOST[sizes] = CR.volume(orc, sizes)
         _DEVICE[sizes] = device_copy(api, _HOST[sizes])
     return _HOST[sizes], _DEVICE[sizes]
-
-
-def on_device(rays):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(rays, dtype=np.float32)).cuda()
 
 
 def statement(orc, hv, flags, pose=None, **bounds):

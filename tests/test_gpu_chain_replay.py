@@ -22,7 +22,7 @@ import pytest
 
 import chain_files as CF
 import map_life as ML
-from test_gpu_map_life import assert_arrays_state, first_difference
+from gpu_support import assert_arrays_state
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
@@ -56,7 +56,7 @@ def as_bytes_of(got, want):
 
 def assert_returns(got, want):
     got = tuple(as_bytes_of(g, w) for g, w in zip(got, want))
-    assert len(got) == len(want) and ML.same(got, tuple(want)), first_difference(got, tuple(want))
+    assert len(got) == len(want) and ML.same(got, tuple(want)), ML.first_difference(got, tuple(want))
 
 
 def assert_loop(got, want):

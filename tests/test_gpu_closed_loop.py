@@ -17,7 +17,7 @@ import pytest
 
 import scenes
 from closed_loop_oracle import oracle_loop
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
+from gpu_support import api, assert_volume_equal, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

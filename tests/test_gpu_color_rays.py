@@ -14,86 +14,19 @@ import cast_reference as CR
 import color_rays_reference as CO
 import extract_attributes_reference as A
 import integrate_rays_reference as IR
-import merge_pose_reference as MP
 import merge_reference as M
 import release_reference as R
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
-from test_gpu_release import assert_same_state, device_copy
+from gpu_support import OTHER, SAME, api, assert_same_state, assert_volume_equal, device_copy, on_device, sync  # noqa: F401
+from ray_call_support import RayCall
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
 
-SAME, OTHER = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
 FORMS = [0, CO.VOXEL_UNITS, CO.ONE_OBSERVATION, CO.VOXEL_UNITS | CO.ONE_OBSERVATION]
 ONE_VOXEL, TWO_VOXELS = float(np.float32(R.VOXEL)), CO.TWO_VOXELS
-_WANT = {}
-
-
-def start(orc, sizes, target):
-    """a host volume the call starts from: the scene volume of cast_reference at these table sizes, or a fresh one"""
-    return R.clone(orc, CR.volume(orc, sizes)) if target == "scene" else M.fresh(orc, *sizes[0])
-
-
-def on_device(array):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(array, dtype=np.float32)).cuda()
-
-
-def all_rays(orc, voxel_units):
-    """(rays, ranges, colours): integrate_rays' seven sets, one after the other, with the seeded colours"""
-    rays, ranges = IR.all_rays(orc, voxel_units)
-    return rays, ranges, CO.colors_for(len(ranges))
-
-
-def keywords(flags, kw):
-    """the statement's and the device call's keywords for one case: the band is given in metres (None: the truncation length)
-    and converted like the bounds"""
-    units = bool(flags & CO.VOXEL_UNITS)
-    r_min, r_max = IR.bounds(units)
-    kw = dict(kw)
-    band = np.float32(R.TRUNCATION if kw.get("band") is None else kw["band"])
-    kw["band"] = float(band / np.float32(R.VOXEL)) if units else float(band)
-    return r_min, r_max, kw
-
-
-def statement(orc, sizes, target, flags, pose=None, **kw):
-    """(host volume after the statement, its Result) on all_rays in the form `flags`: once per case, never changed"""
-    key = (sizes, target, flags, None if pose is None else bytes(pose), tuple(sorted(kw.items())))
-    if key not in _WANT:
-        hv = start(orc, sizes, target)
-        r_min, r_max, kw = keywords(flags, kw)
-        _WANT[key] = (hv, CO.color(hv, *all_rays(orc, bool(flags & CO.VOXEL_UNITS)), pose=pose, r_min=r_min, r_max=r_max, flags=flags, **kw))
-    return _WANT[key]
-
-
-def call(dv, rays, ranges, colors, pose, flags, **kw):
-    r_min, r_max, kw = keywords(flags, kw)
-    kw.setdefault("max_color_weight", kw.pop("cap", 16.0))
-    return dv._color_rays_call(rays, ranges, colors, pose, flags, r_min=r_min, r_max=r_max, **kw)
-
-
-def assert_untouched(dv, before):
-    """what the call must leave byte for byte as it found it: everything but the voxels"""
-    sync()
-    assert np.array_equal(dv.host_entries(), before.hash_entries)
-    assert np.array_equal(dv.host_visibility(), before.block_visibility)
-    assert np.array_equal(dv.free_voxel_blocks.cpu().numpy(), before.free_voxel_blocks)
-    assert np.array_equal(dv.host_allocation_types(), before.allocation_types)
-    assert np.array_equal(dv.host_allocation_blocks(), before.allocation_blocks)
-    assert np.array_equal(dv.read_counters(), before.counters[:T.VK_CTR_PUBLIC])
-
-
-def both(api, orc, sizes, target, flags, pose=None, device_pose="same", **kw):
-    hv, want = statement(orc, sizes, target, flags, pose, **kw)
-    before = start(orc, sizes, target)
-    dv = device_copy(api, before)
-    rays, ranges, colors = all_rays(orc, bool(flags & CO.VOXEL_UNITS))
-    got = call(dv, on_device(rays), on_device(ranges), on_device(colors), pose if device_pose == "same" else device_pose, flags, **kw)
-    print("counts", got, want.counts)
-    assert got == want.counts
-    assert_same_state(dv, hv)                       # the voxels the statement leaves; entries, visibility, free list, counters
-    assert_untouched(dv, before)
-    return dv, hv, want
+all_rays = CO.all_rays
+CALL = RayCall(CO.color, all_rays, "_color_rays_call", "max_color_weight", CO.keywords, voxels_only=True)
+start, statement, call, both = CALL.start, CALL.statement, CALL.call, CALL.both
 
 
 @pytest.mark.parametrize("target", ["scene", "fresh"])
@@ -119,16 +52,8 @@ def test_the_cap_reached(api, orc):
 
 @pytest.mark.parametrize("flags", [0, CO.VOXEL_UNITS], ids=["metres", "voxel-units"])
 def test_a_pose_on_the_device(api, orc, flags):
-    import torch
-    dv, hv, want = both(api, orc, SAME, "scene", flags, MP.generic())
+    want, _, _ = CALL.a_pose_on_the_device(api, orc, SAME, flags)
     assert want.counts[0] > 20000 and want.counts[5] > 10000
-    # a device buffer that already holds the pose: the same call
-    pose_dev = torch.as_tensor(np.frombuffer(bytes(MP.generic()), dtype=np.uint8).copy()).cuda()
-    both(api, orc, SAME, "scene", flags, MP.generic(), device_pose=pose_dev)
-    # the identity pose against no pose: the statement of each, and the same volume
-    _, with_identity, _ = both(api, orc, SAME, "scene", flags, T.Transform.identity())
-    without, _ = statement(orc, SAME, "scene", flags)
-    assert with_identity.voxels.tobytes() == without.voxels.tobytes()
 
 
 @pytest.mark.parametrize("band", [ONE_VOXEL, TWO_VOXELS, None], ids=["one-voxel", "two-voxels", "truncation-length"])

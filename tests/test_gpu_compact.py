@@ -6,7 +6,7 @@ entries. Plus what the reference's atomics cannot promise: the ranges are in inp
 import numpy as np
 import pytest
 
-from test_gpu_parity import api, sync  # noqa: F401
+from gpu_support import api, sync  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

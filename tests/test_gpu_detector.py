@@ -5,8 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_parity import api, sync  # noqa: F401  (fixture)
-from test_oracle_detector import cloud
+from gpu_support import api, sync  # noqa: F401
+from scenes import cloud
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import scenes
-from test_gpu_parity import api, assert_volume_equal, frames, make_pair, sync  # noqa: F401
+from gpu_support import api, assert_volume_equal, frames, make_pair, sync  # noqa: F401
 from vulcan_amd import io as vio, vk_types as T
 
 pytestmark = pytest.mark.gpu

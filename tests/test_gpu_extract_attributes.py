@@ -8,8 +8,8 @@ import pytest
 
 import extract_attributes_reference as A
 import scenes
-from test_extract_attributes_reference import ANGLE_P99_DEGREES
-from test_gpu_parity import api, sync  # noqa: F401
+from extract_attributes_reference import ANGLE_P99_DEGREES
+from gpu_support import api, device_copy, sync  # noqa: F401
 from vulcan_amd import io as vio, vk_types as T
 
 pytestmark = pytest.mark.gpu
@@ -26,12 +26,6 @@ def reference(orc, key, hv, all_allocated, interpolate):
         colors, normals = A.extract_attributes(orc, hv, all_allocated, interpolate, statistics)
         _REFERENCE[key] = (points, faces, skipped, colors, normals, statistics)
     return _REFERENCE[key]
-
-
-def device_copy(api, hv):
-    dv = api.Volume(hv.main, hv.excess, voxel_length=hv.voxel_length, truncation_length=hv.truncation_length)
-    dv.upload(hv)
-    return dv
 
 
 def bits(a):

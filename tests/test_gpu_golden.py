@@ -8,13 +8,12 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import api, sync  # noqa: F401
+from gpu_support import api, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_fixtures as mf  # noqa: E402
-from test_golden import compare  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +60,7 @@ def test_device_reproduces_the_golden_vectors(api, name):
     want = golden[f"{name}/counters"].copy()
     for i in (T.VK_CTR_PENDING_ALL, T.VK_CTR_PENDING_EXCESS, T.VK_CTR_REQUESTS, T.VK_CTR_PATCHES):
         got["counters"][i] = want[i]
-    compare(got, golden, name)
+    mf.compare(got, golden, name)
 
 
 def test_device_reproduces_the_step_cap_vectors(api):
@@ -80,7 +79,7 @@ def test_device_reproduces_the_step_cap_vectors(api):
     got = dict(depth=out.depth.cpu().numpy(), color=out.color.cpu().numpy(), normals=out.normals.cpu().numpy(),
                bounds=tracer.bounds.cpu().numpy(), visible=np.sort(dv.visible()),
                entries_sha256=mf.digest(dv.host_entries()), voxels_sha256=mf.digest(dv.host_voxels()))
-    compare(got, golden, "step_cap")
+    mf.compare(got, golden, "step_cap")
     capped, hit = step_cap.classify(got["depth"], got["color"])
     assert capped.sum() > 1200 and hit.sum() > 1200
 

@@ -13,57 +13,17 @@ import pytest
 
 import cast_reference as CR
 import integrate_rays_reference as IR
-import merge_pose_reference as MP
 import merge_reference as M
 import release_reference as R
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_release import assert_same_state, device_copy
+from gpu_support import OTHER, SAME, api, assert_same_state, device_copy, on_device, sync  # noqa: F401
+from ray_call_support import RayCall
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
 
-SAME, OTHER = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
 FORMS = [0, IR.VOXEL_UNITS, IR.ONE_OBSERVATION, IR.VOXEL_UNITS | IR.ONE_OBSERVATION]
-_WANT = {}
-
-
-def start(orc, sizes, target):
-    """a host volume the call starts from: the scene volume of cast_reference at these table sizes, or a fresh one"""
-    return R.clone(orc, CR.volume(orc, sizes)) if target == "scene" else M.fresh(orc, *sizes[0])
-
-
-def on_device(array):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(array, dtype=np.float32)).cuda()
-
-
-def statement(orc, sizes, target, flags, pose=None, **kw):
-    """(host volume after the statement, its Result) on all_rays in the form `flags`: once per case, never changed"""
-    key = (sizes, target, flags, None if pose is None else bytes(pose), tuple(sorted(kw.items())))
-    if key not in _WANT:
-        units = bool(flags & IR.VOXEL_UNITS)
-        hv = start(orc, sizes, target)
-        rays, ranges = IR.all_rays(orc, units)
-        r_min, r_max = IR.bounds(units)
-        _WANT[key] = (hv, IR.integrate(hv, rays, ranges, pose=pose, r_min=r_min, r_max=r_max, flags=flags, **kw))
-    return _WANT[key]
-
-
-def call(dv, rays, ranges, pose, flags, **kw):
-    r_min, r_max = IR.bounds(bool(flags & IR.VOXEL_UNITS))
-    kw.setdefault("max_distance_weight", kw.pop("cap", 16.0))
-    return dv._integrate_rays_call(rays, ranges, pose, flags, r_min=r_min, r_max=r_max, **kw)
-
-
-def both(api, orc, sizes, target, flags, pose=None, device_pose="same", **kw):
-    hv, want = statement(orc, sizes, target, flags, pose, **kw)
-    dv = device_copy(api, start(orc, sizes, target))
-    rays, ranges = IR.all_rays(orc, bool(flags & IR.VOXEL_UNITS))
-    got = call(dv, on_device(rays), on_device(ranges), pose if device_pose == "same" else device_pose, flags, **kw)
-    print("counts", got, want.counts)
-    assert got == want.counts
-    assert_same_state(dv, hv)
-    return dv, hv, want
+CALL = RayCall(IR.integrate, IR.all_rays, "_integrate_rays_call", "max_distance_weight", IR.keywords, voxels_only=False)
+start, statement, call, both = CALL.start, CALL.statement, CALL.call, CALL.both
 
 
 @pytest.mark.parametrize("target", ["scene", "fresh"])
@@ -81,16 +41,8 @@ def test_bit_for_bit(api, orc, sizes, flags, target):
 
 @pytest.mark.parametrize("flags", [0, IR.VOXEL_UNITS], ids=["metres", "voxel-units"])
 def test_a_pose_on_the_device(api, orc, flags):
-    import torch
-    dv, hv, want = both(api, orc, SAME, "scene", flags, MP.generic())
+    want, with_identity, without = CALL.a_pose_on_the_device(api, orc, SAME, flags)
     assert want.counts[0] > 20000 and want.counts[6] > 100000
-    # a device buffer that already holds the pose: the same call
-    pose_dev = torch.as_tensor(np.frombuffer(bytes(MP.generic()), dtype=np.uint8).copy()).cuda()
-    both(api, orc, SAME, "scene", flags, MP.generic(), device_pose=pose_dev)
-    # the identity pose against no pose: the statement of each, and the same volume
-    _, with_identity, _ = both(api, orc, SAME, "scene", flags, T.Transform.identity())
-    without, _ = statement(orc, SAME, "scene", flags)
-    assert with_identity.voxels.tobytes() == without.voxels.tobytes()
     assert np.array_equal(with_identity.hash_entries, without.hash_entries)
 
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import color_scenes as cs
-from test_gpu_parity import api, sync  # noqa: F401  (fixture)
+from gpu_support import api, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

@@ -18,8 +18,8 @@ import time
 import pytest
 
 import long_run
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_tracked_bench_step import POSE_ATOL, pin_bench_defaults
+from closed_loop_oracle import POSE_ATOL
+from gpu_support import api, pin_bench_defaults, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

@@ -13,7 +13,7 @@ import pytest
 
 import color_scenes as cs
 import scenes
-from test_gpu_parity import api, sync  # noqa: F401  (fixture)
+from gpu_support import api, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

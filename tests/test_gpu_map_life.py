@@ -14,9 +14,7 @@ import numpy as np
 import pytest
 
 import map_life as ML
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
-from test_gpu_release import assert_arrays_same_state, device_copy, state_arrays
-from vulcan_amd import vk_types as T
+from gpu_support import api, assert_arrays_state, device_copy, state_arrays, sync  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +44,7 @@ def held_tensors(side):
     return workspaces, counts
 
 
-def overwrite(side, how, generator):
+def overwrite_held(side, how, generator):
     import torch
     workspaces, counts = held_tensors(side)
     for tensor in workspaces:
@@ -59,53 +57,10 @@ def overwrite(side, how, generator):
         tensor.fill_(SENTINEL)
 
 
-def assert_arrays_volume_equal(got, hv):
-    """test_gpu_parity.assert_volume_equal on the arrays of test_gpu_release.state_arrays"""
-    ctr = got["counters"]
-    for i in (T.VK_CTR_VISIBLE, T.VK_CTR_VOXEL_PTR, T.VK_CTR_EXCESS_PTR, T.VK_CTR_DROPPED):
-        assert ctr[i] == hv.counters[i], (i, ctr, hv.counters)
-    assert np.array_equal(got["hash_entries"], hv.hash_entries)
-    assert np.array_equal(got["block_visibility"], hv.block_visibility)
-    assert np.array_equal(got["allocation_types"], hv.allocation_types)
-    assert np.array_equal(got["allocation_blocks"], hv.allocation_blocks)
-    n = int(ctr[T.VK_CTR_VISIBLE])
-    assert np.array_equal(np.sort(got["visible_blocks"][:n]), hv.visible())     # order is unspecified (volume.cu:80-83)
-    assert got["voxels"].tobytes() == hv.voxels.tobytes()
-
-
-def assert_arrays_state(got, hv, defined):
-    """the arrays of test_gpu_release.state_arrays hold the host's state. `defined`: VK_CTR_BANDED is the statements' too —
-    everything test_gpu_release's assert_same_state compares; after a frame step it is the device's own, and the comparison
-    is continue_both's: the volume, and the free list up to VK_CTR_VOXEL_PTR"""
-    if defined:
-        assert_arrays_same_state(got, hv, all_counters=False)
-        return
-    assert_arrays_volume_equal(got, hv)
-    free = max(int(hv.counters[T.VK_CTR_VOXEL_PTR]) + 1, 0)
-    assert np.array_equal(got["free_voxel_blocks"][:free], hv.free_voxel_blocks[:free])
-
-
 def assert_state(dv, hv, defined):
     """the device holds the host's state (assert_arrays_state)"""
     sync()
     assert_arrays_state(state_arrays(dv), hv, defined)
-
-
-def first_difference(got, want):
-    """which part of what a step returned is not the statement's, for the message of a failing step"""
-    if isinstance(want, (tuple, list)) and not all(isinstance(w, (int, np.integer)) for w in want):
-        for k, (g, w) in enumerate(zip(got, want)):
-            if not ML.same(g, w):
-                return f"[{k}] {first_difference(g, w)}"
-    if isinstance(want, np.ndarray):
-        got = np.ascontiguousarray(got)
-        if got.shape != want.shape or got.dtype != want.dtype:
-            return f"{got.dtype}{got.shape} for {want.dtype}{want.shape}"
-        if got.size == 0:
-            return "nothing"
-        rows = np.flatnonzero(got.reshape(len(got), -1).view(np.uint8) != np.ascontiguousarray(want).reshape(len(want), -1).view(np.uint8))
-        return f"{len(rows)} bytes differ"
-    return f"{got} for {want}"
 
 
 def run_on_device(api, orc, chain, workspaces="as-allocated", keep=True):
@@ -127,10 +82,10 @@ def run_on_device(api, orc, chain, workspaces="as-allocated", keep=True):
         try:
             if workspaces != "as-allocated" and step.kind != ML.FRAME:
                 step.workspace(side)
-                overwrite(side, workspaces, generator)
+                overwrite_held(side, workspaces, generator)
             got = step.device(orc, side, record.want)
             sync()
-            assert ML.same(got, record.want), first_difference(got, record.want)
+            assert ML.same(got, record.want), ML.first_difference(got, record.want)
             if workspaces != "as-allocated" and step.kind == ML.MUTATE:          # the counts came from the call, not from the sentinel
                 assert SENTINEL not in got
             # the state: behind every step that changes a volume, and behind the last read of a checkpoint
@@ -178,7 +133,7 @@ def test_a_second_volume_object_sees_the_same_map(api, orc):
     for record in run.records[at + 1:]:
         got = record.step.device(orc, again, record.want)
         sync()
-        assert ML.same(got, record.want), f"{record.step.name}: {first_difference(got, record.want)}"
+        assert ML.same(got, record.want), f"{record.step.name}: {ML.first_difference(got, record.want)}"
     for name in BUFFERS:
         assert getattr(second, name).cpu().numpy().tobytes() == getattr(first, name).cpu().numpy().tobytes(), name
     assert_state(second, run.records[-1].after["map"].restore(orc), run.records[-1].defined["map"])

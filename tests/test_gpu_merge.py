@@ -12,8 +12,7 @@ import pytest
 from abi_support import fake_volume
 import merge_reference as M
 import release_reference as R
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
-from test_gpu_release import assert_same_state, continue_both, device_copy
+from gpu_support import api, assert_same_state, assert_volume_equal, continue_both, device_copy, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

@@ -16,8 +16,7 @@ from abi_support import fake_volume
 import merge_reference as M
 import pack_reference as P
 import release_reference as R
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
-from test_gpu_release import assert_same_state, continue_both, device_copy
+from gpu_support import api, assert_same_state, assert_volume_equal, continue_both, device_copy, overwrite, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
@@ -26,16 +25,6 @@ SIZES = [(509, 4096), (4093, 2048)]
 BOX = ((4, -6, 13), (10, 4, 16))        # cuts state "b" and holds some of its 26 unobserved blocks (test_pack_reference.py)
 POISON = 0xA5
 BLOCK_BYTES = 10240
-
-
-def overwrite(tensor, fill, seed):
-    import torch
-    if fill == "noise":
-        generator = torch.Generator(device="cpu").manual_seed(seed)
-        raw = torch.randint(0, 256, (tensor.numel() * tensor.element_size(),), dtype=torch.uint8, generator=generator)
-        tensor.view(torch.uint8).copy_(raw.to(tensor.device))
-    else:
-        tensor.view(torch.uint8).fill_(0xFF)
 
 
 def dirty(dv, operation, size, workspace_bytes, counts, fill="noise"):

@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_parity import api, sync  # noqa: F401
+from gpu_support import api, sync  # noqa: F401
 from vulcan_amd import io, vk_types as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -10,53 +10,10 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import _without_parameter, api, assert_volume_equal, frames, make_pair, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch
-    assert torch.cuda.is_available()
-    from vulcan_amd import api as a
-    a.lib()
-    return a
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def assert_volume_equal(dv, hv, voxels=True, order_free_visible=True):
-    """Whole-state comparison; allocation is deterministic on both sides (max-key
-    winner, scan-ordered slots), so raw buffers must match byte for byte."""
-    sync()
-    ctr = dv.read_counters()
-    for i in (T.VK_CTR_VISIBLE, T.VK_CTR_VOXEL_PTR, T.VK_CTR_EXCESS_PTR, T.VK_CTR_DROPPED):
-        assert ctr[i] == hv.counters[i], (i, ctr, hv.counters)
-    assert np.array_equal(dv.host_entries(), hv.hash_entries)
-    assert np.array_equal(dv.host_visibility(), hv.block_visibility)
-    assert np.array_equal(dv.host_allocation_types(), hv.allocation_types)
-    assert np.array_equal(dv.host_allocation_blocks(), hv.allocation_blocks)
-    n = int(ctr[T.VK_CTR_VISIBLE])
-    got = dv.visible_blocks[:n].cpu().numpy()
-    assert np.array_equal(np.sort(got), hv.visible())     # order is unspecified (volume.cu:80-83)
-    if voxels:
-        assert dv.host_voxels().tobytes() == hv.voxels.tobytes()
-
-
-def make_pair(api, orc, main, excess, voxel, trunc):
-    hv = orc.HostVolume(main, excess, voxel_length=voxel, truncation_length=trunc)
-    dv = api.Volume(main, excess, voxel_length=voxel, truncation_length=trunc)
-    return hv, dv
-
-
-def frames(api, orc, depth, k, pose, color=None, normals=None):
-    hf = orc.HostFrame(depth, k, pose, color=color, normals=normals)
-    df = api.Frame(depth, k, pose, color=color, normals=normals)
-    return hf, df
 
 
 # ------------------------------------------------------------------ volume --
@@ -484,17 +441,6 @@ def test_icp_track_converges(api, orc, icp_frames):
     np.testing.assert_allclose(got.matrix(), pose.matrix(), atol=2e-5)
     np.testing.assert_allclose(got.matrix(), np.eye(4), atol=5e-4)       # converged to the keyframe pose
     np.testing.assert_allclose(got.matrix() @ got.inverse_matrix(), np.eye(4), atol=1e-5)
-
-
-def _without_parameter(packed, gradient, n, drop):
-    """The packed n x n system with row and column `drop` zeroed (and that gradient entry): rank n - 1."""
-    H = np.zeros((n, n), np.float32)
-    H[np.tril_indices(n)] = packed[: n * (n + 1) // 2]
-    H[drop, :] = 0
-    H[:, drop] = 0
-    g = np.array(gradient[:n], np.float32)
-    g[drop] = 0
-    return H[np.tril_indices(n)].copy(), g
 
 
 @pytest.fixture(scope="module")

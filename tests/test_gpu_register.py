@@ -12,13 +12,11 @@ import merge_pose_reference as MP
 import merge_reference as M
 import register_reference as RR
 import release_reference as R
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_release import device_copy
+from gpu_support import OTHER, SAME, api, assert_system, device_copy, pair_on_device, same_bits, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
 
-SAME, OTHER = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
 _LOOP = {}
 
 
@@ -30,28 +28,10 @@ def statement_loop(orc):
     return _LOOP["loop"]
 
 
-def volumes(api, orc, truth, sizes=SAME, frames=(2, 3)):
-    hd, hs = RR.pair(orc, truth, sizes, frames)
-    return hd, hs, device_copy(api, hd), device_copy(api, hs)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def assert_system(got, want, absolute):
-    """test_icp_system's rule"""
-    error = np.abs(got.astype(np.float64) - want)
-    bound = 2e-5 * absolute + 1e-12
-    print("system: worst error / bound", float((error / bound).max()))
-    assert (error <= bound).all()
-    assert not got[21:36].any() and not got[43:48].any()
-
-
 @pytest.mark.parametrize("sizes", [SAME, OTHER], ids=["long-chains", "other-bucket-count"])
 @pytest.mark.parametrize("pose", ["generic", "identity"])
 def test_terms_bit_for_bit(api, orc, sizes, pose):
-    hd, hs, dd, ds = volumes(api, orc, MP.generic(), sizes)
+    hd, hs, dd, ds = pair_on_device(api, orc, MP.generic(), sizes)
     pose = MP.generic() if pose == "generic" else T.Transform.identity()
     want = RR.terms(RR.Pair(hd, hs), pose, 0.75)
     valid, residuals, jacobians = dd._register_terms_call(ds, pose, 0.75)
@@ -64,7 +44,7 @@ def test_terms_bit_for_bit(api, orc, sizes, pose):
 
 @pytest.mark.parametrize("sizes", [SAME, OTHER], ids=["long-chains", "other-bucket-count"])
 def test_system(api, orc, sizes):
-    hd, hs, dd, ds = volumes(api, orc, MP.generic(), sizes)
+    hd, hs, dd, ds = pair_on_device(api, orc, MP.generic(), sizes)
     evaluated = RR.terms(RR.Pair(hd, hs), MP.generic(), 0.75)
     want, absolute = RR.system(evaluated)
     got, counts = dd._register_system_call(ds, MP.generic(), 0.75)
@@ -77,7 +57,7 @@ def test_system(api, orc, sizes):
 
 def test_loop_from_the_identity(api, orc):
     want = statement_loop(orc)
-    hd, hs, dd, ds = volumes(api, orc, MP.generic())
+    hd, hs, dd, ds = pair_on_device(api, orc, MP.generic())
     pose, state, counts, system, _ = dd._register_call(ds, T.Transform.identity(), 20, 0.75)
     print("state", state, "statement", want.steps, want.code, "counts", counts, want.counts)
     print("pose: worst entry", float(np.abs(pose.matrix() - want.pose.matrix()).max()),
@@ -99,7 +79,7 @@ def test_loop_from_the_identity(api, orc):
 
 def test_three_steps(api, orc):
     want = statement_loop(orc)
-    _, _, dd, ds = volumes(api, orc, MP.generic())
+    _, _, dd, ds = pair_on_device(api, orc, MP.generic())
     pose, state, _, _, _ = dd._register_call(ds, T.Transform.identity(), 3, 0.75)
     after = want.poses[3]
     print("state", state, "worst entry", float(np.abs(pose.matrix() - after.matrix()).max()))
@@ -109,7 +89,7 @@ def test_three_steps(api, orc):
 
 
 def test_a_clone_is_already_registered(api, orc):
-    hd, _, dd, _ = volumes(api, orc, MP.generic())
+    hd, _, dd, _ = pair_on_device(api, orc, MP.generic())
     clone = device_copy(api, hd)
     start = T.Transform.identity()
     pose, state, counts, system, update = dd._register_call(clone, start, 5, 0.75)
@@ -124,14 +104,14 @@ def test_a_clone_is_already_registered(api, orc):
 
 def test_a_block_shift_has_no_residual(api, orc):
     shift = MP.shift((8, -16, 0))
-    _, _, dd, ds = volumes(api, orc, shift, frames=(2, 2))
+    _, _, dd, ds = pair_on_device(api, orc, shift, frames=(2, 2))
     system, counts = dd._register_system_call(ds, shift, 0.75)
     print("counts", counts, "sum of squares", float(system[42]))
     assert counts[2] > 100000 and float(system[42]) == 0.0
 
 
 def test_the_band(api, orc):
-    hd, hs, dd, ds = volumes(api, orc, MP.generic())
+    hd, hs, dd, ds = pair_on_device(api, orc, MP.generic())
     counts = {}
     for band in (0.5, 0.75):
         _, counts[band] = dd._register_system_call(ds, MP.generic(), band)
@@ -142,7 +122,7 @@ def test_the_band(api, orc):
 
 @pytest.mark.parametrize("metres", [10.0, 3000.0], ids=["apart", "beyond-the-block-range"])
 def test_no_overlap(api, orc, metres):
-    _, _, dd, ds = volumes(api, orc, MP.generic())
+    _, _, dd, ds = pair_on_device(api, orc, MP.generic())
     start = T.Transform.translate(metres, 0.0, 0.0) * MP.generic()
     pose, state, counts, _, update = dd._register_call(ds, start, 5, 0.75)
     print("state", state, "counts", counts)
@@ -153,7 +133,7 @@ def test_no_overlap(api, orc, metres):
 
 
 def test_an_empty_source(api, orc):
-    hd, _, dd, _ = volumes(api, orc, MP.generic())
+    hd, _, dd, _ = pair_on_device(api, orc, MP.generic())
     empty = device_copy(api, M.fresh(orc, 509, 4096))
     pose, state, counts, _, _ = dd._register_call(empty, MP.generic(), 5, 0.75)
     assert state == (1, T.VK_REGISTER_NO_OVERLAP) and counts == (0, 0, 0, 0) and bytes(pose) == bytes(MP.generic())
@@ -162,7 +142,7 @@ def test_an_empty_source(api, orc):
 def test_register_then_merge(api, orc):
     """the registered pose merges as the true pose does: the voxels that take a distance sample differ by less than 2 % (a
     cap that catches a wrong pose; the statement's pose gives 213 716 against 213 721 on the CPU)"""
-    hd, _, dd, ds = volumes(api, orc, MP.generic())
+    hd, _, dd, ds = pair_on_device(api, orc, MP.generic())
     result = dd.register(ds)
     assert result.converged
     registered = dd.merge(ds, pose=result.pose)
@@ -172,7 +152,7 @@ def test_register_then_merge(api, orc):
 
 
 def test_arguments_are_checked_on_the_host(api, orc):
-    hd, hs, dd, ds = volumes(api, orc, MP.generic())
+    hd, hs, dd, ds = pair_on_device(api, orc, MP.generic())
     b, good = dd._register_setup(ds, T.Transform.identity(), 20, 0.75)
     sync()
     lib = api.lib()

@@ -1,7 +1,7 @@
 """vk_volume_register_rays on the device against its CPU statement (tests/register_rays_reference.py). The volume starts from an
 uploaded oracle state. The per-ray terms are one defined sequence of float32 operations and equal the statement's bit for bit;
 the sums are added in float32 in the device's own fixed order and are held to the bound the depth tracker's system is held to
-(test_gpu_register.assert_system: 2e-5 of the sum of the absolute terms); a pose after the loop is held to 2e-5 per entry, the
+(gpu_support.assert_system: 2e-5 of the sum of the absolute terms); a pose after the loop is held to 2e-5 per entry, the
 project's standing bound for a tracked pose against the oracle. The rays are integrate_rays' sets (a)-(g), which reach every
 branch of the definition (tests/test_register_rays_reference.py), and the displaced sweep of register_rays_reference."""
 import numpy as np
@@ -15,36 +15,18 @@ import merge_reference as M
 import register_rays_reference as RY
 import register_reference as RR
 import release_reference as R
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_register import OTHER, SAME, assert_system, same_bits
-from test_gpu_release import device_copy
+from gpu_support import OTHER, SAME, api, assert_system, device_copy, form, on_device, same_bits, sync, world  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
 
 RUN = 512                                      # the rays of one workgroup: one row of partial sums
 RAGGED = (1, 63, 64, 65, 255, 256, 257, RUN + 1)
-_WORLDS, _WANT, _LOOP = {}, {}, {}
-
-
-def on_device(array):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(array, dtype=np.float32)).cuda()
-
-
-def world(orc, sizes):
-    if sizes not in _WORLDS:
-        _WORLDS[sizes] = RY.Map(CR.volume(orc, sizes))
-    return _WORLDS[sizes]
+_WANT, _LOOP = {}, {}
 
 
 def pose_of(name):
     return MP.generic() if name == "generic" else T.Transform.identity()
-
-
-def form(units):
-    """(flags, r_min, r_max) of a form"""
-    return (RY.VOXEL_UNITS if units else 0,) + IR.bounds(units)
 
 
 def statement(orc, sizes, units, pose, permuted=False):

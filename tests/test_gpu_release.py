@@ -9,66 +9,11 @@ import numpy as np
 import pytest
 
 import release_reference as R
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
+from gpu_support import api, assert_same_state, assert_volume_equal, continue_both, device_copy, sync  # noqa: F401
+from release_reference import RULES, helper_arguments
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
-
-BOX = ((-10, -8, 14), (2, 7, 16))
-RULES = {
-    "repair": {},
-    "unobserved": {"unobserved": True},
-    "no-surface": {"min_abs_distance": 0.75},
-    "unobserved+no-surface": {"unobserved": True, "min_abs_distance": 0.75},
-    "all-three": {"unobserved": True, "min_abs_distance": 0.75, "keep_box": BOX},
-}
-
-
-def helper_arguments(rule):
-    flags = ((R.UNOBSERVED if rule.get("unobserved") else 0) | (R.NO_SURFACE if "min_abs_distance" in rule else 0) |
-             (R.OUTSIDE_BOX if "keep_box" in rule else 0))
-    lo, hi = rule.get("keep_box", ((0, 0, 0), (0, 0, 0)))
-    return flags, rule.get("min_abs_distance", 0.0), lo, hi
-
-
-def device_copy(api, hv):
-    dv = api.Volume(hv.main, hv.excess, voxel_length=hv.voxel_length, truncation_length=hv.truncation_length)
-    dv.upload(hv)
-    return dv
-
-
-DEFINED_COUNTERS = (T.VK_CTR_VISIBLE, T.VK_CTR_VOXEL_PTR, T.VK_CTR_EXCESS_PTR, T.VK_CTR_DROPPED, T.VK_CTR_BANDED)
-
-
-def state_arrays(dv):
-    """the state of an api.Volume as host arrays, with the dtypes of the oracle's HostVolume: what the comparisons below and
-    those of test_gpu_map_life take — from a device volume here, from the files of a replay in test_gpu_chain_replay"""
-    return {"hash_entries": dv.host_entries(), "block_visibility": dv.host_visibility(),
-            "free_voxel_blocks": dv.free_voxel_blocks.cpu().numpy(), "voxels": dv.host_voxels(), "counters": dv.read_counters(),
-            "allocation_types": dv.host_allocation_types(), "allocation_blocks": dv.host_allocation_blocks(),
-            "visible_blocks": dv.visible_blocks.cpu().numpy()}
-
-
-def assert_arrays_same_state(got, hv, all_counters=True):
-    """assert_same_state on the arrays of state_arrays"""
-    assert np.array_equal(got["hash_entries"], hv.hash_entries)
-    assert np.array_equal(got["block_visibility"], hv.block_visibility)
-    assert np.array_equal(got["free_voxel_blocks"], hv.free_voxel_blocks)
-    assert got["voxels"].tobytes() == hv.voxels.tobytes()
-    counters = got["counters"]
-    print("counters", counters, hv.counters[:T.VK_CTR_PUBLIC])
-    if all_counters:
-        assert np.array_equal(counters, hv.counters[:T.VK_CTR_PUBLIC])
-    for counter in DEFINED_COUNTERS:
-        assert counters[counter] == hv.counters[counter], counter
-    assert np.array_equal(got["allocation_types"], hv.allocation_types)
-
-
-def assert_same_state(dv, hv, all_counters=True):
-    """everything the call defines, and the rest of the volume with it. `all_counters`: the device has run nothing but
-    uploads and releases, so all its public counters are the host's (the oracle does not keep the SetView statistics)"""
-    sync()
-    assert_arrays_same_state(state_arrays(dv), hv, all_counters)
 
 
 def release_both(dv, hv, rule, all_counters=True):
@@ -78,29 +23,6 @@ def release_both(dv, hv, rule, all_counters=True):
     assert got == want
     assert_same_state(dv, hv, all_counters)
     return want
-
-
-def continue_both(api, orc, dv, hv, yaw_deg):
-    """three SetView calls, a depth integration and a raycast on both sides. vk_volume_set_view_rounds ends its rounds with
-    the first round that drops a request (vk.h), so where the oracle's three calls drop one the device makes three calls too."""
-    dropped = int(hv.counters[T.VK_CTR_DROPPED])
-    want = R.continue_at(orc, hv, yaw_deg)
-    hf = R.frame_at(orc, yaw_deg)
-    df = api.Frame(hf.depth, hf.depth_projection, hf.depth_to_world)
-    if int(hv.counters[T.VK_CTR_DROPPED]) != dropped:
-        for _ in range(3):
-            dv.set_view(df)
-    else:
-        dv.set_view(df, rounds=3)
-    api.DepthIntegrator(dv).integrate(df)
-    out = api.Frame(np.zeros((R.H, R.W), np.float32), hf.depth_projection, hf.depth_to_world)
-    api.Tracer(dv).trace(out)
-    assert_volume_equal(dv, hv)
-    assert np.array_equal(dv.free_voxel_blocks.cpu().numpy()[:max(int(hv.counters[T.VK_CTR_VOXEL_PTR]) + 1, 0)],
-                          hv.free_voxel_blocks[:max(int(hv.counters[T.VK_CTR_VOXEL_PTR]) + 1, 0)])
-    for got, expected in zip((out.depth, out.color, out.normals), want):
-        assert got.cpu().numpy().tobytes() == expected.tobytes()
-    assert (want[0] > 0).sum() > 1000
 
 
 @pytest.mark.parametrize("rule", list(RULES))

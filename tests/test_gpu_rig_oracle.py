@@ -16,7 +16,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_rig_views as rv  # noqa: E402
-from test_gpu_parity import _without_parameter, api, sync  # noqa: E402,F401
+from gpu_support import _without_parameter, api, sync  # noqa: F401
 from vulcan_amd import vk_types as T  # noqa: E402
 
 pytestmark = pytest.mark.gpu

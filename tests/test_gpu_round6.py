@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import scenes
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
+from gpu_support import api, assert_volume_equal, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

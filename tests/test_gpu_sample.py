@@ -10,28 +10,19 @@ import pytest
 
 import merge_pose_reference as MP
 import merge_reference as M
-import register_reference as RR
 import sample_reference as S
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_release import device_copy
+from gpu_support import OTHER, SAME, api, device_copy, on_device, pair_on_device, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
 
-SAME, OTHER = ((509, 4096), (509, 4096)), ((4093, 2048), (509, 4096))
 FORMS = [0, S.VOXEL_UNITS, S.DISTANCE_ONLY, S.VOXEL_UNITS | S.DISTANCE_ONLY]
 _STATE = {}
 
 
 def volumes(api, orc, sizes=SAME):
     """(host dst, host src, device dst, device src) of the register tests' pair"""
-    hd, hs = RR.pair(orc, MP.generic(), sizes)
-    return hd, hs, device_copy(api, hd), device_copy(api, hs)
-
-
-def device_points(points):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32)).cuda()
+    return pair_on_device(api, orc, MP.generic(), sizes)
 
 
 def statement(orc, hv, flags, pose=None):
@@ -60,7 +51,7 @@ def assert_is_statement(got, want):
 def test_bit_for_bit(api, orc, sizes, flags):
     hd, _, dd, _ = volumes(api, orc, sizes)
     want = statement(orc, hd, flags)
-    points = device_points(S.all_points(orc, bool(flags & S.VOXEL_UNITS)))
+    points = on_device(S.all_points(orc, bool(flags & S.VOXEL_UNITS)))
     got = raw(*dd._sample_call(points, None, flags))
     d, g = want[0]["distance_weight"] != 0, want[1][:, 3] != 0
     print("points", len(points), "with distance", int(d.sum()), "with gradient", int(g.sum()), "with colour", int((want[0]["color_weight"] != 0).sum()))
@@ -74,7 +65,7 @@ def test_bit_for_bit(api, orc, sizes, flags):
 def test_a_pose_on_the_device(api, orc, flags):
     hd, _, dd, _ = volumes(api, orc)
     units = bool(flags & S.VOXEL_UNITS)
-    points = device_points(S.all_points(orc, units))
+    points = on_device(S.all_points(orc, units))
     want = statement(orc, hd, flags, MP.generic())
     got = raw(*dd._sample_call(points, MP.generic(), flags))
     print("with distance", int((want[0]["distance_weight"] != 0).sum()), "with gradient", int((want[1][:, 3] != 0).sum()))
@@ -100,7 +91,7 @@ def test_ragged_counts(api, orc, count):
     want = statement(orc, hd, 0)
     # from the middle of (a)-(b) on: vertices, then points around them
     first = 19000
-    points = device_points(S.all_points(orc, False)[first:first + count + 64])
+    points = on_device(S.all_points(orc, False)[first:first + count + 64])
 
     def buffers():
         return (torch.full((count + 64, 20), 0xA5, dtype=torch.uint8, device="cuda"),
@@ -130,7 +121,7 @@ def test_the_volume_is_only_read(api, orc):
     before = (dd.host_voxels().tobytes(), dd.host_entries().tobytes(), dd.counters.cpu().numpy().tobytes(),
               dd.host_visibility().tobytes(), dd.free_voxel_blocks.cpu().numpy().tobytes())
     for flags in FORMS:
-        dd._sample_call(device_points(S.all_points(orc, bool(flags & S.VOXEL_UNITS))), MP.generic() if flags == 0 else None, flags)
+        dd._sample_call(on_device(S.all_points(orc, bool(flags & S.VOXEL_UNITS))), MP.generic() if flags == 0 else None, flags)
     sync()
     after = (dd.host_voxels().tobytes(), dd.host_entries().tobytes(), dd.counters.cpu().numpy().tobytes(),
              dd.host_visibility().tobytes(), dd.free_voxel_blocks.cpu().numpy().tobytes())
@@ -172,7 +163,7 @@ def test_a_fresh_merge_is_the_samples_of_its_centres(api, orc):
     origins = entries["block"]["origin"][held].astype(np.int64)
     centres = ((8 * origins[:, None, :] + MP.OFFSETS[None]).astype(np.float32) + np.float32(0.5)).reshape(-1, 3)
     at = (entries["data"][held].astype(np.int64)[:, None] * 512 + np.arange(512)[None]).reshape(-1)
-    samples, _ = ds._sample_call(device_points(centres), MP.generic().inverse(), S.VOXEL_UNITS, gradients=False)
+    samples, _ = ds._sample_call(on_device(centres), MP.generic().inverse(), S.VOXEL_UNITS, gradients=False)
     want = samples.clone()
     weights = want.view(torch.int16)[:, 8:10]
     weights.clamp_(max=16)
@@ -187,7 +178,7 @@ def test_arguments_are_checked_on_the_host(api, orc):
     import torch
     hd, _, dd, _ = volumes(api, orc)
     lib = api.lib()
-    points = device_points(S.all_points(orc, False)[:64])
+    points = on_device(S.all_points(orc, False)[:64])
     samples = torch.full((64, 20), 0xA5, dtype=torch.uint8, device="cuda")
     gradients = torch.full((65, 4), -7.5, dtype=torch.float32, device="cuda")
     sync()

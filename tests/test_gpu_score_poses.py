@@ -17,10 +17,7 @@ import register_rays_reference as RY
 import register_reference as RR
 import release_reference as R
 import score_poses_reference as SP
-from test_gpu_parity import api, sync  # noqa: F401
-from test_gpu_register import OTHER, SAME
-from test_gpu_register_rays import form, on_device, world
-from test_gpu_release import device_copy
+from gpu_support import OTHER, SAME, api, device_copy, form, on_device, sync, world  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu

@@ -18,24 +18,11 @@ import numpy as np
 import pytest
 
 import scenes
-from closed_loop_oracle import oracle_loop
-from test_gpu_parity import api, assert_volume_equal, sync  # noqa: F401
+from closed_loop_oracle import POSE_ATOL, oracle_loop
+from gpu_support import api, assert_volume_equal, pin_bench_defaults, sync  # noqa: F401
 from vulcan_amd import vk_types as T
 
 pytestmark = pytest.mark.gpu
-
-POSE_ATOL = 2e-5
-
-
-def pin_bench_defaults(monkeypatch):
-    """the forms of the tracked step that bench.py times when no VK_BENCH_* variable is set — whatever the environment says"""
-    import bench
-    monkeypatch.setattr(bench, "SET_VIEW_AT_DEVICE_POSE", 2)
-    monkeypatch.setattr(bench, "PYRAMID_AHEAD", False)
-    monkeypatch.setattr(bench, "KEY_NORMALS_WITH_PYRAMID", True)
-    monkeypatch.setattr(bench, "NORMALS_IN_SET_VIEW", True)
-    return bench
-
 
 def pose_distance(a, b):
     """largest |a - b| over the entries of the matrix and of the inverse matrix"""

@@ -33,7 +33,7 @@ import numpy as np
 import pytest
 
 import tracker_sum_cases as tc
-from test_gpu_parity import api, sync  # noqa: F401  (fixture)
+from gpu_support import api, sync  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -5,12 +5,8 @@ text: FilterKernel :14-35, GetValidPosition :131-141, Filter :152-188."""
 import numpy as np
 import pytest
 
+from scenes import cloud
 from vulcan_amd import vk_types as T
-
-
-def cloud(n, seed, centre=(0.3, -0.2, 1.0), sigma=0.05):
-    rng = np.random.default_rng(seed)
-    return (rng.normal(0.0, sigma, size=(n, 3)) + np.asarray(centre)).astype(np.float32)
 
 
 def test_defaults_match_reference_constructor():
