@@ -1394,6 +1394,59 @@ VK_API size_t vk_volume_merge_posed_workspace_bytes(int32_t src_main, int32_t sr
 VK_API int vk_volume_merge_posed(const vk_volume* dst, const vk_volume* src, const vk_merge_pose_params* p,
     int32_t* counts_dev /* [8] */, void* workspace, void* stream);
 
+/* ------------------------------------------- merge through a pose and a change of scale -- */
+
+typedef struct vk_merge_resample_params {
+  vk_merge_params merge;      /* flags, max_rounds, the two caps: as vk_volume_merge */
+  vk_transform    pose;       /* T_dst_src, metres; m and inv both used as given */
+  int32_t         supersample;/* n in 1..4: n^3 sample points per dst voxel */
+  int32_t         reserved;   /* 0 */
+} vk_merge_resample_params;
+
+/* Fuse volume `src` into volume `dst` through a rigid pose when the two differ in voxel length, in truncation length or
+ * in both: vk_volume_merge_posed with a change of scale. A coarser destination takes the mean of n^3 sample points per
+ * voxel (a box filter against aliasing), and the stored distances, which are in truncation lengths, are carried into the
+ * destination's. No upstream counterpart; ref: as vk_volume_merge_posed, and src/depth_integrator.cu for the band a
+ * stored distance lies in ((-1, 1]: the integrator never writes behind the band). The definition is this comment: it is
+ * vk_volume_merge_posed's with the changes below, and at bitwise equal lengths with supersample == 1 it is that
+ * definition word for word. tests/merge_resample_reference.py states it on the CPU and the device is held to it bit for
+ * bit. All arithmetic is fp32, one rounding per operation, no contraction, IEEE division.
+ * PRECONDITIONS and host checks: vk_volume_merge_posed's, except that the lengths may differ. r_fwd = src->voxel_length /
+ * dst->voxel_length and r_back = dst->voxel_length / src->voxel_length (one division each) both lie in [0.25, 4];
+ * k = src->truncation_length / dst->truncation_length is finite and > 0; supersample is in 1..4; reserved == 0. Anything
+ * else is VK_ERR_ARGUMENT with no device touched.
+ * (coordinates) each volume's own voxel units. fwd(c)_a = ((fm[a][0] c_0 + fm[a][1] c_1) + fm[a][2] c_2) + tm_a with
+ * fm[a][j] = m[4j+a] * r_fwd and tm_a = m[12+a] / dst->voxel_length; back(c) the same with inv, r_back and
+ * inv[12+a] / src->voxel_length. (x * 1.0f == x: at r == 1.0f these are vk_volume_merge_posed's.)
+ * (sample points) a dst voxel with centre c has n^3 points p = c + (o_jx, o_jy, o_jz), jx fastest, then jy, then jz,
+ * o_j = (float)(2j+1) / (float)(2n) - 0.5f; n == 1 gives o == 0.0f and p == c bitwise.
+ * (source blocks) vk_volume_merge's, SKIP_UNOBSERVED included.
+ * (candidates) the box [lo, hi]^3 of a considered source block from its eight corners through fwd as
+ * vk_volume_merge_posed defines it, hi_a capped at lo_a + K - 1 with K = min(8, (int)(r_fwd * 1.7320508f) + 2): a block
+ * of 8 r_fwd voxels spans no more along an axis than its diagonal (3 at ratio 1). A block B of the box with every
+ * coordinate in the int16 range is a candidate of o iff one of its voxels has a sample point p whose cell =
+ * floorf(back(p)) has 8 o_a <= cell_a <= 8 o_a + 7 on all three axes.
+ * (allocation) vk_volume_merge's rounds with the candidates in the place of the source blocks, unchanged.
+ * (a sub-sample) vk_volume_merge_posed's trilinear sample at back(p) for a sample point p: g_a = back(p)_a - 0.5f, the
+ * USED lattice points, the lerps along x, then y, then z, the weight the smallest over the USED points; distance and
+ * colour apart. When k != 1.0f (bitwise) the distance sub-sample goes on: for k < 1 it does not exist if the stored
+ * distance of a USED point is >= 1.0f (a saturated value says "at least one source truncation length away", which
+ * cannot be said in the destination's units); else d' = k * d; d' >= 1 becomes 1.0f; d' <= -1 makes the sub-sample not
+ * exist (nothing is stored behind the band). Colour is not rescaled.
+ * (a voxel's sample) per field it exists iff more than half of the n^3 sub-samples exist, 2 * count > n^3; its value is
+ * the sum of those sub-samples in point order — the first, then + the next, ... — divided by (float)count, per channel
+ * for colour; its weight is the smallest of their weights. It continues the voxel's running average as
+ * vk_volume_merge does with a source voxel of that value and weight, the caps included; a field without a sample keeps
+ * its bytes. One wave writes a dst block; no atomic touches a voxel.
+ * (CONTINUE), (afterwards) and the eight counts: vk_volume_merge_posed's; counts[7] counts the voxels that took a
+ * distance sample. A CONTINUE call takes the previous call's workspace for this pair, pose and supersample.
+ * workspace: device, vk_volume_merge_resampled_workspace_bytes(..., K) bytes with the K above (0 for sizes that are not a
+ * volume's or a K outside 2..8), need not be initialised (a CONTINUE call's excepted). */
+VK_API size_t vk_volume_merge_resampled_workspace_bytes(int32_t src_main, int32_t src_excess,
+    int32_t dst_main, int32_t dst_excess, int32_t box_blocks_per_axis);
+VK_API int vk_volume_merge_resampled(const vk_volume* dst, const vk_volume* src, const vk_merge_resample_params* p,
+    int32_t* counts_dev /* [8] */, void* workspace, void* stream);
+
 /* --------------------------------------------------------------- pack the blocks -- */
 
 typedef struct vk_block_pack {

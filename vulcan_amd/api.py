@@ -123,6 +123,8 @@ _SIGNATURES = {
     "vk_volume_merge": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_volume_merge_posed_workspace_bytes": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32], _SZ),
     "vk_volume_merge_posed": ([_P, _P, _P, _P, _P, _P], _I),
+    "vk_volume_merge_resampled_workspace_bytes": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32], _SZ),
+    "vk_volume_merge_resampled": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_volume_pack_workspace_bytes": ([C.c_int32, C.c_int32], _SZ),
     "vk_volume_pack": ([_P, _P, _P, _P, _P, _P], _I),
     "vk_volume_merge_packed_workspace_bytes": ([C.c_int32], _SZ),
@@ -771,6 +773,66 @@ class Volume:
         check(lib().vk_volume_merge_posed(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(counts), _ptr(workspace),
                                           stream()), "vk_volume_merge_posed")
         return _ints(counts)
+
+    def _resample_ratios(self, other):
+        """(r_fwd, r_back, K) of vk_volume_merge_resampled(self <- other): the two ratios of the voxel lengths as the library
+        takes them, one float32 division each, and the blocks per axis of a source block's box that sizes the workspace"""
+        mine, theirs = np.float32(self.voxel_length), np.float32(other.voxel_length)
+        r_fwd, r_back = theirs / mine, mine / theirs
+        if not (0.25 <= r_fwd <= 4.0 and 0.25 <= r_back <= 4.0):
+            raise VkError(f"merge_resampled: voxel lengths {other.voxel_length} and {self.voxel_length} are more than a factor of "
+                          "4 apart; chain two calls")
+        return float(r_fwd), float(r_back), min(8, int(r_fwd * np.float32(1.7320508)) + 2)
+
+    def _merge_resampled_call(self, other, pose, supersample, flags, max_rounds, max_distance_weight, max_color_weight):
+        """one vk_volume_merge_resampled(self <- other through `pose`, a T.Transform): the eight counts from one blocking read"""
+        self._no_requests_pending("merge_resampled")
+        other._no_requests_pending("merge_resampled")
+        box = self._resample_ratios(other)[2]
+        workspace, counts = self._workspace("merge_resampled", (other.main, other.excess, self.main, self.excess, box),
+                                            lib().vk_volume_merge_resampled_workspace_bytes, 8, flags)
+        params = T.MergeResampleParams(T.MergeParams(int(flags), int(max_rounds), float(max_distance_weight), float(max_color_weight)),
+                                       pose, int(supersample), 0)
+        self._table_changes()
+        check(lib().vk_volume_merge_resampled(_ref(self.desc()), _ref(other.desc()), _ref(params), _ptr(counts), _ptr(workspace),
+                                              stream()), "vk_volume_merge_resampled")
+        return _ints(counts)
+
+    def merge_resampled(self, other, pose=None, supersample=None, max_distance_weight=16, max_color_weight=16, skip_unobserved=False,
+                        max_rounds=8):
+        """vk_volume_merge_resampled (not upstream): merge(other, pose=...) for a volume `other` of another voxel length (up to
+        a factor of 4 either way), another truncation length, or both. Every voxel of the blocks of this volume that
+        `other`'s blocks reach takes the mean of `supersample`^3 trilinear samples of `other` spread over the voxel — a
+        box filter, so a coarser copy does not alias; None: as many per axis as voxels of `other` lie along one of
+        this volume's, min(4, max(1, ceil(ratio))) — and a stored distance is carried from `other`'s truncation length
+        into this volume's: values beyond this volume's band saturate at 1 or, behind the surface, are left out.
+        `pose` (a 4x4 array or a Transform, T_self_other in metres; None: the identity). Everything else — the rounds, the
+        call that continues, what is refused and when, the eight counts — is merge(other, pose=...)'s. A PackedVolume
+        has no table to sample: TypeError."""
+        if isinstance(other, PackedVolume):
+            raise TypeError("merge_resampled: a PackedVolume has no table to sample; load it into a Volume first")
+        flags = T.VK_MERGE_SKIP_UNOBSERVED if skip_unobserved else 0
+        pose = _as_pose(pose, identity=True)
+        if supersample is None:
+            supersample = min(4, max(1, int(np.ceil(self._resample_ratios(other)[1] - 1e-6))))
+        # (considered, candidates, fused, allocated, left out, rounds, skipped, sampled)
+        return self._merge_rounds(lambda go_on: self._merge_resampled_call(other, pose, supersample, flags | go_on, max_rounds,
+                                                                           max_distance_weight, max_color_weight),
+                                  max_rounds, 4, 5, (2, 3, 5, 7))
+
+    def resampled(self, voxel_length, truncation_length, main_block_count, excess_block_count, pose=None, supersample=None,
+                  depth_range=(0.1, 5.0), max_rounds=8):
+        """This map at another resolution: a fresh Volume of the given voxel length, truncation length and table sizes on
+        this volume's device, and merge_resampled(self) into it with both caps 32767, which into empty blocks keeps
+        the sampled weights (as Volume.load is built). `pose`: T_new_self. Raises when the blocks do not fit the sizes."""
+        volume = Volume(main_block_count, excess_block_count, voxel_length=voxel_length, truncation_length=truncation_length,
+                        depth_range=depth_range, device=self.device)
+        counts = volume.merge_resampled(self, pose=pose, supersample=supersample, max_distance_weight=32767,
+                                        max_color_weight=32767, max_rounds=max_rounds)
+        if counts[4]:
+            raise VkError(f"Volume.resampled: {counts[4]} of {counts[1]} blocks did not fit ({main_block_count} main, "
+                          f"{excess_block_count} excess entries)")
+        return volume
 
     def _merge_packed_call(self, pack, flags, max_rounds, max_distance_weight, max_color_weight):
         """one vk_volume_merge_packed(self <- pack): the six counts from one blocking read"""

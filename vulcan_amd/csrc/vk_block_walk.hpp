@@ -6,7 +6,7 @@
 //   find_block, mark_chain                  the chain walk that finds a block; the one that lists a bucket's blocks
 //   Ray, load_ray, finite3, cell_of, kFar   a ray in the volume's frame, and the cell of a point
 //   Lattice, lattice_at, lattice_of         the lattice cell a carried point falls into
-//   fill_directory                          the 4x4x4 blocks under one carried block, as slots in LDS
+//   fill_directory, fill_directory_cells    the 4x4x4 blocks under one carried block, or side^3 from a given block, as slots in LDS
 //   trilinear, trilinear_gradient           the value and gradient over a cell's eight values
 //   Cell, read_cell, store_sample, store_gradient   the cell of a point read from the pool as vk_volume_sample defines it
 //   volume_ok, volumes_match                the host's checks of a volume and of a pair
@@ -187,6 +187,23 @@ __device__ __forceinline__ Lattice lattice_of(const float* rows, int ox, int oy,
 constexpr int kFootprint = 4;                  // blocks per axis under one block carried through a rigid pose
 static_assert(kFootprint * kFootprint * kFootprint == kWave, "one lane per directory cell");
 
+// One wave: the slots (-1: absent) of the side^3 blocks of `v` from block (least_x, least_y, least_z) into the wave's LDS
+// `directory`, cell (rx, ry, rz) at rx + side ry + side^2 rz. The lanes stride over the cells, one chain walk per cell.
+__device__ __forceinline__ void fill_directory_cells(const vk_volume& v, int total, int least_x, int least_y, int least_z, int side,
+    int* directory)
+{
+  const int cells = side * side * side;
+  for (int cell = lane_id(); cell < cells; cell += kWave)
+  {
+    const int sx = least_x + cell % side, sy = least_y + (cell / side) % side, sz = least_z + cell / (side * side);
+    int slot = -1;
+    Entry main_entry;
+    if (in_int16(sx, sy, sz)) find_block(v, total, sx, sy, sz, slot, main_entry);
+    directory[cell] = slot;
+  }
+  wave_lds_fence();
+}
+
 // One wave, eight voxels per lane (lane = 8 y + x). Under a rigid pose the lattice points of the 512 samples of block `mine`
 // carried through `rows` lie in at most 4^3 blocks of `v` from the least one: lane k walks the chain of cell k once and
 // leaves the slot (-1: absent) in the wave's 64-word LDS `directory`, cell (rx, ry, rz) at rx + 4 ry + 16 rz.
@@ -206,12 +223,7 @@ __device__ __forceinline__ void fill_directory(const vk_volume& v, int total, co
   least_x = wave_min(least_x);
   least_y = wave_min(least_y);
   least_z = wave_min(least_z);
-  const int sx = least_x + (lane & 3), sy = least_y + ((lane >> 2) & 3), sz = least_z + (lane >> 4);
-  int slot = -1;
-  Entry main_entry;
-  if (in_int16(sx, sy, sz)) find_block(v, total, sx, sy, sz, slot, main_entry);
-  directory[lane] = slot;
-  wave_lds_fence();
+  fill_directory_cells(v, total, least_x, least_y, least_z, kFootprint, directory);
 }
 
 // the value, vk_volume_merge_posed's spelling: an axis with f == 0 takes its base value

@@ -365,6 +365,14 @@ class Volume
     // blocks reach takes a trilinear sample of `other` at its own centre carried back; a reached block no sample falls into
     // stays allocated and empty (ReleaseBlocks with `unobserved` gives those back). Otherwise as Merge(other).
     MergePoseCounts Merge(const Volume& other, const Transform& Tdst_src, const MergeOptions& options = MergeOptions());
+    // ... when `other` has another voxel length (up to a factor of 4 either way), another truncation length, or both
+    // (vk_volume_merge_resampled). Every voxel takes the mean of supersample^3 (1 .. 4 per axis) trilinear samples of
+    // `other` spread over the voxel — a box filter, so a coarser copy does not alias; 0: as many per axis as voxels of
+    // `other` lie along one of this volume's — and a stored distance is carried from `other`'s truncation length into this
+    // volume's: beyond this volume's band it saturates at 1 or, behind the surface, is left out. At equal lengths with
+    // supersample 1 this is Merge(other, Tdst_src), byte for byte. Otherwise as Merge(other, Tdst_src).
+    MergePoseCounts MergeResampled(const Volume& other, const Transform& Tdst_src, int supersample = 0,
+        const MergeOptions& options = MergeOptions());
     // Not upstream: refine that pose from the two volumes themselves (vk_volume_register) — Gauss-Newton on the TSDFs,
     // every voxel of `other` within `max_abs_distance` truncation lengths of the surface against the trilinear sample of
     // this volume where `start` (then the refined pose) carries it. `start` has to bring the two surfaces within roughly
@@ -521,6 +529,8 @@ class Volume
     mutable Buffer<int> pack_counts_;
     Buffer<unsigned char> merge_pose_workspace_;   // Merge through a pose: again for another pair of sizes
     Buffer<int> merge_pose_counts_;
+    Buffer<unsigned char> merge_resample_workspace_;   // MergeResampled: again for another pair of sizes or another ratio
+    Buffer<int> merge_resample_counts_;
     // a registration's device buffers, and what is done with them before and after the loop
     struct RegistrationBuffers
     {

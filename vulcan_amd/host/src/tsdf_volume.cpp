@@ -524,6 +524,37 @@ MergePoseCounts Volume::Merge(const Volume& other, const Transform& Tdst_src, co
   return out;
 }
 
+MergePoseCounts Volume::MergeResampled(const Volume& other, const Transform& Tdst_src, int supersample, const MergeOptions& options)
+{
+  // the two ratios as the library takes them: one division each
+  const float r_fwd = other.voxel_length_ / voxel_length_, r_back = voxel_length_ / other.voxel_length_;
+  VULCAN_ASSERT_MSG(r_fwd >= 0.25f && r_fwd <= 4.0f && r_back >= 0.25f && r_back <= 4.0f,
+      "the voxel lengths are more than a factor of 4 apart: chain two calls");
+  VULCAN_ASSERT_MSG(supersample >= 0 && supersample <= 4, "1 .. 4 sample points per axis, or 0 for the ratio's");
+  if (supersample == 0) supersample = std::min(4, std::max(1, int(std::ceil(double(r_back) - 1e-6))));
+  const int box = std::min(8, int(r_fwd * 1.7320508f) + 2);           // K of vk.h: sizes the workspace
+  vk_merge_resample_params p;
+  p.merge = ToVkMergeParams(options);
+  p.pose = Tdst_src.ToVk();                       // the matrix and its inverse, from the one Transform
+  p.supersample = supersample;
+  p.reserved = 0;
+  int32_t counts[8];
+  MergeRounds(&other, p.merge, merge_resample_workspace_, vk_volume_merge_resampled_workspace_bytes(other.main_block_count_,
+      other.excess_block_count_, main_block_count_, excess_block_count_, box), merge_resample_counts_, 8, counts,
+      [&p](const vk_volume* dst, const vk_volume* src, int32_t* counts_dev, void* workspace)
+      { return vk_volume_merge_resampled(dst, src, &p, counts_dev, workspace, Device::GetStream()); });
+  MergePoseCounts out;
+  out.considered = counts[0];
+  out.candidates = counts[1];
+  out.fused = counts[2];
+  out.allocated = counts[3];
+  out.left_out = counts[4];
+  out.rounds = counts[5];
+  out.skipped = counts[6];
+  out.sampled = counts[7];
+  return out;
+}
+
 // ---- PackedVolume: a volume's blocks, compact (vk_block_pack) ----
 
 static const char kMapMagic[8] = {'V', 'U', 'L', 'C', 'A', 'N', 'M', 'P'};

@@ -231,6 +231,12 @@ class MergePoseParams(C.Structure):
     _fields_ = [("merge", MergeParams), ("pose", Transform)]
 
 
+class MergeResampleParams(C.Structure):
+    """vk_merge_resample_params (vk.h): vk_merge_params, the pose T_dst_src, and the n of the n^3 sample points per voxel
+    that vk_volume_merge_resampled takes between volumes of different voxel or truncation length"""
+    _fields_ = [("merge", MergeParams), ("pose", Transform), ("supersample", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RegisterParams(C.Structure):
     """vk_register_params (vk.h): how vk_volume_register aligns one volume to another; the band is in truncation lengths"""
     _fields_ = [("flags", C.c_int32), ("iterations", C.c_int32), ("max_abs_distance", C.c_float), ("pad", C.c_int32)]
