@@ -2028,6 +2028,81 @@ VK_API int vk_volume_score_poses(const vk_volume* v, const float* rays, const fl
 VK_API int vk_volume_score_poses_best(const vk_pose_score* scores_dev, const vk_transform* poses_dev, int32_t pose_count,
     const vk_score_poses_params* p, int32_t* best_dev, vk_transform* pose_out_dev, void* stream);
 
+/* ---------------------------------------------------------- clearance field -- */
+
+enum { VK_CELL_UNKNOWN = 1, VK_CELL_FREE = 2, VK_CELL_OCCUPIED = 4 };
+enum { VK_FIELD_SIGNED = 1 };
+#define VK_FIELD_BEYOND INT32_MAX   /* d2 of a cell with no site within max_cells */
+
+typedef struct vk_cell_grid {
+  int32_t origin[3];         /* lattice coordinates of the grid's first voxel, each a multiple of stride, |origin| <= 2^20 */
+  int32_t dims[3];           /* cells per axis, 1 .. 1024 each, nx * ny * nz <= 2^27 */
+  int32_t stride;            /* voxels per cell and axis: 1, 2, 4 or 8 */
+  int32_t pad;
+} vk_cell_grid;              /* 32 bytes */
+
+typedef struct vk_distance_field_params {
+  int32_t flags;             /* 0 or VK_FIELD_SIGNED; an unknown bit is VK_ERR_ARGUMENT */
+  int32_t site_mask;         /* 1 .. 7: VK_CELL_* or'ed, the classes a distance is measured to */
+  int32_t max_cells;         /* 1 .. 256: the cap of the search, in cells */
+  float   occupied_below;    /* finite, in [-1, 1], truncation lengths; 0: the zero crossing */
+} vk_distance_field_params;  /* 16 bytes */
+
+/* How far is a place from the nearest surface: the hashed volume classified into a dense grid of cells, and the exact
+ * Euclidean distance transform of that grid. The stored distance saturates at one truncation length; a planner needs metres
+ * of clearance, densely, over a box. No upstream counterpart (the reference never leaves its truncation band; ref:
+ * src/volume.cu:168-191 for the chain walk). The definition is this comment; tests/distance_field_reference.py states it on
+ * the CPU and the device is held to it bit for bit: the classes and the squared distances are integers, and the float field is
+ * fp32 with one rounding per operation, a correctly rounded square root and no contraction.
+ * ACCESS: the volume is only read: the calls are allowed while a frame is announced, like vk_volume_sample. No atomic and
+ * no wait on another workgroup; a chain walk is bounded by the table, everything else by dims and max_cells: they cannot
+ * hang a device. Nothing is read back. Every call initialises what it reads of the workspace, and writes only the arrays
+ * it was given, elements [0, nx*ny*nz) of each.
+ * (grid) cell (i, j, k), 0 <= i < dims[0], 0 <= j < dims[1], 0 <= k < dims[2], covers the stride^3 voxels
+ * n_a = origin_a + stride * idx_a + e_a, 0 <= e_a < stride, in lattice coordinates as vk_volume_sample numbers them: n is
+ * voxel (n mod 8) — index z*64 + y*8 + x — of block floor(n / 8), found by the chain walk; the block is absent when a
+ * coordinate leaves the int16 range. As every origin_a is a multiple of stride, a cell lies in one block. Arrays are indexed
+ * (k * ny + j) * nx + i, x fastest.
+ * (class of a cell, one uint8_t) a voxel is OBSERVED iff its block is present and distance_weight != 0; it is OCCUPIED iff it
+ * is observed and distance <= occupied_below (an fp32 compare of the stored value; a NaN is not occupied). A cell is
+ * VK_CELL_OCCUPIED iff one of its voxels is occupied, else VK_CELL_FREE iff one of its voxels is observed, else
+ * VK_CELL_UNKNOWN. This map allocates blocks only inside the truncation band: open space in front of the band has no blocks
+ * and reads UNKNOWN, not FREE (vk_volume_carve_rays observes it). The clearance field, whose sites are the occupied cells,
+ * does not depend on that.
+ * (transform) a cell is a SITE iff class & site_mask != 0. d2(p) is the minimum of |p - q|^2 over the sites q of the grid,
+ * in cells, an integer; it is VK_FIELD_BEYOND where the grid has no site or where that minimum exceeds max_cells^2. Cells
+ * outside the grid do not exist. (Three separable passes along x, y and z that search only offsets within max_cells and drop
+ * what exceeds max_cells^2 give exactly this: a nearest site within the cap is within the cap on every axis.)
+ * (float field) distance = (sqrtf((float)d2) * (float)stride) * voxel_length, +INFINITY where d2 is VK_FIELD_BEYOND;
+ * (float)d2 is exact, d2 <= 65536. With VK_FIELD_SIGNED a site cell takes -((sqrtf((float)e2) * (float)stride) * voxel_length)
+ * instead, e2 being the same transform with the complement mask 7 ^ site_mask, and -INFINITY where e2 is VK_FIELD_BEYOND
+ * (e2 >= 1 at a site). d2 is the unsigned transform's in either case.
+ * HOST CHECKS (VK_ERR_ARGUMENT, no device touched): a null pointer that is not optional, a volume that vk_volume_sample would
+ * refuse, a stride other than 1, 2, 4 or 8, an origin that is not a multiple of the stride or beyond +-2^20, a dim outside
+ * 1 .. 1024 or more than 2^27 cells, site_mask outside 1 .. 7, max_cells outside 1 .. 256, an unknown flag, occupied_below
+ * not finite or outside [-1, 1], d2 or distance not 4-byte aligned, a workspace not 16-byte aligned.
+ * vk_volume_classify_cells: one fill of the grid with UNKNOWN, then one wave per table entry whose block meets the grid
+ * reduces the block's stride^3 groups and stores that block's cells; a cell has one owner block, so no atomic and no order.
+ * vk_grid_distance_transform: classes -> d2, three launches. workspace: vk_grid_distance_transform_workspace_bytes(dims)
+ * bytes (0 for dims outside the limits), need not be initialised.
+ * vk_volume_distance_field: the two calls and the conversion in one enqueue. classes and d2 are optional outputs and are
+ * exactly what the two separate calls write; with d2 == NULL the last pass writes the floats and no int32 grid reaches
+ * memory but the passes' own intermediate. workspace: vk_volume_distance_field_workspace_bytes(grid, p) bytes (0 for a grid
+ * or parameters the call would refuse), need not be initialised. */
+VK_API int vk_volume_classify_cells(const vk_volume* v, const vk_cell_grid* grid, float occupied_below,
+    uint8_t* classes /* device [nx*ny*nz] */, void* stream);
+/* ref: none (no upstream counterpart: the reference has no dense grid). The bytes of the workspace for a grid of these dims. */
+VK_API size_t vk_grid_distance_transform_workspace_bytes(const int32_t dims[3]);
+/* ref: none (no upstream counterpart). classes: device uint8 [nx*ny*nz]; d2: device int32 [nx*ny*nz], 4-byte aligned. */
+VK_API int vk_grid_distance_transform(const uint8_t* classes, const int32_t dims[3], int32_t site_mask, int32_t max_cells,
+    int32_t* d2, void* workspace, void* stream);
+/* ref: none (no upstream counterpart). The same bytes as vk_grid_distance_transform_workspace_bytes(grid->dims). */
+VK_API size_t vk_volume_distance_field_workspace_bytes(const vk_cell_grid* grid, const vk_distance_field_params* p);
+/* ref: src/volume.cu:168-191 (the chain walk that finds a cell's block; no upstream counterpart). classes (optional) and
+ * distance: device [nx*ny*nz]; d2 (optional): device int32 [nx*ny*nz]; d2 and distance 4-byte aligned. */
+VK_API int vk_volume_distance_field(const vk_volume* v, const vk_cell_grid* grid, const vk_distance_field_params* p,
+    uint8_t* classes, int32_t* d2, float* distance, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

@@ -150,6 +150,11 @@ _SIGNATURES = {
     "vk_volume_score_poses_workspace_bytes": ([C.c_int32, C.c_int32], C.c_size_t),
     "vk_volume_score_poses": ([_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_volume_score_poses_best": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
+    "vk_volume_classify_cells": ([_P, _P, _F, _P, _P], _I),
+    "vk_grid_distance_transform_workspace_bytes": ([_P], C.c_size_t),
+    "vk_grid_distance_transform": ([_P, _P, C.c_int32, C.c_int32, _P, _P, _P], _I),
+    "vk_volume_distance_field_workspace_bytes": ([_P, _P], C.c_size_t),
+    "vk_volume_distance_field": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
     "vk_detect_workspace_bytes": ([C.c_int32], _SZ),
     "vk_detect_filter": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
     "vk_detect": ([_P, _P, C.c_int32, _P, _P, _P, _P], _I),
@@ -500,6 +505,62 @@ class RayHits:
         self.samples, self.gradients = at.samples, at.gradients
         self.distance, self.distance_weight, self.color, self.color_weight = at.distance, at.distance_weight, at.color, at.color_weight
         self.gradient, self.gradient_valid = at.gradient, at.gradient_valid
+
+
+CELL_UNKNOWN, CELL_FREE, CELL_OCCUPIED = T.CELL_UNKNOWN, T.CELL_FREE, T.CELL_OCCUPIED
+
+
+class DistanceField:
+    """what Volume.distance_field returns: the device tensors vk_volume_distance_field wrote, each [nz, ny, nx] over the
+    grid of `origin` (lattice coordinates of the first voxel), `stride` voxels per cell and `cell_length` metres per cell.
+    `classes` uint8 (CELL_UNKNOWN, CELL_FREE, CELL_OCCUPIED); `distance` float32, metres to the nearest site cell, +inf
+    beyond the cap (with `signed`: negative on site cells); `squared_cells` int32, the squared distance in cells and
+    VK_FIELD_BEYOND beyond the cap, or None when it was not asked for."""
+
+    def __init__(self, classes, distance, squared_cells, origin, stride, cell_length):
+        self.classes, self.distance, self.squared_cells = classes, distance, squared_cells
+        self.origin, self.stride, self.cell_length = tuple(int(o) for o in origin), int(stride), float(cell_length)
+
+
+def grid_for_box(lo, hi, stride, voxel_length):
+    """(origin, dims) of the smallest grid of `stride`-voxel cells, aligned to the stride, that covers the metric box
+    [lo, hi] of a volume of this voxel length: host arithmetic, in float64"""
+    stride = int(stride)
+    first = np.floor(np.asarray(lo, dtype=np.float64) / voxel_length / stride).astype(np.int64)
+    last = np.floor(np.asarray(hi, dtype=np.float64) / voxel_length / stride).astype(np.int64)
+    if np.any(last < first):
+        raise VkError("grid_for_box: hi lies below lo")
+    return tuple(int(f) * stride for f in first), tuple(int(n) for n in last - first + 1)
+
+
+def _grid_workspace_bytes(nx, ny, nz):
+    return lib().vk_grid_distance_transform_workspace_bytes((C.c_int32 * 3)(nx, ny, nz))
+
+
+def _grid_shape(dims):
+    """[nz, ny, nx] of a grid of dims = (nx, ny, nz) cells that the library takes; VkError for any other"""
+    nx, ny, nz = (int(d) for d in dims)
+    if not (all(1 <= n <= 1024 for n in (nx, ny, nz)) and _grid_workspace_bytes(nx, ny, nz)):
+        raise VkError(f"a grid has 1 .. 1024 cells per axis and at most 2^27 in all, not {(nx, ny, nz)}")
+    return nz, ny, nx
+
+
+def distance_transform(classes, site_mask=T.CELL_OCCUPIED, max_cells=256):
+    """vk_grid_distance_transform (not upstream): the exact squared Euclidean distance, in cells, from every cell of the
+    uint8 [nz, ny, nx] device tensor `classes` to the nearest cell with class & site_mask != 0, as an int32 tensor of that
+    shape; VK_FIELD_BEYOND where there is none within `max_cells`. With other masks: the distance to unobserved space, or
+    the depth inside an obstacle. Three launches, nothing is read back."""
+    import torch
+    if not (hasattr(classes, "data_ptr") and classes.dtype == torch.uint8 and classes.dim() == 3):
+        raise VkError("distance_transform: classes is a uint8 [nz, ny, nx] device tensor")
+    classes = classes.contiguous()
+    nz, ny, nx = (int(n) for n in classes.shape)
+    dims = (C.c_int32 * 3)(nx, ny, nz)
+    workspace = _dev_bytes(_grid_workspace_bytes(nx, ny, nz), classes.device)
+    d2 = torch.empty((nz, ny, nx), dtype=torch.int32, device=classes.device)
+    check(lib().vk_grid_distance_transform(_ptr(classes), dims, int(site_mask), int(max_cells), _ptr(d2), _ptr(workspace), stream()),
+          "vk_grid_distance_transform")
+    return d2
 
 
 class PackedVolume:
@@ -1045,6 +1106,49 @@ class Volume:
         flags = (T.VK_SAMPLE_VOXEL_UNITS if voxel_units else 0) | (0 if color else T.VK_SAMPLE_DISTANCE_ONLY)
         samples, gradients = self._sample_call(points, _as_pose(pose, device=True), flags, True, bool(gradient), points.shape[0])
         return Samples(samples, gradients, bool(color), self.truncation_length)
+
+    def grid_for_box(self, lo, hi, stride=1):
+        """(origin, dims) of the smallest aligned grid of `stride`-voxel cells that covers the metric box [lo, hi]"""
+        return grid_for_box(lo, hi, stride, self.voxel_length)
+
+    def classify_cells(self, origin, dims, stride=1, occupied_below=0.0):
+        """vk_volume_classify_cells (not upstream): the grid of dims = (nx, ny, nz) cells of `stride`^3 voxels from the voxel
+        `origin` (lattice coordinates, multiples of the stride) as a uint8 [nz, ny, nx] device tensor of CELL_UNKNOWN,
+        CELL_FREE and CELL_OCCUPIED: a cell is occupied where an observed voxel stores a distance <= `occupied_below`
+        (truncation lengths), else free where a voxel is observed. Blocks exist only in the truncation band: open space
+        in front of it reads CELL_UNKNOWN. The volume is only read; two launches, nothing is read back."""
+        import torch
+        grid = T.CellGrid.make(origin, dims, stride)
+        classes = torch.empty(_grid_shape(dims), dtype=torch.uint8, device=self.device)
+        check(lib().vk_volume_classify_cells(_ref(self.desc()), _ref(grid), float(occupied_below), _ptr(classes), stream()),
+              "vk_volume_classify_cells")
+        return classes
+
+    def distance_field(self, origin, dims, stride=1, max_distance=None, max_cells=None, occupied_below=0.0, sites=CELL_OCCUPIED,
+                       signed=False, squared=False):
+        """vk_volume_distance_field (not upstream): how far every cell of a dense grid is from the nearest surface — the
+        clearance a planner asks for, which the stored distance cannot give beyond one truncation length. The grid is
+        classify_cells' (`origin`, `dims`, `stride`, `occupied_below`); a cell is a site where its class & `sites` != 0, and
+        every cell takes the exact Euclidean distance to the nearest site cell, centre to centre, in metres, +inf where
+        none lies within the cap: `max_cells` cells (1 .. 256), or `max_distance` metres, rounded up to whole cells and
+        clamped to 256 (neither: 256). `signed`: a site cell takes minus its distance to the nearest cell that is no site.
+        `squared`: also the squared distance in cells as int32. The volume is only read; one enqueue, nothing is read back.
+        Returns a DistanceField."""
+        import torch
+        stride = int(stride)
+        cell_length = float(np.float32(np.float32(stride) * np.float32(self.voxel_length)))
+        if max_cells is None:
+            max_cells = 256 if max_distance is None else min(256, max(1, int(np.ceil(float(max_distance) / cell_length))))
+        grid = T.CellGrid.make(origin, dims, stride)
+        shape = _grid_shape(dims)
+        workspace, _ = self._workspace("distance_field", shape[::-1], _grid_workspace_bytes, 1)
+        classes = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        distance = torch.empty(shape, dtype=torch.float32, device=self.device)
+        d2 = torch.empty(shape, dtype=torch.int32, device=self.device) if squared else None
+        params = T.DistanceFieldParams(T.VK_FIELD_SIGNED if signed else 0, int(sites), int(max_cells), float(occupied_below))
+        check(lib().vk_volume_distance_field(_ref(self.desc()), _ref(grid), _ref(params), _ptr(classes), _ptr(d2), _ptr(distance),
+                                             _ptr(workspace), stream()), "vk_volume_distance_field")
+        return DistanceField(classes, distance, d2, origin, stride, cell_length)
 
     def _cast_call(self, rays, pose=None, flags=0, t_min=0.0, t_max=5.0, max_steps=500, samples=True, gradients=True, count=None,
                    out=None):

@@ -151,6 +151,35 @@ struct SampleOptions
   bool distance_only = false;   // the colour fields of a sample stay 0 and no colour is read
 };
 
+// Not upstream: a dense grid of cells over the volume's lattice (vk_cell_grid): cell (i, j, k) covers the stride^3 voxels from
+// origin + stride * (i, j, k); arrays over it are indexed (k * ny + j) * nx + i
+struct CellGrid
+{
+  int origin[3] = {0, 0, 0};    // lattice coordinates of the first voxel, each a multiple of stride
+  int dims[3] = {1, 1, 1};      // cells per axis (nx, ny, nz): 1 .. 1024 each, 2^27 in all
+  int stride = 1;               // voxels per cell and axis: 1, 2, 4 or 8
+  size_t Cells() const { return size_t(dims[0]) * size_t(dims[1]) * size_t(dims[2]); }
+};
+
+// Not upstream: what Volume::DistanceField measures (vk_distance_field_params)
+struct DistanceFieldOptions
+{
+  int site_mask = VK_CELL_OCCUPIED;   // the classes a distance is measured to, VK_CELL_* or'ed
+  int max_cells = 256;                // the cap of the search, in cells (1 .. 256); beyond it the distance is +infinity
+  float occupied_below = 0.0f;        // an observed voxel is occupied where its stored distance is <= this, truncation lengths
+  bool is_signed = false;             // a site cell takes minus its distance to the nearest cell that is no site
+  bool squared = false;               // also the squared distance in cells (int32, VK_FIELD_BEYOND beyond the cap)
+};
+
+// Not upstream: the device buffers Volume::DistanceField and ClassifyCells fill, one element per cell: allocated by the first
+// call, again for a grid of another size
+struct DistanceFieldBuffers
+{
+  Buffer<unsigned char> classes;      // VK_CELL_UNKNOWN, VK_CELL_FREE or VK_CELL_OCCUPIED
+  Buffer<float> distance;             // metres to the nearest site cell
+  Buffer<int> squared_cells;          // with DistanceFieldOptions::squared
+};
+
 // Not upstream: how Volume::CastRays reads its rays, how far it marches and what it samples at a hit (vk_cast_params)
 struct CastOptions
 {
@@ -390,6 +419,16 @@ class Volume
     void Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, Vector4f* gradients_dev, const Transform* pose = nullptr,
         const SampleOptions& options = SampleOptions()) const;
 
+    // Not upstream: how far every cell of a dense grid is from the nearest surface (vk_volume_distance_field) — the
+    // clearance a planner asks for, which the stored distance cannot give beyond one truncation length. The grid is
+    // classified (unknown, free, occupied: ClassifyCells alone does that much) and every cell takes the exact Euclidean
+    // distance, centre to centre and in metres, to the nearest cell whose class is in options.site_mask; +infinity where
+    // none lies within options.max_cells. Blocks exist only inside the truncation band, so open space in front of it reads
+    // unknown. The volume is only read — like Sample both are allowed while a frame is announced — in one enqueue on
+    // Device::GetStream(); nothing is read back.
+    void DistanceField(const CellGrid& grid, const DistanceFieldOptions& options, DistanceFieldBuffers& buffers) const;
+    void ClassifyCells(const CellGrid& grid, float occupied_below, Buffer<unsigned char>& classes) const;
+
     // Not upstream: what each of `count` arbitrary rays hits first in the volume (vk_volume_cast_rays) — the raycast's
     // march along rays that are no pixels of a camera: a line of sight, a simulated range sensor, picking. Per ray the
     // outcome (VK_RAY_MISS, _HIT, _STEPS, _INVALID) in status_dev, the distance along the normalised direction in t_dev
@@ -547,6 +586,7 @@ class Volume
     Buffer<unsigned char> register_workspace_;     // Register: again for a source of another size
     RegistrationBuffers register_;
     mutable Buffer<float> sample_pose_;            // Sample, CastRays, IntegrateRays, CarveRays, ColorRays: the pose on the device (32)
+    mutable Buffer<unsigned char> field_workspace_;   // DistanceField: again for a grid of another size
     Buffer<unsigned char> rays_workspace_;         // IntegrateRays: allocated by the first call
     Buffer<int> rays_counts_;
     Buffer<unsigned char> carve_workspace_;        // CarveRays: allocated by the first call

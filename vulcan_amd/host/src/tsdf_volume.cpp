@@ -833,6 +833,48 @@ void Volume::Sample(const Vector3f* points_dev, int count, Voxel* samples_dev, V
       reinterpret_cast<float*>(gradients_dev), Device::GetStream()));
 }
 
+static vk_cell_grid ToVkGrid(const CellGrid& grid)
+{
+  vk_cell_grid g;
+  for (int a = 0; a < 3; ++a)
+  {
+    g.origin[a] = grid.origin[a];
+    g.dims[a] = grid.dims[a];
+  }
+  g.stride = grid.stride;
+  g.pad = 0;
+  return g;
+}
+
+void Volume::ClassifyCells(const CellGrid& grid, float occupied_below, Buffer<unsigned char>& classes) const
+{
+  const vk_cell_grid g = ToVkGrid(grid);
+  VULCAN_ASSERT_MSG(vk_grid_distance_transform_workspace_bytes(g.dims) != 0, "a grid has 1 .. 1024 cells per axis and at most 2^27");
+  if (classes.GetSize() != grid.Cells()) classes.Resize(grid.Cells());
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_classify_cells(&v, &g, occupied_below, classes.GetData(), Device::GetStream()));
+}
+
+void Volume::DistanceField(const CellGrid& grid, const DistanceFieldOptions& options, DistanceFieldBuffers& buffers) const
+{
+  const vk_cell_grid g = ToVkGrid(grid);
+  vk_distance_field_params p;
+  p.flags = options.is_signed ? VK_FIELD_SIGNED : 0;
+  p.site_mask = options.site_mask;
+  p.max_cells = options.max_cells;
+  p.occupied_below = options.occupied_below;
+  const size_t bytes = vk_volume_distance_field_workspace_bytes(&g, &p);
+  VULCAN_ASSERT_MSG(bytes != 0, "a grid or options that vk_volume_distance_field refuses");
+  const size_t cells = grid.Cells();
+  if (field_workspace_.GetSize() != bytes) field_workspace_.Resize(bytes);
+  if (buffers.classes.GetSize() != cells) buffers.classes.Resize(cells);
+  if (buffers.distance.GetSize() != cells) buffers.distance.Resize(cells);
+  if (options.squared && buffers.squared_cells.GetSize() != cells) buffers.squared_cells.Resize(cells);
+  const vk_volume v = ToVk();
+  VK_ASSERT(vk_volume_distance_field(&v, &g, &p, buffers.classes.GetData(), options.squared ? buffers.squared_cells.GetData() : nullptr,
+      buffers.distance.GetData(), field_workspace_.GetData(), Device::GetStream()));
+}
+
 void Volume::CastRays(const Ray* rays_dev, int count, float* t_dev, int* status_dev, Voxel* samples_dev, Vector4f* gradients_dev,
     const Transform* pose, const CastOptions& options) const
 {

@@ -300,6 +300,30 @@ pose_score_dtype = np.dtype([("measured", "<i4"), ("sampled", "<i4"), ("residual
 assert C.sizeof(ScorePosesParams) == 24 and C.sizeof(PoseScore) == 32 and pose_score_dtype.itemsize == 32
 
 
+# vk_volume_distance_field (vk.h): the class of a cell, the flag of the signed field, d2 where no site is within reach
+CELL_UNKNOWN, CELL_FREE, CELL_OCCUPIED = 1, 2, 4
+VK_FIELD_SIGNED = 1
+VK_FIELD_BEYOND = 2147483647
+
+
+class CellGrid(C.Structure):
+    """vk_cell_grid (vk.h): a dense grid of cells over the lattice — the first voxel, the cells per axis, voxels per cell"""
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("stride", C.c_int32), ("pad", C.c_int32)]
+
+    @staticmethod
+    def make(origin, dims, stride=1):
+        return CellGrid((C.c_int32 * 3)(*(int(o) for o in origin)), (C.c_int32 * 3)(*(int(d) for d in dims)), int(stride), 0)
+
+
+class DistanceFieldParams(C.Structure):
+    """vk_distance_field_params (vk.h): whether site cells take a negative distance, the classes a distance is measured to,
+    the cap of the search in cells, and the stored distance at or below which an observed voxel is occupied"""
+    _fields_ = [("flags", C.c_int32), ("site_mask", C.c_int32), ("max_cells", C.c_int32), ("occupied_below", C.c_float)]
+
+
+assert C.sizeof(CellGrid) == 32 and C.sizeof(DistanceFieldParams) == 16
+
+
 class PyramidAhead(C.Structure):
     """vk_pyramid_ahead (vk.h): ABI 7's record of the retired pyramid ride; the library leaves it invalid"""
     _fields_ = [("key_depths", C.c_void_p), ("key_normals", C.c_void_p), ("frame_depths", C.c_void_p), ("frame_normals", C.c_void_p),
