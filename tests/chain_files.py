@@ -34,6 +34,10 @@ CALLS = {
     "release_blocks": "Volume::ReleaseBlocks",
     "merge": "Volume::Merge(other)",
     "merge_posed": "Volume::Merge(other, Tdst_src)",
+    "merge_resampled": "Volume::MergeResampled(other, Tdst_src, supersample)",
+    "pack_merge": "Volume::Pack(options) of the source, Volume::Merge(pack); the pack's origins and voxels are written out",
+    "load": "Volume::Pack() of the source, PackedVolume::Save, Volume::Load(file, main, excess): the new object takes the place of `on`",
+    "distance_field": "Volume::DistanceField, squared, into the one DistanceFieldBuffers kept per volume",
     "frame": "Volume::SetView(frame, 3), or three SetView(frame) where the statement ran dry; DepthIntegrator::Integrate; Tracer::Trace",
     "raycast": "Tracer::Trace",
     "sample": "Volume::Sample, voxel units, gradients",
@@ -56,6 +60,8 @@ RETURNS = {
     "cast_rays": (("status", np.int32, ()), ("t", np.float32, ()), ("samples", T.voxel_dtype, ()), ("gradients", np.float32, (4,))),
     "extract": (("points", np.float32, (3,)), ("faces", np.int32, (3,)), ("colors", np.float32, (3,)), ("normals", np.float32, (3,))),
     "score_poses": (("scores", T.pose_score_dtype, ()),),
+    "pack_merge": (("origins", np.int16, (4,)), ("voxels", T.voxel_dtype, ())),        # behind the step's six counts
+    "distance_field": (("classes", np.uint8, ()), ("squared_cells", np.int32, ()), ("distance", np.uint32, ())),
 }
 LOOPS = ("register_terms", "register_rays_terms")
 
@@ -134,13 +140,27 @@ def tokens(w, orc, index, record):
             out += [("t_from", hex32(facts["t_from"]))]
         return out
     if operation == "release_blocks":
-        rule = R.RULES[facts["rule"]]
+        rule = facts["keywords"]
         lo, hi = rule.get("keep_box", ((0, 0, 0), (0, 0, 0)))
         return [("on", step.on), ("unobserved", int(bool(rule.get("unobserved")))), ("no_surface", int("min_abs_distance" in rule)),
                 ("min_abs_distance", hex32(rule.get("min_abs_distance", 0.0))), ("outside_box", int("keep_box" in rule)),
                 ("keep_lo", ",".join(str(v) for v in lo)), ("keep_hi", ",".join(str(v) for v in hi))]
     if operation in ("merge", "merge_posed"):
         return [("on", step.on), ("source", facts["source"]), ("pose", w.pose(facts["pose"])), ("max_rounds", facts["max_rounds"])]
+    if operation == "merge_resampled":
+        return [("on", step.on), ("source", facts["source"]), ("pose", w.pose(facts["pose"])), ("supersample", facts["supersample"]),
+                ("max_rounds", facts["max_rounds"]), ("skip_unobserved", int(facts["skip_unobserved"]))]
+    if operation == "pack_merge":
+        lo, hi = facts["box"] if facts["box"] is not None else ((0, 0, 0), (0, 0, 0))
+        return [("on", step.on), ("source", facts["source"]), ("box", int(facts["box"] is not None)), ("lo", ",".join(str(v) for v in lo)),
+                ("hi", ",".join(str(v) for v in hi)), ("skip_unobserved", int(facts["skip_unobserved"])), ("max_rounds", facts["max_rounds"]),
+                ("packed", facts["packed"][2])]
+    if operation == "load":
+        return [("on", step.on), ("source", facts["source"])]
+    if operation == "distance_field":
+        origin, dims = facts["grid"]
+        return [("on", step.reads[0]), ("origin", ",".join(str(v) for v in origin)), ("dims", ",".join(str(v) for v in dims)),
+                ("stride", facts["stride"]), ("max_cells", facts["max_cells"]), ("signed", int(facts["signed"])), ("sites", facts["sites"])]
     if operation == "frame":
         out, hf = _frame(w, orc, facts["yaw"])
         return [("on", step.on)] + out + [("depth", w.array(f"depth_{facts['yaw']:g}", lambda: hf.depth)), ("ran_dry", int(bool(record.want[1])))]

@@ -12,6 +12,11 @@ Two of the read steps compare the terms of a registration, which the C++ class l
 statement of the loop the class makes instead, for tests/test_gpu_chain_replay.py, which runs the same chains through that layer
 from the files tests/chain_files.py writes.
 
+The chains over two lattices (two_resolutions, resampled_exhausted, random_resolution_chain) add the resampled merge, the pack
+and its merge, the load of a saved map into an object of other table sizes and the clearance field; they start from the
+depth-integrated view, since a map of two ray quarters gives a resampled merge next to nothing to sample. These four are not
+yet calls of the class layer's replay.
+
 The rays are integrate_rays_reference.pixel_hits: the 19 200 pixel rays with the ranges cast_rays gives them, taken in strided
 quarters of 4 800; the colours are color_rays_reference.colors_for, seeded by the quarter."""
 import numpy as np
@@ -19,10 +24,13 @@ import numpy as np
 import carve_rays_reference as CV
 import cast_reference as CR
 import color_rays_reference as CO
+import distance_field_reference as DF
 import extract_attributes_reference as A
 import integrate_rays_reference as IR
 import merge_pose_reference as MP
 import merge_reference as M
+import merge_resample_reference as MR
+import pack_reference as P
 import register_rays_reference as RY
 import register_reference as RR
 import release_reference as R
@@ -75,6 +83,21 @@ class DeviceSide:
     def __init__(self, api, volumes):
         self.api, self.volumes = api, volumes
         self._tensors, self._extractors, self._tracers = {}, {}, {}
+        self._directory = None
+
+    def directory(self):
+        """a temporary directory of this side's own, for the map files of the load steps: gone with the side"""
+        import pathlib
+        import tempfile
+        if self._directory is None:
+            self._directory = tempfile.TemporaryDirectory(prefix="map_life_")
+        return pathlib.Path(self._directory.name)
+
+    def replace(self, name, volume):
+        """another object under `name` (a load step): the Extractor and the Tracer of the one before go with it"""
+        self.volumes[name] = volume
+        self._extractors.pop(name, None)
+        self._tracers.pop(name, None)
 
     def tensor(self, key, make):
         import torch
@@ -208,9 +231,9 @@ def carve_rays(quarter, pose=None, flags=0, cap=16.0, stretch=BEYOND, on="map"):
                 t_from=kw["t_from"], stretch=stretch)
 
 
-def release_blocks(rule, on="map"):
-    """`rule`: a key of release_reference.RULES"""
-    keywords = R.RULES[rule]
+def release_blocks(rule, on="map", keep_box=None):
+    """`rule`: a key of release_reference.RULES; `keep_box`: that rule set with this box to keep, in block coordinates"""
+    keywords = R.RULES[rule] if keep_box is None else dict(R.RULES[rule], keep_box=keep_box)
 
     def host(orc, volumes):
         return R.release_blocks(volumes[on], *R.helper_arguments(keywords))
@@ -222,8 +245,9 @@ def release_blocks(rule, on="map"):
         dv = side.volumes[on]
         _workspace(side, on, "release", (dv.main, dv.excess), "vk_volume_release_workspace_bytes", 4)
 
-    return Step(f"release_blocks({rule})", MUTATE, on, host, device, workspace, work=lambda counts: counts[0] > 0,
-                operation="release_blocks", rule=rule)
+    name = f"release_blocks({rule}{'' if keep_box is None else ', keep %s .. %s' % keep_box})"
+    return Step(name, MUTATE, on, host, device, workspace, work=lambda counts: counts[0] > 0,
+                operation="release_blocks", rule=rule, keywords=keywords)
 
 
 def merge_statement(dst, src, pose=None, max_rounds=8, calls=None):
@@ -231,11 +255,17 @@ def merge_statement(dst, src, pose=None, max_rounds=8, calls=None):
     round, dropped none and still left blocks out — the later calls' counts added up as Volume._merge_rounds adds them.
     `calls`: a list that takes the counts of every call made"""
     workspace = {}
-    dropped = int(dst.counters[T.VK_CTR_DROPPED])
     if pose is None:
-        call, left_out, rounds, summed = (lambda flags: M.merge(dst, src, flags, max_rounds, workspace=workspace)), 3, 4, (1, 2, 4)
-    else:
-        call, left_out, rounds, summed = (lambda flags: MP.merge(dst, src, pose, flags, max_rounds, workspace=workspace)), 4, 5, (2, 3, 5, 7)
+        return rounds_statement(dst, lambda flags: M.merge(dst, src, flags, max_rounds, workspace=workspace), max_rounds, False, calls)
+    return rounds_statement(dst, lambda flags: MP.merge(dst, src, pose, flags, max_rounds, workspace=workspace), max_rounds, True, calls)
+
+
+def rounds_statement(dst, call, max_rounds, eight, calls=None):
+    """Volume._merge_rounds on the host: `call(0)`, then `call(CONTINUE)` under merge_statement's rule. `eight`: the call
+    returns the eight counts of the posed and the resampled merge (left out = 4, rounds = 5, summed 2, 3, 5, 7), not the
+    six of the plain and the packed one (left out = 3, rounds = 4, summed 1, 2, 4)"""
+    dropped = int(dst.counters[T.VK_CTR_DROPPED])
+    left_out, rounds, summed = (4, 5, (2, 3, 5, 7)) if eight else (3, 4, (1, 2, 4))
     counts = call(0)
     total = list(counts)
     made = [] if calls is None else calls
@@ -272,6 +302,118 @@ def merge(on, source, pose=None, max_rounds=8):
     step = Step(name, MUTATE, on, host, device, workspace, reads=(source,),
                 work=lambda counts: counts[1 if pose is None else 2] > 0, operation="merge", posed=pose is not None, allocates=True, source=source, pose=pose,
                 max_rounds=max_rounds)
+    return step
+
+
+def merge_resampled(on, source, pose, supersample, max_rounds=8, skip_unobserved=False):
+    """volume `on` takes volume `source` of another voxel or truncation length through `pose` (T_on_source), `supersample`^3
+    samples a voxel, in calls of `max_rounds` allocation rounds: Volume.merge_resampled, with merge's rule for the calls that
+    continue; the calls the statement made are the step's facts["calls"]"""
+    step = None
+    flags = MR.SKIP_UNOBSERVED if skip_unobserved else 0
+
+    def host(orc, volumes):
+        step.facts["calls"] = []
+        dst, src, workspace = volumes[on], volumes[source], {}
+        return rounds_statement(dst, lambda go_on: MR.merge(dst, src, pose, supersample, flags | go_on, max_rounds, workspace=workspace),
+                                max_rounds, True, step.facts["calls"])
+
+    def device(orc, side, want):
+        return side.volumes[on].merge_resampled(side.volumes[source], pose=pose, supersample=supersample, skip_unobserved=skip_unobserved,
+                                                max_rounds=max_rounds)
+
+    def workspace(side):
+        dv, ds = side.volumes[on], side.volumes[source]
+        box = MR.box_blocks(f32(ds.voxel_length) / f32(dv.voxel_length))
+        _workspace(side, on, "merge_resampled", (ds.main, ds.excess, dv.main, dv.excess, box), "vk_volume_merge_resampled_workspace_bytes", 8)
+
+    name = (f"merge_resampled({on} <- {source}, n {supersample}{', skip unobserved' if skip_unobserved else ''}"
+            f"{'' if max_rounds == 8 else ', %d round(s) a call' % max_rounds})")
+    step = Step(name, MUTATE, on, host, device, workspace, reads=(source,), work=lambda counts: counts[2] > 0 and counts[7] > 0,
+                operation="merge_resampled", allocates=True, source=source, pose=pose, supersample=supersample, max_rounds=max_rounds,
+                skip_unobserved=skip_unobserved)
+    return step
+
+
+def _pack_rule(box, skip_unobserved):
+    flags = (P.SKIP_UNOBSERVED if skip_unobserved else 0) | (P.BOX if box is not None else 0)
+    lo, hi = box if box is not None else ((0, 0, 0), (0, 0, 0))
+    return flags, lo, hi
+
+
+def pack_merge(on, source, box=None, skip_unobserved=False, max_rounds=8):
+    """volume `source` packed under the rule (`box` in block coordinates, inclusive; `skip_unobserved`), and the pack merged
+    into volume `on` (which may be `source` itself: a pack is a copy): Volume.pack, then Volume.merge(pack). Returns merge's
+    six counts, then the pack's origins and voxels; the pack's four counts are the step's facts["packed"]"""
+    step = None
+
+    def host(orc, volumes):
+        dst, workspace = volumes[on], {}
+        origins, voxels, step.facts["packed"] = P.pack(volumes[source], *_pack_rule(box, skip_unobserved))
+        src = volumes[source]
+        step.facts["calls"] = []
+        if len(origins) == 0:                                             # Volume.merge makes no call for a pack without blocks
+            return (0, 0, 0, 0, 0, 0, origins, voxels)
+        counts = rounds_statement(dst, lambda go_on: P.merge_packed(dst, origins, voxels, len(origins), src.voxel_length, src.truncation_length,
+                                                                    go_on, max_rounds, workspace=workspace),
+                                  max_rounds, False, step.facts["calls"])
+        return counts + (origins, voxels)
+
+    def device(orc, side, want):
+        pack = side.volumes[source].pack(box=box, skip_unobserved=skip_unobserved)
+        counts = side.volumes[on].merge(pack, max_rounds=max_rounds)
+        return tuple(counts) + pack.host()
+
+    def workspace(side):
+        ds = side.volumes[source]
+        _workspace(side, source, "pack", (ds.main, ds.excess), "vk_volume_pack_workspace_bytes", 4)
+        _workspace(side, on, "merge_packed", (step.facts["packed"][2],), "vk_volume_merge_packed_workspace_bytes", 6)
+
+    rule = "".join([", box" if box is not None else "", ", skip unobserved" if skip_unobserved else ""])
+    name = f"pack_merge({on} <- {source}{rule}{'' if max_rounds == 8 else ', %d round(s) a call' % max_rounds})"
+    step = Step(name, MUTATE, on, host, device, workspace, reads=(source,), work=lambda want: want[1] > 0, operation="pack_merge",
+                allocates=True, source=source, box=box, skip_unobserved=skip_unobserved, max_rounds=max_rounds)
+    return step
+
+
+def load(on, source):
+    """volume `source` packed whole, saved, and the file loaded as a new volume in the place of `on` — a volume the chain
+    starts fresh, of `source`'s lattice and of table sizes of its own, which nothing has touched: PackedVolume.save, then
+    Volume.load with `on`'s sizes. Volume.load returns the volume and no counts (it raises where a block is left out), so
+    the step returns the one number both sides can give, (blocks loaded,): on the host the blocks the merge of the load —
+    both caps 32767 — fused, none left out; on the device the blocks of the pack that was saved. What holds the device to
+    the statement is the state of `on` compared behind the step."""
+    step = None
+
+    def host(orc, volumes):
+        dst, src = volumes[on], volumes[source]
+        assert not (dst.hash_entries["data"] >= 0).any() and not (dst.voxels["distance_weight"] != 0).any(), f"{on} is not fresh"
+        assert int(dst.counters[T.VK_CTR_DROPPED]) == 0, f"{on} is not fresh"
+        assert (f32(dst.voxel_length), f32(dst.truncation_length)) == (f32(src.voxel_length), f32(src.truncation_length))
+        origins, voxels, step.facts["packed"] = P.pack(src)
+        workspace = {}
+        counts = rounds_statement(dst, lambda go_on: P.merge_packed(dst, origins, voxels, len(origins), src.voxel_length, src.truncation_length,
+                                                                    go_on, 8, 32767.0, 32767.0, workspace=workspace),
+                                  8, False)
+        assert counts[3] == 0 and counts[1] == len(origins), "the chain's sizes for the loaded volume must hold the map"
+        return (counts[1],)
+
+    def device(orc, side, want):
+        api, old = side.api, side.volumes[on]
+        path = side.directory() / f"{on}.vkmap"
+        pack = side.volumes[source].pack()
+        pack.save(path)
+        new = api.Volume.load(path, old.main, old.excess)
+        assert new._workspaces == {} and new._sample_pose is None, "a loaded volume has made no call of its own"
+        side.replace(on, new)
+        return (len(pack),)
+
+    def workspace(side):
+        ds = side.volumes[source]
+        _workspace(side, source, "pack", (ds.main, ds.excess), "vk_volume_pack_workspace_bytes", 4)
+
+    step = Step(f"load({on} <- {source})", MUTATE, on, host, device, workspace, reads=(source,), work=lambda counts: counts[0] > 0,
+                operation="load", allocates=True, source=source)
     return step
 
 
@@ -475,6 +617,39 @@ def register_rays_terms(quarter, pose, on="map"):
                 work=lambda want: want[0].sum() > 1000, class_host=class_host, operation="register_rays", quarter=quarter, pose=pose)
 
 
+def distance_field(on, stride, max_cells, signed=False, sites=DF.OCCUPIED, most=(64, 56, 48)):
+    """Volume.distance_field over distance_field_reference.grid_around of the host state's blocks, at most `most` cells an
+    axis — the grid comes with the statement, as sample's points do, and is the step's facts["grid"]: (the grid's origin
+    and dims [6], classes, squared cells, the distance's bits as uint32)"""
+    step = None
+
+    def host(orc, volumes):
+        hv = volumes[on]
+        table = RR.block_table(hv)
+        origin, dims = DF.grid_around(table, stride, most)
+        step.facts["grid"] = (origin, dims)
+        classes, d2, distance = DF.distance_field(hv, origin, dims, stride, max_cells, site_mask=sites, signed=signed, table=table)
+        return np.array(origin + dims, dtype=np.int64), classes, d2, np.ascontiguousarray(distance, dtype=f32).view(np.uint32)
+
+    def device(orc, side, want):
+        origin, dims = tuple(int(c) for c in want[0][:3]), tuple(int(c) for c in want[0][3:])
+        got = side.volumes[on].distance_field(origin, dims, stride=stride, max_cells=max_cells, sites=sites, signed=signed, squared=True)
+        return want[0], got.classes.cpu().numpy(), got.squared_cells.cpu().numpy(), got.distance.cpu().numpy().view(np.uint32)
+
+    def workspace(side):
+        dims = step.facts["grid"][1]
+        side.volumes[on]._workspace("distance_field", tuple(dims), side.api._grid_workspace_bytes, 1)
+
+    def work(want):
+        classes, d2 = want[1], want[2]
+        return all((classes == c).any() for c in (DF.UNKNOWN, DF.FREE, DF.OCCUPIED)) and ((d2 > 0) & (d2 != DF.BEYOND)).any()
+
+    name = f"distance_field({on}, stride {stride}, {max_cells} cells{', signed' if signed else ''}{'' if sites == DF.OCCUPIED else ', sites %d' % sites})"
+    step = Step(name, READ, None, host, device, workspace, reads=(on,), work=work, operation="distance_field", stride=stride,
+                max_cells=max_cells, signed=signed, sites=sites)
+    return step
+
+
 def same(got, want):
     """is what the device returned what the statement returned, bit for bit: counts as they are, arrays as bytes"""
     if isinstance(want, (tuple, list)):
@@ -555,6 +730,66 @@ def pose_buffer():
     return Chain("pose_buffer", {"map": lambda orc: R.fused_state(orc, *LONG)}, steps)
 
 
+COARSE = (0.016, 0.08)                                     # the other lattice: voxel and truncation length in metres
+MIDDLE = (0.012, 0.06)                                     # a third lattice, of `coarse`'s table sizes
+MID_CUT = ((-2, -2, 9), (1, 1, 11))
+FINE_CUT = ((-6, -5, 13), (5, 4, 17))                      # block boxes, inclusive, that cut a source before it is sampled
+COARSE_CUT = ((-3, -3, 6), (2, 2, 8))
+COARSE_SMALL = ((-1, -2, 6), (1, 0, 8))
+FIT_BOX = ((0, -3, 7), (3, 0, 8))                           # resampled_exhausted: 32 blocks, each present in the dry destination
+PACK_BOX = ((-4, -4, 5), (1, 3, 9))                        # the box of two_resolutions' pack, on the 16 mm lattice
+
+
+def field_reads(on):
+    """Volume.distance_field on three grids in a row through the volume's one cached workspace: one, one of another shape,
+    the first again"""
+    return [distance_field(on, 1, 16), distance_field(on, 2, 12), distance_field(on, 1, 16)]
+
+
+def two_resolutions():
+    """a depth-integrated 8 mm map that lives (colour from rays, carved, released), resampled into a 16 mm map that then
+    lives itself (a camera, carved, released), resampled back one round a call with a plain posed merge straight behind it,
+    saved and loaded into other table sizes, and the loaded map — a camera and a repair later — packed under a rule
+    back into the 16 mm map; the clearance field at every stage"""
+    generic, identity = MP.generic(), T.Transform.identity()
+    fine, coarse, back, loaded, mid = "fine", "coarse", "back", "loaded", "mid"
+    steps = [color_rays(0, flags=IR.VOXEL_UNITS, band=CO.TWO_VOXELS, on=fine), carve_rays(0, on=fine), carve_rays(0, on=fine), carve_rays(0, on=fine),
+             release_blocks("unobserved+no-surface", on=fine, keep_box=FINE_CUT)]
+    steps += [merge_resampled(coarse, fine, generic, 2), raycast(12, on=coarse), frame(12, on=coarse)]
+    steps += checkpoint(coarse)[:5] + field_reads(coarse)
+    steps += [carve_rays(0, on=coarse), distance_field(coarse, 1, 16, signed=True, sites=7), distance_field(coarse, 1, 16, signed=True, sites=DF.OCCUPIED),
+              release_blocks("no-surface", on=coarse, keep_box=COARSE_CUT)]
+    # two ratios into one destination from sources of one table size: the cached workspace differs in the box size K alone
+    # (12 mm into 8 mm: K = 4, then 16 mm into 8 mm: K = 5, the larger one second)
+    steps += [merge_resampled(mid, fine, generic, 2), release_blocks("unobserved", on=mid, keep_box=MID_CUT),
+              merge_resampled(back, mid, identity, 1)]
+    steps += [merge_resampled(back, coarse, identity, 1, max_rounds=1), merge(back, fine, generic)]
+    steps += checkpoint(back, register=(fine, generic))
+    steps += [load(loaded, coarse), frame(25, on=loaded), release_blocks("repair", on=loaded)]
+    steps += checkpoint(loaded)[:5] + [distance_field(loaded, 1, 16)]
+    steps += [pack_merge(coarse, loaded, box=PACK_BOX, skip_unobserved=True), raycast(12, on=coarse)]
+    steps += checkpoint(coarse)[:5] + [distance_field(coarse, 2, 12)]
+    start = {fine: lambda orc: M.view_state(orc, "a", *LONG), coarse: lambda orc: MR.fresh(orc, 509, 1024, *COARSE),
+             back: lambda orc: M.fresh(orc, *OTHER), loaded: lambda orc: MR.fresh(orc, *OTHER, *COARSE),
+             mid: lambda orc: MR.fresh(orc, 509, 1024, *MIDDLE)}
+    return Chain("two_resolutions", start, steps)
+
+
+def resampled_exhausted():
+    """a destination whose excess list a resampled merge runs dry: it drops, nothing continues; then the repair, the pack of
+    the same source cut to a box that fits, a camera, the raycast alone and the clearance field. A pack keeps its lattice
+    and merge(pack) refuses another, so the 8 mm source cannot be packed into the 16 mm destination: the source, cut by a
+    release, is first resampled into a roomy 16 mm volume "fit", and the pack is of that, under FIT_BOX"""
+    generic = MP.generic()
+    steps = [color_rays(0, on="fine"), carve_rays(0, on="fine"), release_blocks("unobserved+no-surface", on="fine"),
+             merge_resampled("coarse", "fine", generic, 2), release_blocks("repair", on="coarse"),
+             release_blocks("unobserved", on="fine", keep_box=FINE_CUT), merge_resampled("fit", "fine", generic, 2),
+             pack_merge("coarse", "fit", box=FIT_BOX), frame(12, on="coarse"), raycast(12, on="coarse"), distance_field("coarse", 1, 16)]
+    start = {"fine": lambda orc: M.view_state(orc, "a", *LONG), "coarse": lambda orc: MR.fresh(orc, 509, 16, *COARSE),
+             "fit": lambda orc: MR.fresh(orc, 509, 1024, *COARSE)}
+    return Chain("resampled_exhausted", start, steps)
+
+
 # Six seeds whose chains have no step that does nothing (tests/test_map_life.py). A release by the "repair" rule set releases
 # no block by definition, so a chain that draws it cannot pass that test and its seed is not among these: the repair alone is
 # a step of ray_map and of exhausted.
@@ -601,6 +836,99 @@ def random_chain(seed):
         previous = yaw_deg
     steps += [sample(), cast_rays(2), score_poses(2)]
     return Chain(f"random_chain({seed})", start, steps)
+
+
+RESOLUTION_OPERATIONS = OPERATIONS + ("merge_resampled", "pack_merge", "load")
+RESOLUTION_SEEDS = (1, 2, 12, 19, 24)
+_STARTS = {}
+
+
+def _resolution_start(orc, which):
+    """the dense starts of random_resolution_chain, made once and handed out as copies: view "a" cut to FINE_CUT, and what
+    the statement of the resampled merge makes of it on the 16 mm lattice through generic() with n = 2"""
+    if "fine" not in _STARTS:
+        _STARTS["fine"] = MR.cut(M.view_state(orc, "a", *LONG), FINE_CUT)
+        coarse = MR.fresh(orc, 509, 1024, *COARSE)
+        MR.merge(coarse, _STARTS["fine"], MP.generic(), 2)
+        _STARTS["coarse"] = coarse
+    return R.clone(orc, _STARTS[which])
+
+
+def random_resolution_chain(seed):
+    """random_chain's kind over two lattices: eight mutating steps drawn from the seed, each followed by a frame step on the
+    volume it changed — and, between the two, by the raycast alone at that volume's frame step before — and four reads
+    of each lattice's map at the end (sample, cast_rays, score_poses, distance_field).
+    The volumes: "fine" (8 mm, view "a" cut to a box) and "coarse" (16 mm, its resampled copy), view "b" for the plain
+    merge into "fine", and "loaded", fresh, for the one load a chain may draw — of the lattice of the map it will take,
+    which is known when the chain is drawn; from then on the loaded map lives in the place of the one it was loaded from.
+    The five old operations are drawn onto either lattice (rays in metres on the coarse one: random_chain's voxel units
+    are the fine lattice's); merge_resampled runs either way, n from 1 .. 3, through generic() or the identity, 1 or 8
+    rounds a call, behind a release that cuts its source to a box (facts["cut"]: the statement's cost goes with the blocks
+    sampled); pack_merge takes the pack of the map of its own lattice that the chain holds besides (the loaded map
+    and the one it came from) or of the map itself — a pack is a copy — under the box rule, the skip rule, both or none."""
+    rng = np.random.default_rng(5000 + seed)
+    generic, identity = MP.generic(), T.Transform.identity()
+    now = {"fine": "fine", "coarse": "coarse"}                            # lattice: the volume that lives there
+    loaded_lattice = None
+    steps, posed_merge, previous = [], False, {}
+    for _ in range(8):
+        operation = RESOLUTION_OPERATIONS[int(rng.integers(0, len(RESOLUTION_OPERATIONS)))]
+        lattice = ("fine", "coarse")[int(rng.integers(0, 2))]
+        quarter = int(rng.integers(0, 4))
+        pose = generic if rng.integers(0, 2) else None
+        flags = (IR.VOXEL_UNITS if rng.integers(0, 2) else 0) | (IR.ONE_OBSERVATION if rng.integers(0, 2) else 0)
+        cap = float((3, 16)[int(rng.integers(0, 2))])
+        rule = RULES[int(rng.integers(0, len(RULES)))]
+        yaw_deg = float((0, 12, 25)[int(rng.integers(0, 3))])
+        supersample = int(rng.integers(1, 4))
+        rounds = (1, 8)[int(rng.integers(0, 2))]
+        box, skip = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+        if lattice == "coarse":
+            flags &= ~IR.VOXEL_UNITS
+        if operation == "load" and loaded_lattice is not None:
+            operation = "pack_merge"                                     # one load a chain: "loaded" is fresh once
+        on = now[lattice]
+        if operation == "integrate_rays":
+            steps.append(integrate_rays(quarter, pose, flags, cap, on=on))
+        elif operation == "color_rays":
+            steps.append(color_rays(quarter, pose, flags, cap, on=on))
+        elif operation == "carve_rays":
+            steps.append(carve_rays(quarter, pose, flags, cap, on=on))
+        elif operation == "release_blocks":
+            steps.append(release_blocks(rule, on=on))
+        elif operation == "merge":
+            on = now["fine"]
+            through = pose if not posed_merge else None
+            posed_merge = posed_merge or through is not None
+            steps.append(merge(on, "b", through))
+        elif operation == "merge_resampled":
+            source = now["coarse" if lattice == "fine" else "fine"]
+            # (the statement's cost goes with the candidates times n^3: the source is cut to a box first, a small one on
+            # the coarse lattice, whose every block reaches a dozen fine ones)
+            cut = release_blocks("unobserved", on=source, keep_box=FINE_CUT if lattice == "coarse" else COARSE_SMALL)
+            cut.facts["cut"] = True
+            steps += [cut, merge_resampled(on, source, generic if pose is not None else identity, supersample, max_rounds=rounds)]
+        elif operation == "pack_merge":
+            source = lattice if loaded_lattice == lattice and on == "loaded" else on
+            steps.append(pack_merge(on, source, box=(FINE_CUT if lattice == "fine" else PACK_BOX) if box else None, skip_unobserved=skip))
+        else:
+            loaded_lattice, now[lattice] = lattice, "loaded"
+            steps.append(load("loaded", on))
+            on = "loaded"
+        if on in previous:
+            steps.append(raycast(previous[on], on=on))
+        steps.append(frame(yaw_deg, on=on))
+        previous[on] = yaw_deg
+    for lattice in ("fine", "coarse"):
+        on = now[lattice]
+        steps += [sample(on), cast_rays(2, on), score_poses(2, on), distance_field(on, 1 if lattice == "coarse" else 2, 12)]
+    start = {"fine": lambda orc: _resolution_start(orc, "fine"), "coarse": lambda orc: _resolution_start(orc, "coarse"),
+             "b": lambda orc: M.view_state(orc, "b", *OTHER)}
+    if loaded_lattice is not None:
+        start["loaded"] = (lambda orc: M.fresh(orc, *OTHER)) if loaded_lattice == "fine" else (lambda orc: MR.fresh(orc, *OTHER, *COARSE))
+    chain = Chain(f"random_resolution_chain({seed})", start, steps)
+    chain.drawn = [step for step in steps if step.kind == MUTATE and not step.facts.get("cut")]
+    return chain
 
 
 # ---- the host side of a chain: once, then never changed ------------------------------------------------------------------
@@ -673,7 +1001,7 @@ def _host_run(orc, chain, keep):
         record.step, record.want = step, step.host(orc, volumes)
         if step.kind == FRAME:
             defined[step.on] = False
-        elif step.kind == MUTATE and step.facts["operation"] in ("integrate_rays", "release_blocks", "merge"):
+        elif step.kind == MUTATE and step.facts["operation"] in ("integrate_rays", "release_blocks", "merge", "merge_resampled", "pack_merge", "load"):
             defined[step.on] = True
         if step.on is not None:
             after = dict(after)

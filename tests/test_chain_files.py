@@ -12,6 +12,8 @@ import map_life as ML
 
 CHAINS = [ML.ray_map, ML.exhausted, ML.pose_buffer] + [lambda seed=seed: ML.random_chain(seed) for seed in ML.SEEDS]
 IDS = ["ray_map", "exhausted", "pose_buffer"] + [f"random_chain({seed})" for seed in ML.SEEDS]
+CHAINS += [ML.two_resolutions, ML.resampled_exhausted] + [lambda seed=seed: ML.random_resolution_chain(seed) for seed in ML.RESOLUTION_SEEDS]
+IDS += ["two_resolutions", "resampled_exhausted"] + [f"random_resolution_chain({seed})" for seed in ML.RESOLUTION_SEEDS]
 
 
 def digest(directory):
@@ -51,6 +53,16 @@ def test_a_chain_writes_and_parses_back(orc, tmp_path, make):
             assert (arguments["pose"] == "-") == (facts["pose"] is None)
             if facts["pose"] is not None:
                 assert open(tmp_path / "a" / arguments["pose"], "rb").read() == bytes(facts["pose"])
+        if operation == "merge_resampled":
+            facts = run.records[index].step.facts
+            assert int(arguments["supersample"]) == facts["supersample"] and int(arguments["max_rounds"]) == facts["max_rounds"]
+            assert open(tmp_path / "a" / arguments["pose"], "rb").read() == bytes(facts["pose"])
+        if operation == "distance_field":
+            origin, dims = run.records[index].step.facts["grid"]
+            assert tuple(int(v) for v in arguments["origin"].split(",")) == origin and tuple(int(v) for v in arguments["dims"].split(",")) == dims
+            assert all(o % int(arguments["stride"]) == 0 for o in origin)
+        if operation == "pack_merge":
+            assert int(arguments["packed"]) == len(run.records[index].want[6]) > 0
     # twice: the same bytes
     CF.write(run, str(tmp_path / "b"), "noise", again=again)
     assert digest(str(tmp_path / "a")) == digest(str(tmp_path / "b"))

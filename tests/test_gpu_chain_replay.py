@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "vulcan_amd", "host", "bin", "chain_replay")
 POSE_BOUND = 2e-5
-EMPTIES_THE_VISIBLE_LIST = ("integrate_rays", "release_blocks", "merge", "merge_posed")
+EMPTIES_THE_VISIBLE_LIST = ("integrate_rays", "release_blocks", "merge", "merge_posed", "merge_resampled", "pack_merge", "load")
 
 
 def replay(directory, fill, exe=EXE, env=None):
@@ -75,11 +75,14 @@ def assert_step(operation, record, got, fill):
     step, want = record.step, record.want
     if step.kind == ML.MUTATE:
         counts = tuple(int(c) for c in got["counts"])
-        assert counts == tuple(int(c) for c in want), f"counts {counts} for {tuple(want)}"
+        expected = tuple(int(c) for c in want if not isinstance(c, np.ndarray))
+        assert counts == expected, f"counts {counts} for {expected}"
         assert CF.SENTINEL not in counts
+        if operation == "pack_merge":                                    # the pack itself, behind the six counts
+            assert_returns(got["returns"], want[6:])
     elif operation == "frame":
         assert_returns(got["returns"], want[0])
-    elif operation == "sample":
+    elif operation in ("sample", "distance_field"):                      # the points and the grid are the statement's own
         assert_returns(got["returns"], want[1:])
     elif operation in CF.LOOPS:
         assert_loop(got["loop"], record.class_want)
@@ -159,3 +162,20 @@ def test_the_pose_buffer_through_the_classes(orc, tmp_path):
 @pytest.mark.parametrize("seed", ML.SEEDS)
 def test_random_chain_through_the_classes(orc, tmp_path, seed):
     run_through_the_classes(orc, ML.random_chain(seed), "noise", tmp_path, keep=False)
+
+
+@pytest.mark.parametrize("fill", CF.FILLS)
+def test_two_resolutions_through_the_classes(orc, tmp_path, fill):
+    """MergeResampled, Pack + Merge(pack), PackedVolume::Save + Volume::Load and DistanceField as steps: the 16 mm map a
+    resampled merge made lives on through the classes, DistanceField (const) resizes field_workspace_ for three grids in a
+    row, and the object Volume::Load hands out takes the place of the fresh one and goes on: frame, repair, reads"""
+    run_through_the_classes(orc, ML.two_resolutions(), fill, tmp_path)
+
+
+def test_resampled_exhausted_through_the_classes(orc, tmp_path):
+    run_through_the_classes(orc, ML.resampled_exhausted(), "noise", tmp_path)
+
+
+@pytest.mark.parametrize("seed", ML.RESOLUTION_SEEDS)
+def test_random_resolution_chain_through_the_classes(orc, tmp_path, seed):
+    run_through_the_classes(orc, ML.random_resolution_chain(seed), "noise", tmp_path, keep=False)

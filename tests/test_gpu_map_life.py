@@ -20,6 +20,8 @@ pytestmark = pytest.mark.gpu
 
 WORKSPACES = ["as-allocated", "ones", "noise"]
 SENTINEL = 0x5A5A5A5A
+NEW_OPERATIONS = ("merge_resampled", "pack_merge", "load", "distance_field")
+NEW_WORKSPACES = {"merge_resampled", "pack", "merge_packed", "distance_field"}      # their keys of Volume._workspaces
 BUFFERS = ("voxels", "hash_entries", "free_voxel_blocks", "allocation_types", "allocation_blocks", "block_visibility", "visible_blocks",
            "counters")
 
@@ -83,11 +85,17 @@ def run_on_device(api, orc, chain, workspaces="as-allocated", keep=True):
             if workspaces != "as-allocated" and step.kind != ML.FRAME:
                 step.workspace(side)
                 overwrite_held(side, workspaces, generator)
+            held = {name: (dv, dict(dv._workspaces)) for name, dv in side.volumes.items()}
             got = step.device(orc, side, record.want)
             sync()
+            if workspaces != "as-allocated" and step.facts["operation"] in NEW_OPERATIONS:
+                # the call used the workspaces step.workspace() made and overwrite_held dirtied: it allocated none of them again
+                for name, (dv, before) in held.items():
+                    for operation in NEW_WORKSPACES & set(before):
+                        assert dv._workspaces[operation] is before[operation], f"{name}: a new {operation} workspace"
             assert ML.same(got, record.want), ML.first_difference(got, record.want)
             if workspaces != "as-allocated" and step.kind == ML.MUTATE:          # the counts came from the call, not from the sentinel
-                assert SENTINEL not in got
+                assert SENTINEL not in [part for part in got if not isinstance(part, np.ndarray)]
             # the state: behind every step that changes a volume, and behind the last read of a checkpoint
             read |= set(step.reads)
             last_read = step.kind == ML.READ and (index + 1 == len(run.records) or run.records[index + 1].step.kind != ML.READ)
@@ -115,28 +123,61 @@ def test_random_chain(api, orc, seed):
     run_on_device(api, orc, ML.random_chain(seed), "noise", keep=False)
 
 
-def test_a_second_volume_object_sees_the_same_map(api, orc):
-    """after ray_map the map is downloaded and uploaded into a new api.Volume: the last checkpoint again, from an object that
-    has made no call — nothing the operations need lives only in the first object's caches"""
-    side, run = run_on_device(api, orc, ML.ray_map())
+def cached_workspaces(side):
+    """the operations whose workspace some volume of the side holds: held_tensors overwrites exactly these"""
+    return set(operation for dv in side.volumes.values() for operation in dv._workspaces)
+
+
+@pytest.mark.parametrize("workspaces", WORKSPACES)
+def test_two_resolutions_chain(api, orc, workspaces):
+    side, _ = run_on_device(api, orc, ML.two_resolutions(), workspaces)
+    assert cached_workspaces(side) >= NEW_WORKSPACES
+
+
+@pytest.mark.parametrize("workspaces", WORKSPACES)
+def test_resampled_exhausted_chain(api, orc, workspaces):
+    side, _ = run_on_device(api, orc, ML.resampled_exhausted(), workspaces)
+    assert cached_workspaces(side) >= NEW_WORKSPACES
+
+
+@pytest.mark.parametrize("seed", ML.RESOLUTION_SEEDS)
+def test_random_resolution_chain(api, orc, seed):
+    run_on_device(api, orc, ML.random_resolution_chain(seed), "noise", keep=False)
+
+
+def second_object_sees_the_same_map(api, orc, chain, name):
+    """after `chain` its volume `name` is downloaded and uploaded into a new api.Volume: the last checkpoint again, from an
+    object that has made no call — nothing the operations need lives only in the first object's caches"""
+    side, run = run_on_device(api, orc, chain)
     sync()
-    first = side.volumes["map"]
-    hv = run.records[-1].after["map"].restore(orc)
-    for name in BUFFERS:
-        array = getattr(first, name).cpu().numpy()
-        getattr(hv, name)[:] = np.frombuffer(array.tobytes(), dtype=getattr(hv, name).dtype)
+    first = side.volumes[name]
+    hv = run.records[-1].after[name].restore(orc)
+    for buffer in BUFFERS:
+        array = getattr(first, buffer).cpu().numpy()
+        getattr(hv, buffer)[:] = np.frombuffer(array.tobytes(), dtype=getattr(hv, buffer).dtype)
     second = device_copy(api, hv)
     assert second._workspaces == {} and second._sample_pose is None and second._register_buffers is None
-    again = ML.DeviceSide(api, {"map": second, "other": side.volumes["other"]})
+    again = ML.DeviceSide(api, dict(side.volumes, **{name: second}))
     at = max(index for index, record in enumerate(run.records) if record.step.kind != ML.READ)
     assert len(run.records) - at - 1 >= 3
     for record in run.records[at + 1:]:
         got = record.step.device(orc, again, record.want)
         sync()
         assert ML.same(got, record.want), f"{record.step.name}: {ML.first_difference(got, record.want)}"
-    for name in BUFFERS:
-        assert getattr(second, name).cpu().numpy().tobytes() == getattr(first, name).cpu().numpy().tobytes(), name
-    assert_state(second, run.records[-1].after["map"].restore(orc), run.records[-1].defined["map"])
+    for buffer in BUFFERS:
+        assert getattr(second, buffer).cpu().numpy().tobytes() == getattr(first, buffer).cpu().numpy().tobytes(), buffer
+    assert_state(second, run.records[-1].after[name].restore(orc), run.records[-1].defined[name])
+
+
+def test_a_second_volume_object_sees_the_same_map(api, orc):
+    """ray_map's map (second_object_sees_the_same_map)"""
+    second_object_sees_the_same_map(api, orc, ML.ray_map(), "map")
+
+
+def test_a_second_volume_object_sees_the_same_coarse_map(api, orc):
+    """two_resolutions' 16 mm map, which a resampled merge made and a pack went into: its last checkpoint, the clearance
+    field included, from an object with no cached workspace"""
+    second_object_sees_the_same_map(api, orc, ML.two_resolutions(), "coarse")
 
 
 @pytest.mark.parametrize("workspaces", ["as-allocated", "noise"])

@@ -2,6 +2,7 @@
 the device to every step of them, so a chain that never pops a rebuilt free list, never reads a colour that color_rays wrote or
 never runs its pool dry would make that file green for nothing. Every number below is a lower bound on what the statements
 give (the measured value stands beside it), never the digits themselves."""
+import numpy as np
 import pytest
 
 import cast_reference as CR
@@ -212,3 +213,195 @@ def test_the_loops_of_the_class_layer_move_the_pose(orc):
         print(record.step, want.steps, want.code, want.counts)
         assert want.steps == ML.LOOP_STEPS and want.counts[2] > 100       # the bar of the scores: more than 100 residuals
         assert bytes(want.pose) != bytes(record.step.facts["pose"]) or want.code == 1
+
+
+# ---- the chains over two lattices ----------------------------------------------------------------------------------------
+
+def steps_of(run, operation):
+    return [(index, record) for index, record in enumerate(run.records) if record.step.facts["operation"] == operation]
+
+
+def carved(state):
+    """voxels that carve_rays pushed to distance 1 and that keep a weight"""
+    voxels = state.written_voxels()
+    return int(((voxels["distance"] == 1) & (voxels["distance_weight"] > 0)).sum())
+
+
+def assert_fields_have_all_classes(run):
+    fields = steps_of(run, "distance_field")
+    for _, record in fields:
+        classes = record.want[1]
+        print(record.step, [int((classes == c).sum()) for c in (ML.DF.UNKNOWN, ML.DF.FREE, ML.DF.OCCUPIED)])
+        assert all((classes == c).any() for c in (ML.DF.UNKNOWN, ML.DF.FREE, ML.DF.OCCUPIED)), record.step
+        # (with every class a site no cell has a distance to measure: the one read that is all zeros and -inf by definition)
+        assert record.step.work(record.want) or record.step.facts["sites"] == 7, record.step
+    return fields
+
+
+def test_two_resolutions_reaches_what_it_is_for(orc):
+    run = ML.host_run(orc, ML.two_resolutions())
+    for index, record in changing(run):
+        if record.step.facts.get("rule") != "repair":
+            assert record.step.work(record.want), record.step
+
+    # the resampled merge samples a source that has lived: carved voxels (measured: 56 529), colour that color_rays wrote
+    # where the camera wrote none, a table a release compacted — and the colour arrives
+    (at, down), _, (second_at, second), (up_at, up) = steps_of(run, "merge_resampled")
+    fine, was, coarse = ML.before(run, at)["fine"], ML.before(run, at)["coarse"], down.after["coarse"]
+    release = run.records[at - 1]
+    rays = run.records[0]
+    print("fine: carved", carved(fine), "coloured", coloured(fine), "by color_rays", rays.want, "release", release.want)
+    assert release.step.facts["operation"] == "release_blocks" and release.want[0] > 100
+    # colour from rays, in a band of two voxels and not the truncation band the camera's colour lies in
+    assert rays.step.facts["operation"] == "color_rays" and rays.step.facts["band"] == 2.0 and rays.want[5] > 5000       # voxels (measured: 19 758)
+    assert rays.after["fine"].written_voxels()["color"].tobytes() != run.start["fine"].written_voxels()["color"].tobytes()
+    assert carved(fine) > 10000 and coloured(fine) > 10000
+    print("down", down.want, "coloured", coloured(coarse))
+    assert not ML.entries_in_use(was) and down.want[7] > 5000 and coloured(coarse) > 1000
+    assert coarse.counters[T.VK_CTR_VISIBLE] == 0 and coarse.counters[T.VK_CTR_BANDED] == -1
+    assert run.records[at + 1].step.facts["operation"] == "raycast" and not run.records[at + 1].want[0].any()
+    camera = run.records[at + 2]
+    assert camera.step.kind == ML.FRAME and int((camera.want[0][0] > 0).sum()) > 10000
+
+    # two ratios into one destination, from sources of one table size: the workspaces differ in K alone, the larger K second
+    a, b, into = ML.before(run, second_at)["mid"], ML.before(run, up_at)["coarse"], second.after["back"]
+    boxes = [ML.MR.box_blocks(np.float32(source.shape[2]) / np.float32(into.shape[2])) for source in (a, b)]
+    print("into back", second.want, "K", boxes)
+    assert second.step.on == up.step.on == "back" and (a.main, a.excess) == (b.main, b.excess) and boxes[0] < boxes[1]
+    assert second.want[3] > 50 and up.want[2] - up.want[3] > 50          # the second merge also fuses into blocks the first made
+
+    # back, one round a call: more calls than one (measured: 3), from a source that was carved and released on its lattice
+    calls = up.step.facts["calls"]
+    source = ML.before(run, up_at)["coarse"]
+    print("up", up.want, "calls", calls, "coarse: carved", carved(source))
+    assert up.step.facts["max_rounds"] == 1 and len(calls) >= 2 and carved(source) > 1000
+    assert all(call[5] == 1 and call[4] > 0 for call in calls[:-1]) and up.want[4] == 0
+    assert up.want[2] == sum(call[2] for call in calls) and up.want[7] == sum(call[7] for call in calls)
+    posed = run.records[up_at + 1]
+    assert posed.step.facts["operation"] == "merge" and posed.step.facts["posed"] and posed.want[3] > 100     # measured: 210 new blocks
+
+    # the pack of the released map is smaller than the pool's high-water mark, the loaded map is the map, and it goes on living
+    (at, loaded), = steps_of(run, "load")
+    source = ML.before(run, at)["coarse"]
+    high_water = max(len(ML.slots_in_use(record.after["coarse"])) for record in run.records[:at])
+    print("load", loaded.want, loaded.step.facts["packed"], "high-water mark", high_water)
+    assert loaded.step.facts["packed"][2] == len(ML.slots_in_use(source)) < high_water
+    a, b = ML.MP.cloud(loaded.after["loaded"].restore(orc)), ML.MP.cloud(source.restore(orc))
+    order_a, order_b = (np.lexsort(c[0].T) for c in (a, b))
+    assert (a[0][order_a] == b[0][order_b]).all() and a[1][order_a].tobytes() == b[1][order_b].tobytes()
+    assert (loaded.after["loaded"].main, loaded.after["loaded"].excess) != (source.main, source.excess)
+    assert run.records[at + 1].step.kind == ML.FRAME and run.records[at + 1].step.work(run.records[at + 1].want)
+
+    # the pack under a rule leaves blocks out (measured: 86 of 226) and lands in a destination that has lived
+    (at, packed), = steps_of(run, "pack_merge")
+    counts = packed.step.facts["packed"]
+    print("pack_merge", packed.want[:6], counts)
+    assert 0 < counts[1] < counts[0] and packed.want[1] == counts[2] and packed.want[2] > 0 and 0 < packed.want[1] - packed.want[2]
+    assert len(packed.want[6]) == counts[2] and len(packed.want[7]) == 512 * counts[2]
+
+    # the clearance field: three grids in a row (one, another shape, the first again), then behind a carve, a frame step, a load
+    fields = assert_fields_have_all_classes(run)
+    shapes = [record.want[1].shape for _, record in fields]
+    assert len(fields) == 7 and shapes[0] == shapes[2] != shapes[1]
+    assert [record.step.facts["sites"] for _, record in fields[3:5]] == [7, ML.DF.OCCUPIED]
+    assert all(record.step.facts["signed"] for _, record in fields[3:5])
+    assert not np.isfinite(fields[3][1].want[3].view(np.float32)).any()
+
+
+def test_resampled_exhausted_drops_then_recovers(orc):
+    run = ML.host_run(orc, ML.resampled_exhausted())
+    (at, dry), (_, fits) = steps_of(run, "merge_resampled")
+    was, now = ML.before(run, at)["coarse"], dry.after["coarse"]
+    calls = dry.step.facts["calls"]
+    print("dry", dry.want, "calls", calls)
+    assert (was.main, was.excess) == (509, 16)
+    assert dry.want[4] > 10 and len(calls) == 1                              # measured: 38 left out; a call that dropped is not continued
+    assert now.counters[T.VK_CTR_DROPPED] > was.counters[T.VK_CTR_DROPPED]
+    repair = run.records[at + 1]
+    assert repair.step.facts["rule"] == "repair" and repair.want[0] == 0
+    (_, packed), = steps_of(run, "pack_merge")
+    print("pack_merge", packed.want[:6], packed.step.facts["packed"])
+    assert packed.want[1] == packed.step.facts["packed"][2] >= 20 and packed.want[3] == 0        # the box fits: none left out
+    for record in run.records[-3:]:
+        assert record.step.work(record.want), record.step
+    assert [record.step.facts["operation"] for record in run.records[-3:]] == ["frame", "raycast", "distance_field"]
+    assert_fields_have_all_classes(run)
+
+
+NEW = ("merge_resampled", "pack_merge", "load")
+
+
+def resolution_summary(orc, seed):
+    """[(step, what the statement returned)] of random_resolution_chain(seed), every step; the snapshots are not kept"""
+    key = ("resolution", seed)
+    if key not in _SUMMARIES:
+        run = ML.host_run(orc, ML.random_resolution_chain(seed), keep=False)
+        _SUMMARIES[key] = [(record.step, record.want) for record in run.records]
+    return _SUMMARIES[key]
+
+
+def behind(steps):
+    """{(new operation, "release" | "frame")}: the operation ran on a volume — the one it changes or the one it reads —
+    whose last changing step was a frame step, or whose last drawn operation, the frame step behind it aside, was a release.
+    The release that cuts a resampled merge's source (facts["cut"]) stands in front of every one of them by construction
+    and does not count"""
+    last_mutate, last_change, out = {}, {}, set()
+    for step in steps:
+        if step.kind == ML.READ:
+            continue
+        operation = step.facts["operation"]
+        if operation in NEW:
+            for name in (step.on,) + step.reads:
+                if last_mutate.get(name) == "release_blocks":
+                    out.add((operation, "release"))
+                if last_change.get(name) == "frame":
+                    out.add((operation, "frame"))
+        if step.facts.get("cut"):
+            continue
+        if step.kind == ML.MUTATE:
+            last_mutate[step.on] = operation
+        last_change[step.on] = operation
+    return out
+
+
+@pytest.mark.parametrize("seed", ML.RESOLUTION_SEEDS)
+def test_no_step_of_a_random_resolution_chain_is_a_no_op(orc, seed):
+    steps = resolution_summary(orc, seed)
+    drawn = [(step, want) for step, want in steps if step.kind != ML.READ and not step.facts.get("cut")]
+    assert len(drawn) == 16 and [step.kind for step, _ in drawn] == [ML.MUTATE, ML.FRAME] * 8
+    assert all(frame.on == step.on for (step, _), (frame, _) in zip(drawn[0::2], drawn[1::2]))
+    for step, want in steps:
+        if step.kind == ML.MUTATE:
+            print(step, tuple(part for part in want if not isinstance(part, np.ndarray)))
+        if step.facts["operation"] != "raycast":
+            assert step.work(want), step
+    # the raycast alone: behind the new operations, which move blocks, what was made ahead is void and the image is empty
+    alone = [(steps[k - 1][0].facts["operation"], int((want[0] > 0).sum())) for k, (step, want) in enumerate(steps)
+             if step.facts["operation"] == "raycast"]
+    print(alone)
+    assert all(pixels == 0 for operation, pixels in alone if operation in NEW + ("integrate_rays", "release_blocks", "merge"))
+    assert [step.facts["operation"] for step, _ in steps[-4:]] == ["sample", "cast_rays", "score_poses", "distance_field"]
+
+
+def test_the_random_resolution_chains_cover_the_new_operations(orc):
+    assert len(ML.RESOLUTION_SEEDS) >= 4
+    seen = set()
+    for seed in ML.RESOLUTION_SEEDS:
+        chain = ML.random_resolution_chain(seed)
+        seen |= behind(chain.steps)
+    print(sorted(seen))
+    assert seen == {(operation, what) for operation in NEW for what in ("release", "frame")}
+    # and a raycast alone stands behind each of them, on a volume whose Tracer holds bounds an earlier frame step made ahead
+    # (behind a load the volume is a new object: there the bounds are its predecessor's, which the step lets go)
+    behind_new = set()
+    for seed in ML.RESOLUTION_SEEDS:
+        steps = ML.random_resolution_chain(seed).steps
+        behind_new |= {a.facts["operation"] for a, b in zip(steps, steps[1:]) if b.facts["operation"] == "raycast"}
+    print(sorted(behind_new))
+    assert behind_new >= {"merge_resampled", "pack_merge"}
+
+
+def test_the_old_random_chains_draw_what_they_drew(orc):
+    """random_resolution_chain stands beside random_chain: the old generator's operations and seeds are as they were"""
+    assert ML.OPERATIONS == ("integrate_rays", "color_rays", "carve_rays", "release_blocks", "merge") and ML.SEEDS == (1, 8, 9, 12, 15, 17)
+    assert ML.RESOLUTION_OPERATIONS[:5] == ML.OPERATIONS and set(ML.RESOLUTION_OPERATIONS[5:]) == set(NEW)

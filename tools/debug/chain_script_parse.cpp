@@ -56,7 +56,7 @@ int main(int argc, char** argv)
           if (!(step.Float(key) == step.Float(key))) throw chain::Error("a NaN in step " + std::to_string(step.index));
           ++floats;
         }
-        else if (key == "keep_lo" || key == "keep_hi")
+        else if (key == "keep_lo" || key == "keep_hi" || key == "lo" || key == "hi" || key == "origin" || key == "dims")
         {
           for (const std::string& item : step.Names(key)) (void)chain::Integer(item);
         }

@@ -954,6 +954,7 @@ class Volume:
         if counts[3]:
             raise VkError(f"Volume.load: {counts[3]} of {len(pack)} blocks did not fit ({main_block_count} main, "
                           f"{excess_block_count} excess entries)")
+        volume._workspaces.clear()          # the load's own workspace, sized by the file: the volume it hands out has made no call
         return volume
 
     def _merge_rounds(self, call, max_rounds, left_out, rounds, summed):

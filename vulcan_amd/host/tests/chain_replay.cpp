@@ -7,7 +7,8 @@
 //   ./chain_replay DIR as-allocated|ones|noise
 //
 // reads DIR/volumes.txt, DIR/script.txt and the arrays they name (chain_script.h), and writes into DIR/out, per step <i>:
-//   <i>.counts                       the counts the call returned, int32
+//   <i>.counts                       the counts the call returned, int32 (load: the blocks of the pack that was saved)
+//   <i>.origins, <i>.voxels          pack_merge: the pack itself; <i>.map (load): the file PackedVolume::Save wrote
 //   <i>.<array>                      what a read step returned, raw (tests/chain_files.py RETURNS)
 //   <i>.loop, <i>.pose               Register / RegisterRays: steps, end code, the four counts (the class's own buffers), then
 //                                    the Registration's steps, converged, overlap, residuals; the pose as a vk_transform
@@ -20,10 +21,12 @@
 //
 // "ones" / "noise": before every step but a frame step the buffers the coming call will ask for are sized as the class sizes
 // them, then every workspace, pose, score and counts buffer of every object is overwritten (0xFF; a fixed-seed xorshift; the
-// counts with 0x5A5A5A5A). The classes keep those buffers protected: the two classes below derive to reach them.
+// counts with 0x5A5A5A5A). The classes keep those buffers protected: the two classes below derive to reach them. The object
+// Volume::Load hands out is a plain Volume: its buffers cannot be reached and stay as its own calls leave them.
 //
 // Exit status 0: every step made and written. 1: an exception or a failed read, with the step's index and line; nothing
 // further is run. Nothing is retried and no process is started.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -114,6 +117,34 @@ class ReplayVolume : public Volume
       else if (op == "merge_posed")
         Sized(merge_pose_workspace_, vk_volume_merge_posed_workspace_bytes(other->GetMainBlockCount(), other->GetExcessBlockCount(),
             main, excess), merge_pose_counts_, 8);
+      else if (op == "merge_resampled")
+      {
+        const int box = std::min(8, int(other->GetVoxelLength() / GetVoxelLength() * 1.7320508f) + 2);      // K of vk.h
+        Sized(merge_resample_workspace_, vk_volume_merge_resampled_workspace_bytes(other->GetMainBlockCount(), other->GetExcessBlockCount(),
+            main, excess, box), merge_resample_counts_, 8);
+      }
+      else if (op == "pack_merge")
+        Sized(merge_packed_workspace_, vk_volume_merge_packed_workspace_bytes(step.Int("packed")), merge_packed_counts_, 6);
+      else if (op == "distance_field")
+      {
+        vk_cell_grid g;
+        std::memset(&g, 0, sizeof(g));
+        const std::vector<std::string> origin = step.Names("origin"), dims = step.Names("dims");
+        if (origin.size() != 3 || dims.size() != 3) throw chain::Error("a grid has three coordinates and three sizes");
+        for (int a = 0; a < 3; ++a)
+        {
+          g.origin[a] = chain::Integer(origin[a]);
+          g.dims[a] = chain::Integer(dims[a]);
+        }
+        g.stride = step.Int("stride");
+        vk_distance_field_params p;
+        p.flags = step.Flag("signed") ? VK_FIELD_SIGNED : 0;
+        p.site_mask = step.Int("sites");
+        p.max_cells = step.Int("max_cells");
+        p.occupied_below = 0.0f;
+        const size_t bytes = vk_volume_distance_field_workspace_bytes(&g, &p);
+        if (bytes != 0 && field_workspace_.GetSize() != bytes) field_workspace_.Resize(bytes);
+      }
       else if (op == "register_terms")
       {
         const size_t bytes = vk_volume_register_workspace_bytes(other->GetMainBlockCount(), other->GetExcessBlockCount());
@@ -141,8 +172,25 @@ class ReplayVolume : public Volume
         sample_pose_.Resize(32);
     }
 
+    // Pack of this volume is coming (pack_merge and load read their source through it)
+    void ExpectPack()
+    {
+      if (pack_counts_.GetSize() == 0)
+      {
+        pack_workspace_.Resize(vk_volume_pack_workspace_bytes(main_block_count_, excess_block_count_));
+        pack_counts_.Resize(4);
+      }
+    }
+
     void Overwrite(Dirt& dirt)
     {
+      Soil(dirt, merge_resample_workspace_);
+      Soil(dirt, merge_packed_workspace_);
+      Soil(dirt, pack_workspace_);
+      Soil(dirt, field_workspace_);
+      SoilCounts(dirt, merge_resample_counts_);
+      SoilCounts(dirt, merge_packed_counts_);
+      SoilCounts(dirt, pack_counts_);
       Soil(dirt, release_workspace_);
       Soil(dirt, merge_workspace_);
       Soil(dirt, merge_pose_workspace_);
@@ -199,11 +247,18 @@ class ReplayExtractor : public Extractor
 struct Kept
 {
   chain::Shape shape;
-  std::shared_ptr<ReplayVolume> volume;
+  std::shared_ptr<Volume> volume;
+  ReplayVolume* reach = nullptr;        // the same object where its protected buffers can be reached: not one Volume::Load made
+  std::unique_ptr<DistanceFieldBuffers> field;      // the one set of output buffers DistanceField fills for this volume
   std::unique_ptr<Tracer> tracer;
   std::unique_ptr<DepthIntegrator> integrator;
   std::unique_ptr<ReplayExtractor> extractor;
 
+  DistanceFieldBuffers& TheField()
+  {
+    if (!field) field.reset(new DistanceFieldBuffers());
+    return *field;
+  }
   Tracer& TheTracer()
   {
     if (!tracer) tracer.reset(new Tracer(volume));
@@ -277,7 +332,9 @@ class Replay
       {
         Kept& kept = kept_[shape.name];
         kept.shape = shape;
-        kept.volume = Construct(shape);
+        const std::shared_ptr<ReplayVolume> made = Construct(shape);
+        kept.volume = made;
+        kept.reach = made.get();
         // the counterpart of api.Volume.upload: the eight buffers as the files hold them, each of exactly the buffer's size
         for (const BufferOf& buffer : Buffers(*kept.volume))
         {
@@ -295,12 +352,16 @@ class Replay
       const Volume* other = step.Has("source") ? Of(step.Get("source")).volume.get() : nullptr;
       if (dirt_.fill != kAsAllocated && op != "frame" && op != "second_volume")
       {
-        on.volume->Expect(step, other);
+        if (on.reach) on.reach->Expect(step, other);
+        if ((op == "pack_merge" || op == "load") && Of(step.Get("source")).reach) Of(step.Get("source")).reach->ExpectPack();
         if (op == "extract") on.TheExtractor().Expect();
         for (auto& entry : kept_)
         {
-          entry.second.volume->Overwrite(dirt_);
+          if (entry.second.reach) entry.second.reach->Overwrite(dirt_);
           if (entry.second.extractor) entry.second.extractor->Overwrite(dirt_);
+          Soil(dirt_, entry.second.TheField().classes);
+          Soil(dirt_, entry.second.TheField().distance);
+          Soil(dirt_, entry.second.TheField().squared_cells);
         }
       }
       if (op == "integrate_rays") IntegrateRays(step, on);
@@ -309,6 +370,10 @@ class Replay
       else if (op == "release_blocks") ReleaseBlocks(step, on);
       else if (op == "merge") Merge(step, on, *other);
       else if (op == "merge_posed") MergePosed(step, on, *other);
+      else if (op == "merge_resampled") MergeResampled(step, on, *other);
+      else if (op == "pack_merge") PackMerge(step, on, *other);
+      else if (op == "load") Load(step, on, *other);
+      else if (op == "distance_field") DistanceField(step, on);
       else if (op == "frame") FrameStep(step, on);
       else if (op == "raycast") Raycast(step, on);
       else if (op == "sample") Sample(step, on);
@@ -462,6 +527,83 @@ class Replay
       Write(step.index, "counts", counts, sizeof(counts));
     }
 
+    void MergeResampled(const chain::Step& step, Kept& on, const Volume& other)
+    {
+      MergeOptions options;
+      options.max_rounds = step.Int("max_rounds");
+      options.skip_unobserved = step.Flag("skip_unobserved");
+      const MergePoseCounts c = on.volume->MergeResampled(other, PoseOf(step.Get("pose")), step.Int("supersample"), options);
+      const int32_t counts[8] = {c.considered, c.candidates, c.fused, c.allocated, c.left_out, c.rounds, c.skipped, c.sampled};
+      Write(step.index, "counts", counts, sizeof(counts));
+    }
+
+    void PackMerge(const chain::Step& step, Kept& on, const Volume& other)
+    {
+      PackOptions rule;
+      rule.skip_unobserved = step.Flag("skip_unobserved");
+      rule.box = step.Flag("box");
+      const std::vector<std::string> lo = step.Names("lo"), hi = step.Names("hi");
+      if (lo.size() != 3 || hi.size() != 3) throw chain::Error("a box has three coordinates a corner");
+      for (int a = 0; a < 3; ++a)
+      {
+        rule.lo[a] = int16_t(chain::Integer(lo[a]));
+        rule.hi[a] = int16_t(chain::Integer(hi[a]));
+      }
+      const PackedVolume pack = other.Pack(rule);
+      MergeOptions options;
+      options.max_rounds = step.Int("max_rounds");
+      const MergeCounts c = on.volume->Merge(pack, options);
+      const int32_t counts[6] = {c.considered, c.fused, c.allocated, c.left_out, c.rounds, c.skipped};
+      Write(step.index, "counts", counts, sizeof(counts));
+      WriteDevice(step.index, "origins", pack.GetOrigins().GetData(), size_t(pack.Count()) * 4 * sizeof(int16_t));
+      WriteDevice(step.index, "voxels", pack.GetVoxels().GetData(), size_t(pack.Count()) * VK_BLOCK_VOXELS * sizeof(vk_voxel));
+    }
+
+    // the source packed whole and saved; the file loaded as a new Volume of the sizes of `on`, which takes its place
+    void Load(const chain::Step& step, Kept& on, const Volume& other)
+    {
+      const PackedVolume pack = other.Pack();
+      const std::string path = Path(step.index, "map");
+      pack.Save(path);
+      const std::shared_ptr<Volume> loaded = Volume::Load(path, on.shape.main, on.shape.excess);
+      loaded->SetDepthRange(on.shape.depth_min, on.shape.depth_max);
+      on.tracer.reset();
+      on.integrator.reset();
+      on.extractor.reset();
+      on.volume = loaded;
+      on.reach = nullptr;
+      on.field.reset();
+      const int32_t counts[1] = {pack.Count()};
+      Write(step.index, "counts", counts, sizeof(counts));
+    }
+
+    void DistanceField(const chain::Step& step, Kept& on)
+    {
+      CellGrid grid;
+      const std::vector<std::string> origin = step.Names("origin"), dims = step.Names("dims");
+      if (origin.size() != 3 || dims.size() != 3) throw chain::Error("a grid has three coordinates and three sizes");
+      for (int a = 0; a < 3; ++a)
+      {
+        grid.origin[a] = chain::Integer(origin[a]);
+        grid.dims[a] = chain::Integer(dims[a]);
+      }
+      grid.stride = step.Int("stride");
+      DistanceFieldOptions options;
+      options.site_mask = step.Int("sites");
+      options.max_cells = step.Int("max_cells");
+      options.is_signed = step.Flag("signed");
+      options.squared = true;
+      const Volume& volume = *on.volume;                 // DistanceField is const: field_workspace_ is resized behind it
+      DistanceFieldBuffers& field = on.TheField();
+      volume.DistanceField(grid, options, field);
+      const size_t cells = grid.Cells();
+      if (field.classes.GetSize() != cells || field.distance.GetSize() != cells || field.squared_cells.GetSize() != cells)
+        throw chain::Error("the field's buffers are not of the grid's size");
+      WriteDevice(step.index, "classes", field.classes.GetData(), cells);
+      WriteDevice(step.index, "squared_cells", field.squared_cells.GetData(), cells * sizeof(int));
+      WriteDevice(step.index, "distance", field.distance.GetData(), cells * sizeof(float));
+    }
+
     // the frame a raycast fills: the camera of the step, images of its size
     Frame Target(const chain::Step& step) const
     {
@@ -589,7 +731,8 @@ class Replay
     void Loop(const chain::Step& step, Kept& on, bool rays, const Registration& result)
     {
       int32_t ints[10];
-      on.volume->LoopInts(rays, ints);
+      if (!on.reach) throw chain::Error("the loop's own buffers of a loaded volume cannot be reached");
+      on.reach->LoopInts(rays, ints);
       ints[6] = result.steps;
       ints[7] = result.converged ? 1 : 0;
       ints[8] = result.overlap ? 1 : 0;
@@ -626,6 +769,8 @@ class Replay
       on.integrator.reset();
       on.extractor.reset();
       on.volume = second;
+      on.reach = second.get();
+      on.field.reset();
     }
 
     void DumpState(int index, const std::string& name, const Volume& volume) const
